@@ -191,6 +191,27 @@ def run_cpu_baseline(full_size, reps=5, warm=2):
     return out
 
 
+DUMP_MAX_ELEMS = 7 << 20   # per array: 28 MB of fp32, so the two parameter-sized arrays stay under 64 MB together
+
+
+def dump_outputs(out_dir, net):
+    """What a caller of the timed step receives after its last call: read_metrics() (loss, accuracy over all / over
+    non-zero voxels), get_gradients() and the post-Adam get_variables(), each flattened in variable_names() order.
+    An array longer than DUMP_MAX_ELEMS is replaced by a fixed sample: sorted indices drawn by a generator seeded with
+    0, which depend only on the array's length, so two builds dump the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = net.variable_names()
+    arrays = {"metrics": np.asarray(net.read_metrics(), np.float64)}
+    for tag, values in (("gradients", net.get_gradients()), ("variables", net.get_variables())):
+        arrays[tag] = np.concatenate([values[k].reshape(-1) for k in names]).astype(np.float32)
+    for tag, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, tag + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N-rank job as a CHILD process (nothing in this
     process has touched the GPU yet -- never re-exec a process that has) and relay its JSON line and exit code."""
@@ -226,11 +247,16 @@ def main():
     ap.add_argument("--secondary-workload", default="", choices=[""] + sorted(WORKLOADS),
                     help="workload of the secondary leg (default: cfg5_3d256_f8_b4_bf16 behind the default cfg3 run; naming one "
                          "attaches it to any primary workload -- the N > 1 rehearsal uses the tiny pair)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what their last step computed (metrics, gradients, post-Adam "
+                         "variables) as DIR/<name>.npy, so that two builds can be compared output for output")
     ap.add_argument("--cpu-baseline-child", default="")
     ap.add_argument("--cpu-size", type=int, default=192)
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--cpu-warm", type=int, default=2)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_child:
         return cpu_baseline_child(args.cpu_baseline_child, args.cpu_size, args.cpu_reps, args.cpu_warm)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -298,6 +324,8 @@ def main():
         step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, net)
     # Roofline leg: per-kernel durations with HIP events on the launch stream.  The timed region above runs the
     # weight gradients on a second stream, where concurrent kernels time-slice and an event interval includes the
     # partner's work; so the same steps are repeated with that overlap switched off and every launch bracketed.

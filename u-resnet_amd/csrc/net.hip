@@ -1080,9 +1080,11 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
   }
   // hipGraph replay (opt-in experiment).  cfg1 (2-D 256^2 x 4) issues ~560 launches per 5.7 ms step and the host needs 5.5 ms to
   // enqueue them (tools/host_enqueue_probe.py), so the step looked launch-bound.  With URSN_GRAPH >= 1 the third call with the same
-  // buffers and batch captures the step's launches -- both streams, the events between them -- into a hipGraph on a stream of the
-  // library's own, and later calls are ONE graph launch.  Measured on ROCm 7.2: the replay takes 10.7 ms per step against 5.7 ms
-  // of ordinary launches (the runtime orders the nodes more strictly than the two streams do), so it is OFF by default.
+  // buffers and batch captures the step's launches into a hipGraph on a stream of the library's own, and later calls are ONE graph
+  // launch.  Measured on ROCm 7.2 (both streams captured): the replay takes 10.7 ms per step against 5.7 ms of ordinary launches
+  // (the runtime orders the nodes more strictly than the two streams do), so it is OFF by default.  The capture now runs with the
+  // second stream off, one chain of nodes: for a graph with forked branches the HIP 7.0 runtime's hipGraphLaunch reads past its
+  // pool of branch streams and faults on the host.
   // URSN_GRAPH=1: when the batch holds <= 2^20 voxels, 2: always.  Never while profiling (events per launch).
   static const int gmode = getenv("URSN_GRAPH") ? atoi(getenv("URSN_GRAPH")) : 0;
   bool geligible = gmode > 0 && !net->profile && !net->graph_broken && !ursn_roctx_on() &&
@@ -1128,7 +1130,10 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
     } else if (++sg->seen >= 3) {
       hipGraph_t graph = nullptr;
       bool ok = hipStreamBeginCapture(net->gstream, hipStreamCaptureModeRelaxed) == hipSuccess;
+      hipStream_t s2_keep = net->s2;
+      net->s2 = nullptr;
       int rc = ok ? run_on(net->gstream) : 1;
+      net->s2 = s2_keep;
       if (ok) ok = hipStreamEndCapture(net->gstream, &graph) == hipSuccess && graph != nullptr;
       if (ok && rc == 0) ok = hipGraphInstantiate(&sg->exec, graph, nullptr, nullptr, 0) == hipSuccess;
       if (graph) (void)hipGraphDestroy(graph);
