@@ -336,8 +336,11 @@ def loss_and_metrics(logits, data, label, weight=None):
 
     label is fed as float and cast to int64 (lib/ssnet.py:32,40).  loss = mean over
     batch of the per-image sum of (weight *) CE (:67-71).  acc_nonzero masks on
-    data > 0 (:59-62; requires one input channel).  argmax returns the lowest
-    index among ties (np.argmax does as well)."""
+    data > 0 (:59-62).  With more than one input channel accuracy_nonzero is NaN:
+    the reference's tf.reshape(data, shape_dim[:-1]) (lib/ssnet.py:59) has no
+    defined meaning there (its element count differs from the label's), and the
+    product reports NaN as well.  argmax returns the lowest index among ties
+    (np.argmax does as well)."""
     N = logits.shape[0]
     lab = np.asarray(label).reshape(logits.shape[:-1]).astype(np.int64)
     p = softmax(logits)
@@ -352,8 +355,12 @@ def loss_and_metrics(logits, data, label, weight=None):
     loss = ce.reshape(N, -1).sum(axis=1).mean()
     pred = np.argmax(logits, axis=-1)
     acc_all = float((pred == lab).mean())
-    nz = np.asarray(data).reshape(lab.shape) > 0
-    acc_nonzero = float((pred[nz] == lab[nz]).mean()) if nz.any() else float("nan")
+    d = np.asarray(data)
+    if d.size != lab.size:   # more than one input channel
+        acc_nonzero = float("nan")
+    else:
+        nz = d.reshape(lab.shape) > 0
+        acc_nonzero = float((pred[nz] == lab[nz]).mean()) if nz.any() else float("nan")
     onehot = np.zeros_like(p)
     np.put_along_axis(onehot, lab[..., None], 1.0, axis=-1)
     dlogits = (p - onehot) / N

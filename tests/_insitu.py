@@ -21,11 +21,12 @@ import numpy as np
 from oracle import uresnet_np as O
 
 
-def topology(F, ns):
+def topology(F, ns, cin=1):
     """Forward order of lib/uresnet.py:22-123 as the oracle walks it: ('layer', name, kind, stride, relu, inputs, act) and
-    ('unit', scope, inputs, cout, stride).  inputs = names of the activations that are concatenated (tf.concat order)."""
+    ('unit', scope, inputs, cout, stride).  inputs = names of the activations that are concatenated (tf.concat order).
+    cin = input channels (dims[-1])."""
     U = "UResNet/"
-    ops, width = [], {"data": 1}
+    ops, width = [], {"data": cin}
     ops.append(("layer", U + "conv0", "conv", 1, True, ["data"], U + "conv0"))
     net, C = U + "conv0", F
     width[net] = F
@@ -176,7 +177,7 @@ class InSitu(object):
         self.net, self.P, self.dims, self.F, self.ncls, self.ns, self.bf16, self.eps = net, P, tuple(dims), F, ncls, ns, bf16, eps
         self.q = O.bf16_round if bf16 else (lambda a: a)
         self.data, self.label, self.weight = O.reshape_inputs(dims, data, label, weight)
-        self.ops, self.width = topology(F, ns)
+        self.ops, self.width = topology(F, ns, cin=self.dims[-1])
         self.tol = Tol(bf16)
         self.grads = net.get_gradients()
         self._cache = {}

@@ -142,6 +142,8 @@ def test_loss_metrics_and_ana_rule():
     ce = -np.log(O.softmax(logits))[0, [0, 1], [0, 1]]
     assert m["loss"] == pytest.approx((ce * weight[0]).sum())
     assert np.isnan(O.loss_and_metrics(logits, np.zeros((1, 2)), label)["acc_nonzero"])
+    assert np.isnan(O.loss_and_metrics(logits, np.ones((1, 2, 2)), label)["acc_nonzero"])   # two input channels: undefined
+    assert O.loss_and_metrics(logits, np.ones((1, 2, 2)), label)["acc_all"] == 0.5
     sm = np.array([[0.2, 0.5, 0.3], [0.2, 0.3, 0.5], [0.2, 0.4, 0.4]])
     assert O.ana_label_rule(sm, np.array([5.0, 5.0, 0.5])).tolist() == [1.0, 2.0, 0.0]
     assert O.ana_label_rule(sm, np.array([5.0, 5.0, 5.0])).tolist() == [1.0, 2.0, 2.0]

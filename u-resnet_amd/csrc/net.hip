@@ -50,7 +50,8 @@ struct Layer {
   ursn_conv_desc desc;
   float *z = nullptr, *dz = nullptr, *mean = nullptr, *rstd = nullptr;
   float* coef = nullptr;   // [6][zcs]: BatchNorm-backward apply coefficients for the data-gradient kernel (ursn_conv_desc.vdz_coef)
-  int zcs = 0;  // channel stride of z / dz: cout rounded up to 4 (only conv2's 3|5 classes differ), pad lanes stay 0
+  int zcs = 0;  // channel stride of z / dz: cout rounded up to 4 (conv2's class count, and every layer whose width is not a
+                // multiple of 4), pad lanes stay 0
 };
 
 struct Unit {
@@ -186,8 +187,10 @@ int plan(ursn_net* n, Arena& A) {
   // the decoder scopes are the reference's literal 'resnet_module%d' % (step + 5) (lib/uresnet.py:100): with more than 5
   // strides they collide with the encoder's names (TensorFlow raises on the duplicate variable scope as well)
   URSN_REQUIRE(c.num_strides >= 1 && c.num_strides <= 5, "num_strides %d out of range [1,5]", c.num_strides);
-  URSN_REQUIRE(c.cin >= 1 && c.base_filters >= 1 && c.num_class >= 1 && c.num_class <= 8 && c.max_batch >= 1,
-               "bad channel / class / batch configuration");
+  URSN_REQUIRE(c.cin >= 1, "input channels (dims[-1]) must be >= 1, got %d", c.cin);
+  URSN_REQUIRE(c.base_filters >= 1, "base_num_outputs must be >= 1, got %d", c.base_filters);
+  URSN_REQUIRE(c.num_class >= 1 && c.num_class <= 8, "num_class %d out of range [1,8] (the head's 8-channel logits piece)", c.num_class);
+  URSN_REQUIRE(c.max_batch >= 1, "max_batch must be >= 1, got %d", c.max_batch);
   const int ns = c.num_strides;
   n->nlev = ns + 1;
   for (int l = 0; l <= ns; ++l) {
@@ -519,7 +522,7 @@ int bn_out(ursn_net* n, int li, const Act& out, int relu, int N, int li2, const 
   a.z = L.z; a.zcs = L.zcs; a.mean = L.mean; a.rstd = L.rstd; a.beta = n->params + L.b_off;
   if (li2 >= 0) {
     Layer& L2 = n->layers[li2];
-    a.z2 = L2.z; a.z2cs = L2.cout; a.mean2 = L2.mean; a.rstd2 = L2.rstd; a.beta2 = n->params + L2.b_off;
+    a.z2 = L2.z; a.z2cs = L2.zcs; a.mean2 = L2.mean; a.rstd2 = L2.rstd; a.beta2 = n->params + L2.b_off;
   }
   a.res = res; a.rescs = rescs;
   a.y = out.p; a.ycs = out.cs; a.V = (int64_t)N * n->lvox[L.lout]; a.C = L.cout; a.relu = relu;
@@ -776,7 +779,7 @@ int bn_back(ursn_net* n, int li, const float* dy, int dycs, const float* y, int 
   a.beta = n->params + L.b_off;
   if (li2 >= 0) {
     Layer& L2 = n->layers[li2];
-    a.z2 = L2.z; a.z2cs = L2.cout; a.mean2 = L2.mean; a.rstd2 = L2.rstd; a.dz2 = L2.dz; a.dz2cs = L2.cout;
+    a.z2 = L2.z; a.z2cs = L2.zcs; a.mean2 = L2.mean; a.rstd2 = L2.rstd; a.dz2 = L2.dz; a.dz2cs = L2.zcs;
     a.dbeta2 = n->grads + L2.b_off;
   }
   a.dres = dres; a.drescs = drescs; a.dres_accumulate = dres_acc;
@@ -1001,12 +1004,12 @@ extern "C" int ursn_create(const ursn_config* cfg, float* params, float* grads, 
     size_t bytes = (size_t)n->cfg.max_batch * n->lvox[L.lout] * L.zcs * sizeof(float);
     if (hipMemset(L.mean, 0, L.zcs * sizeof(float)) != hipSuccess || hipMemset(L.rstd, 0, L.zcs * sizeof(float)) != hipSuccess ||
         hipMemset(L.z, 0, bytes) != hipSuccess || (L.dz && hipMemset(L.dz, 0, bytes) != hipSuccess)) {
-      ursn_set_error("create: hipMemset of padded logits buffers failed");
+      ursn_set_error("create: hipMemset of the padded z / dz buffers of %s failed", L.name.c_str());
       delete n;
       return 1;
     }
   }
-  if (n->dlog) {  // pad lanes of the logits gradient (3|5 classes in 4|8 channels) must be finite: the BN backward runs over them
+  if (n->dlog) {  // pad lanes of the logits gradient (1-3 | 5-7 classes in 4 | 8 channels) must be finite: the BN backward runs over them
     const Layer& LL = n->layers[n->conv2];
     if (hipMemset(n->dlog, 0, (size_t)n->cfg.max_batch * n->lvox[0] * LL.zcs * sizeof(float)) != hipSuccess) {
       ursn_set_error("create: hipMemset of the logits gradient failed");

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -56,6 +57,7 @@ struct BLayer {
   // pass still runs as several launches), so that one launch at the start of a step can fill them all (bf16_pack.h)
   bf16_t* wp[2] = {nullptr, nullptr};
   size_t wp_elems[2] = {0, 0}, wp_stride[2] = {0, 0};
+  std::vector<int> vcs;   // input channel strides of the views the layer runs on (compact kin first): the packs are sized over all
 };
 
 struct BUnit {
@@ -196,7 +198,8 @@ int plan(ursn_bnet* n, Arena& A) {
   URSN_REQUIRE(c.num_strides >= 1 && c.num_strides <= 5, "num_strides %d out of range [1,5]", c.num_strides);
   URSN_REQUIRE(c.cin == 1, "bf16 path: one input channel (the reference's data), got %d", c.cin);
   URSN_REQUIRE(c.base_filters >= 8 && c.base_filters % 8 == 0, "bf16 path: base_num_outputs must be a multiple of 8, got %d", c.base_filters);
-  URSN_REQUIRE(c.num_class >= 1 && c.num_class <= 8 && c.max_batch >= 1, "bad class / batch configuration");
+  URSN_REQUIRE(c.num_class >= 1 && c.num_class <= 8, "num_class %d out of range [1,8] (the head's 8-channel logits piece)", c.num_class);
+  URSN_REQUIRE(c.max_batch >= 1, "max_batch must be >= 1, got %d", c.max_batch);
   const int ns = c.num_strides, F = c.base_filters;
   const bool tr = c.trainable != 0;
   n->nlev = ns + 1;
@@ -304,14 +307,33 @@ int plan(ursn_bnet* n, Arena& A) {
   n->metrics = (float*)A.take(8 * sizeof(float));
   n->beta_pad = (float*)A.take(8 * sizeof(float));
   n->head_scratch = A.take(head_scratch_bytes(c.max_batch, n->lvox[0]) + 64);
+  // the layers run on views whose channel stride can differ from their compact kin (a level's feature map is the second half
+  // of its concat buffer; a virtual input is staged at its producer's stride), and the kernel family, hence the size of the
+  // packed weights, is chosen from the view: size the packs over every stride a layer is launched with
+  for (BLayer& L : n->layers) L.vcs.assign(1, L.kin);
+  auto runs_on = [&](int li, const BAct& in) {
+    std::vector<int>& v = n->layers[li].vcs;
+    for (int cs : {in.cs, in.aff_layer >= 0 ? n->layers[in.aff_layer].kout : 0})
+      if (cs > 0 && std::find(v.begin(), v.end(), cs) == v.end()) v.push_back(cs);
+  };
+  for (const BUnit& u : n->units) {
+    if (u.sc >= 0) runs_on(u.sc, u.in);
+    runs_on(u.c1, u.in);
+    runs_on(u.c2, u.a1);
+  }
+  for (int i = 0; i < ns; ++i) runs_on(n->deconv[i], n->deconv_in[i]);
+  runs_on(n->conv0, n->a_data);
+  runs_on(n->conv1, n->a_pre1);
+  runs_on(n->conv2, n->a_conv1);
   size_t st = 0, bn = 0, wg = 0;
   for (BLayer& L : n->layers) {
     const size_t b = bbn_scratch_bytes((int64_t)c.max_batch * n->lvox[L.lout], L.kout);
     if (b > bn) bn = b;
-    for (int nb = 1; nb <= c.max_batch; ++nb) {   // the launch geometry is chosen per call from the batch actually fed
+    for (int nb = 1; nb <= c.max_batch; ++nb)   // the launch geometry is chosen per call from the batch actually fed
+    for (int ics : L.vcs) {
       GatherGeom g[8];
       for (int pass = 0; pass < (tr ? 3 : 1); ++pass) {
-        const int cnt = layer_geoms(n, L, (ConvPass)pass, nb, L.kin, L.kout, g);
+        const int cnt = layer_geoms(n, L, (ConvPass)pass, nb, ics, L.kout, g);
         URSN_REQUIRE(cnt >= 1, "bf16 plan: bad geometry for %s", L.name.c_str());
         size_t stl = 0, wpl = 0, wps = 0;   // this pass: statistics doubles, packed elements (all classes), class stride
         if (pass != PASS_WGRAD && bdeconv_ok(g, cnt)) {
@@ -359,7 +381,8 @@ int plan(ursn_bnet* n, Arena& A) {
       if (L.wp_stride[pass] * 8 > L.wp_elems[pass] && L.wp_stride[pass] > 0) {
         GatherGeom g[8];
         int cmax = 1;
-        for (int nb = 1; nb <= c.max_batch; ++nb) { const int cc = layer_geoms(n, L, (ConvPass)pass, nb, L.kin, L.kout, g); if (cc > cmax) cmax = cc; }
+        for (int nb = 1; nb <= c.max_batch; ++nb)
+          for (int ics : L.vcs) { const int cc = layer_geoms(n, L, (ConvPass)pass, nb, ics, L.kout, g); if (cc > cmax) cmax = cc; }
         if (L.wp_stride[pass] * cmax > L.wp_elems[pass]) L.wp_elems[pass] = L.wp_stride[pass] * cmax;
       }
       L.wp[pass] = (bf16_t*)A.take(L.wp_elems[pass] * sizeof(bf16_t) + 256);
@@ -427,6 +450,15 @@ double blayer_bytes(const ursn_bnet* n, const BLayer& L, int N) {
   return 2.0 * ((double)N * n->lvox[L.lin] * L.cin + (double)N * n->lvox[L.lout] * L.cout) + 4.0 * taps * L.cin * L.cout;
 }
 
+// the weights a launcher packs at L.wp[pass] + off (elems, from the family chosen at run time) must lie inside the buffer plan()
+// sized, and inside one class stride where a pass runs as several launches
+int pack_fits(const BLayer& L, int pass, size_t elems, size_t off = 0, size_t stride = 0) {
+  URSN_REQUIRE(elems > 0 && off + elems <= L.wp_elems[pass] && (!stride || elems <= stride),
+               "bf16 %s: packed weights of pass %d (%zu elements at %zu, class stride %zu) exceed the planned buffer (%zu)",
+               L.name.c_str(), pass, elems, off, stride, L.wp_elems[pass]);
+  return 0;
+}
+
 const float* beta_of(ursn_bnet* n, const BLayer& L);
 int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, double* stats = nullptr) {
   if (!stats) stats = n->stats;
@@ -439,20 +471,24 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
   int total = 0, off = 0;
   if (bdeconv_ok(g, cnt)) {   // transposed conv 16 -> 8: the eight parity classes in one launch
     total = bdeconv_grid_blocks(g, cnt);
+    URSN_TRY(pack_fits(L, 0, bdeconv_pack_elems()));
     URSN_TRY(launch_bdeconv(g, cnt, in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, s));
     return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
   }
   if (bsconv_ok(g, cnt)) {   // transposed convs of the deeper levels: the eight parity classes in one launch
+    URSN_TRY(pack_fits(L, 0, bsconv_pack_elems(g, cnt)));
     URSN_TRY(launch_bsconv(g, cnt, in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, s));
     return bsconv_stats_finalize(g, cnt, stats, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
   }
   if (cnt == 1 && !in.in_f32 && in.aff_layer < 0 && bs2k8_ok(g[0])) {   // stride-2 gather 8 -> 16 (without a shortcut beside it)
     total = bs2k8_grid_blocks(g[0]);
+    URSN_TRY(pack_fits(L, 0, bs2k8_pack_elems()));
     URSN_TRY(launch_bs2k8(g[0], in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, nullptr, nullptr, 0, s));
     return launch_bn_stats_final(stats, total, g[0].Nn, 16, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
   }
   if (in.in_f32 && cnt == 1 && b0conv_ok(g[0])) {   // conv0 on the raw fp32 input: the taps are the contraction (bf16_conv0.hip)
     total = b0conv_grid_blocks(g[0]);
+    URSN_TRY(pack_fits(L, 0, b0conv_pack_elems()));
     URSN_TRY(launch_b0conv(g[0], in.in_f32, n->params + L.w_off, Nw, L.wp[0], L.z, stats, s));
     return launch_bn_stats_final(stats, total, g[0].Nn, 16, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
   }
@@ -460,6 +496,7 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
     URSN_REQUIRE(cnt == 1 && b3conv_ok(g[0]) && g[0].K == 8, "bf16 forward: %s cannot read a scalar fp32 input", L.name.c_str());
     total = bconv_grid_blocks(g[0]);
     g[0].accumulate = 0;
+    URSN_TRY(pack_fits(L, 0, b3conv_pack_elems()));
     URSN_TRY(launch_b3conv(g[0], nullptr, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, total, s, nullptr, 0, nullptr, nullptr,
                            nullptr, nullptr, 0, in.in_f32));
     return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
@@ -471,6 +508,7 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
     B3Affine af = {P.mean, P.rstd, beta_of(n, P), in.aff_relu};
     total = bconv_grid_blocks(g[0]);
     g[0].accumulate = 0;
+    URSN_TRY(pack_fits(L, 0, b3conv_pack_elems()));
     URSN_TRY(launch_b3conv(g[0], P.z, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, total, s, nullptr, 0, nullptr, nullptr, &af));
     return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
   }
@@ -478,6 +516,7 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
   URSN_REQUIRE(total > 0, "bf16 forward: no kernel for %s", L.name.c_str());
   for (int i = 0; i < cnt; ++i) {
     g[i].accumulate = 0;
+    URSN_TRY(pack_fits(L, 0, bconv_pack_elems(g[i]), (size_t)i * L.wp_stride[0], cnt > 1 ? L.wp_stride[0] : 0));
     URSN_TRY(launch_bconv(g[i], in.p, n->params + L.w_off, Kw, Nw, L.wp[0] + (size_t)i * L.wp_stride[0], L.z, stats, off, total, s));
     off += bconv_grid_blocks(g[i]);
   }
@@ -529,6 +568,7 @@ int unit_fwd(ursn_bnet* n, BUnit& u, int N, hipStream_t s) {
       real_extents(L, PASS_FWD, Kw, Nw);
       BProf ps(n, s, u.c1, 0, blayer_flops(n, L, N) + blayer_flops(n, S, N), blayer_bytes(n, L, N) + 2.0 * N * n->lvox[S.lout] * S.cout);
       const int blocks = bs2k8_grid_blocks(g[0]);
+      URSN_TRY(pack_fits(L, 0, bs2k8_pack_elems()));
       URSN_TRY(launch_bs2k8(g[0], u.in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, n->stats, 0, n->params + S.w_off, S.z, S.kout, s));
       const int64_t V = (int64_t)N * n->lvox[L.lout];
       URSN_TRY(launch_bn_stats_final(n->stats, blocks, 16, 16, V, n->cfg.bn_eps, L.mean, L.rstd, s));
@@ -706,6 +746,7 @@ int conv_bwd(ursn_bnet* n, int li, const BAct& in, bool need_dgrad, int N, hipSt
   if (res) {   // identity unit: the residual branch's share rides in this launch (unit_bwd checked the shape)
     URSN_REQUIRE(cnt == 1 && !acc && fused_sc < 0 && b3conv_ok(g[0]) && g[0].K == g[0].Nn, "bf16 backward: %s cannot carry the residual term", L.name.c_str());
     g[0].accumulate = 0;
+    URSN_TRY(pack_fits(L, 1, b3conv_pack_elems()));
     return launch_b3conv(g[0], L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, 0, 0, s, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0,
                          nullptr, res);
   }
@@ -723,6 +764,7 @@ int conv_bwd(ursn_bnet* n, int li, const BAct& in, bool need_dgrad, int N, hipSt
       }
       r.partial = n->bs_scratch;
       g[0].accumulate = acc ? 1 : 0;
+      URSN_TRY(pack_fits(L, 1, b3conv_pack_elems()));
       URSN_TRY(launch_b3conv(g[0], L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, 0, 0, s, nullptr, 0, nullptr, &r));
       n->bs_layer = bs->li; n->bs_blocks = blocks;
       return 0;
@@ -733,12 +775,14 @@ int conv_bwd(ursn_bnet* n, int li, const BAct& in, bool need_dgrad, int N, hipSt
     URSN_REQUIRE(S.k == 1 && S.stride == 1 && S.kout == g[0].K && S.cout == S.kout && S.kin == g[0].Nn && S.cin == S.kin,
                  "bf16 backward: shortcut of %s does not match its data gradient", L.name.c_str());
     g[0].accumulate = acc ? 1 : 0;
+    URSN_TRY(pack_fits(L, 1, bcbconv_pack_elems(g[0])));
     return launch_bcbconv(g[0], L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, s, S.dz, S.kout, n->params + S.w_off);
   }
   if (fused_sc >= 0) {
     const BLayer& S = n->layers[fused_sc];
     URSN_REQUIRE(cnt == 1 && b3conv_pw_ok(g[0]) && S.kin == 16 && S.cin == 16 && S.cout == 8 && S.kout == 8, "bf16 backward: no fused shortcut term for %s", L.name.c_str());
     g[0].accumulate = acc ? 1 : 0;
+    URSN_TRY(pack_fits(L, 1, b3conv_pack_elems()));
     if (n->dec0_g && in.g == n->cat[n->cfg.num_strides - 1].g && !acc) {   // level-0 concat gradient: two 8-channel tensors
       g[0].out_cs = 8;
       n->split0_done = true;
@@ -748,15 +792,22 @@ int conv_bwd(ursn_bnet* n, int li, const BAct& in, bool need_dgrad, int N, hipSt
     }
     return launch_b3conv(g[0], L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, 0, 0, s, S.dz, S.kout, n->params + S.w_off);
   }
-  if (bdeconv_ok(g, cnt))   // stride-2 conv 8 -> 16: the eight parity classes of its data gradient in one launch
+  if (bdeconv_ok(g, cnt)) {   // stride-2 conv 8 -> 16: the eight parity classes of its data gradient in one launch
+    URSN_TRY(pack_fits(L, 1, bdeconv_pack_elems()));
     return launch_bdeconv(g, cnt, L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, acc ? 1 : 0, s);
-  if (cnt == 1 && fused_sc < 0 && bs2k8_ok(g[0]))   // transposed conv 16 -> 8: its data gradient is a stride-2 gather 8 -> 16
+  }
+  if (cnt == 1 && fused_sc < 0 && bs2k8_ok(g[0])) {   // transposed conv 16 -> 8: its data gradient is a stride-2 gather 8 -> 16
+    URSN_TRY(pack_fits(L, 1, bs2k8_pack_elems()));
     return launch_bs2k8(g[0], L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, acc ? 1 : 0, nullptr, nullptr, 0, s);
-  if (bsconv_ok(g, cnt))   // stride-2 convs of the deeper levels: likewise
+  }
+  if (bsconv_ok(g, cnt)) {   // stride-2 convs of the deeper levels: likewise
+    URSN_TRY(pack_fits(L, 1, bsconv_pack_elems(g, cnt)));
     return launch_bsconv(g, cnt, L.dz, n->params + L.w_off, Kw, Nw, L.wp[1], in.g, nullptr, acc ? 1 : 0, s);
+  }
   for (int i = 0; i < cnt; ++i) {
     if (g[i].ntaps == 0) continue;
     g[i].accumulate = acc ? 1 : 0;
+    URSN_TRY(pack_fits(L, 1, bconv_pack_elems(g[i]), (size_t)i * L.wp_stride[1], cnt > 1 ? L.wp_stride[1] : 0));
     URSN_TRY(launch_bconv(g[i], L.dz, n->params + L.w_off, Kw, Nw, L.wp[1] + (size_t)i * L.wp_stride[1], in.g, nullptr, 0, 0, s));
   }
   return 0;
