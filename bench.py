@@ -11,9 +11,15 @@ F=8 U-ResNet at batch 4 per GPU, fp32.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-  roofline     -- the dominant kernel: algorithmic FLOPs / HIP-event launch durations vs the fp32 peak
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set up, warm up, time the steps, write
+--dump-outputs if asked, print.  --full then adds the measurements that take runs of their own, each as an object of the
+line (null without --full):
+  roofline     -- the dominant kernel: algorithmic FLOPs / HIP-event launch durations vs the fp32 peak, from a separate
+                  pass with the weight-gradient stream serialised (--breakdown / --layers print its tables)
+  step_parts   -- zero_gradients, all-reduce and Adam each timed alone
+  host_feed    -- the step fed from pinned host buffers (--host-feed)
   cpu_baseline -- the torch-CPU restatement of the reference graph (oracle "port") timed on the host
+  secondary    -- a second workload timed by a child job (cfg5 256^3 bf16 behind the default cfg3 run)
 """
 import argparse
 import json
@@ -233,6 +239,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg3_3d192_f8_b4", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what it does not need: the roofline pass, the step parts timed "
+                         "alone, the CPU baseline and the secondary workload (the options below that report from these "
+                         "legs need it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--breakdown", action="store_true", help="per-kernel time table on stderr")
     ap.add_argument("--layers", action="store_true", help="per-(layer, pass) time table on stderr")
@@ -257,6 +267,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    needs_full = [o for o, on in (("--breakdown", args.breakdown), ("--layers", args.layers), ("--host-feed", args.host_feed),
+                                  ("--secondary-workload", args.secondary_workload)) if on]
+    if needs_full and not args.full:
+        ap.error("%s report from the --full legs; add --full" % ", ".join(needs_full))
     if args.cpu_baseline_child:
         return cpu_baseline_child(args.cpu_baseline_child, args.cpu_size, args.cpu_reps, args.cpu_warm)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -326,6 +340,45 @@ def main():
     elapsed = time.perf_counter() - t0
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, net)
+    metrics = net.read_metrics()
+    per_rank = None
+    if world > 1:
+        # every rank's own clock over the SAME barrier-bracketed region and the device it bound: a straggler GPU or two ranks
+        # on one device show up in the line (the headline uses the maximum, as the contract asks)
+        mine = torch.tensor([elapsed, float(dev_index)], dtype=torch.float64, device=dev)
+        allr = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(allr, mine)
+        el = [float(a[0].item()) for a in allr]
+        per_rank = {"ms_per_step_min": round(min(el) / args.steps * 1e3, 3), "ms_per_step_max": round(max(el) / args.steps * 1e3, 3),
+                    "ms_per_step": [round(e / args.steps * 1e3, 3) for e in el], "device_index": [int(a[1].item()) for a in allr]}
+        elapsed = max(el)
+    ms_per_step = elapsed / args.steps * 1e3
+    value = batch * world * args.steps / elapsed
+
+    def result_line(parts=None, host_feed=None, roofline=None, cpu=None, secondary=None):
+        return {
+            "metric": "fwd+bwd images/sec on 3D 192^3x1 U-ResNet" if args.workload.startswith("cfg3")
+                      else "fwd+bwd images/sec (%s)" % args.workload,
+            "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
+            "config": {"workload": args.workload, "dims": list(dims), "base_filters": base, "num_class": ncls,
+                       "batch_per_gpu": batch, "global_batch": batch * world,
+                       "step": "zero_gradients+accum_gradients(fwd+loss+bwd)+allreduce+adam",
+                       "parallelism": "dp%d" % world, "backend": (args.backend if world > 1 else None)},
+            "ranks_seen": ranks_seen, "per_rank": per_rank,
+            "last_metrics": {"loss": metrics[0], "acc_all": metrics[1], "acc_nonzero": metrics[2]},
+            "step_parts": parts, "host_feed": host_feed,
+            "roofline": roofline, "cpu_baseline": cpu, "secondary": secondary,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line()))
+        if world > 1 and dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
     # Roofline leg: per-kernel durations with HIP events on the launch stream.  The timed region above runs the
     # weight gradients on a second stream, where concurrent kernels time-slice and an event interval includes the
     # partner's work; so the same steps are repeated with that overlap switched off and every launch bracketed.
@@ -339,18 +392,6 @@ def main():
     torch.cuda.synchronize()
     serial_ms_per_step = (time.perf_counter() - tp0) / prof_steps * 1e3
     _lib.check(lib.ursn_set_wgrad_overlap(net._handle, 1))
-    per_rank = None
-    if world > 1:
-        # every rank's own clock over the SAME barrier-bracketed region and the device it bound: a straggler GPU or two ranks
-        # on one device show up in the line (the headline uses the maximum, as the contract asks)
-        mine = torch.tensor([elapsed, float(dev_index)], dtype=torch.float64, device=dev)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        el = [float(a[0].item()) for a in allr]
-        per_rank = {"ms_per_step_min": round(min(el) / args.steps * 1e3, 3), "ms_per_step_max": round(max(el) / args.steps * 1e3, 3),
-                    "ms_per_step": [round(e / args.steps * 1e3, 3) for e in el], "device_index": [int(a[1].item()) for a in allr]}
-        elapsed = max(el)
-    metrics = net.read_metrics()
 
     # the non-conv parts of the step, each timed alone (Adam and the all-reduce reported separately)
     def timed_ms(fn, reps=5):
@@ -421,8 +462,6 @@ def main():
         if r.pass_ <= 2:
             t_roof_ms += max(r.flops / (PEAK_FP32_TFLOPS * 1e9), r.bytes / (PEAK_HBM_GBS * 1e6))
             conv_flops += r.flops; conv_bytes += r.bytes
-    ms_per_step = elapsed / args.steps * 1e3
-    value = batch * world * args.steps / elapsed
 
     # HBM traffic of the dominant kernel: PMC counters cannot be read from inside the process; the per-launch figure
     # comes from the committed rocprofv3 --pmc passes of this same command (profiles/pmc_traffic.json), else null
@@ -548,7 +587,7 @@ def main():
         # launcher variables of THIS rank must not leak into it.  The headline above is untouched.
         try:
             cmd = [sys.executable, os.path.abspath(__file__), "--workload", sec_wl, "--steps", str(args.steps),
-                   "--warmup", str(args.warmup), "--no-cpu-baseline", "--gpus", str(world), "--backend", args.backend]
+                   "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--gpus", str(world), "--backend", args.backend]
             cenv = {k: v for k, v in os.environ.items()
                     if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "ROLE_WORLD_SIZE",
                                  "MASTER_PORT", "TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT", "TORCHELASTIC_MAX_RESTARTS",
@@ -569,22 +608,7 @@ def main():
             secondary = {"workload": sec_wl, "error": repr(e)}
 
     if rank == 0:
-        out = {
-            "metric": "fwd+bwd images/sec on 3D 192^3x1 U-ResNet" if args.workload.startswith("cfg3")
-                      else "fwd+bwd images/sec (%s)" % args.workload,
-            "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
-            "config": {"workload": args.workload, "dims": list(dims), "base_filters": base, "num_class": ncls,
-                       "batch_per_gpu": batch, "global_batch": batch * world,
-                       "step": "zero_gradients+accum_gradients(fwd+loss+bwd)+allreduce+adam",
-                       "parallelism": "dp%d" % world, "backend": (args.backend if world > 1 else None)},
-            "ranks_seen": ranks_seen, "per_rank": per_rank,
-            "last_metrics": {"loss": metrics[0], "acc_all": metrics[1], "acc_nonzero": metrics[2]},
-            "step_parts": parts, "host_feed": host_feed,
-            "roofline": roofline, "cpu_baseline": cpu, "secondary": secondary,
-        }
-        print(json.dumps(out))
+        print(json.dumps(result_line(parts, host_feed, roofline, cpu, secondary)))
     if world > 1 and dist.is_initialized():
         dist.destroy_process_group()
 

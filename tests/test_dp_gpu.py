@@ -75,7 +75,7 @@ def test_bench_n2_path_two_ranks_on_one_gpu_over_gloo():
     ranks on the one GPU over gloo (--backend gloo; RCCL refuses two ranks on one device).  The 8-GPU RCCL run is the driver's."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--workload", "tiny_3d64_f8_b2", "--secondary-workload", "tiny_3d64_f8_b2_bf16",
                         "--backend", "gloo"], env=env, cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -98,3 +98,23 @@ def test_bench_n2_path_two_ranks_on_one_gpu_over_gloo():
     assert sec["workload"] == "tiny_3d64_f8_b2_bf16" and sec["dtype"] == "bf16" and sec["n_gpus"] == 2 and sec["ranks_seen"] == 2
     assert sec["config"]["global_batch"] == 4 and sec["value"] > 0 and sec["step_parts"]["allreduce_ms"] > 0
     assert len(sec["per_rank"]["ms_per_step"]) == 2
+
+
+def test_bench_plain_run_prints_the_headline_alone():
+    """Without --full the bench times its steps and prints the line, nothing more: the legs that take runs of their own
+    (roofline pass, step parts, CPU baseline, secondary workload) stay null, while the headline and the per-rank clocks of the
+    world > 1 path are there as with --full."""
+    import json
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--workload", "tiny_3d64_f8_b2", "--backend", "gloo"], env=env, cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.split("\n") if x.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "fwd+bwd images/sec (tiny_3d64_f8_b2)" and out["unit"] == "images/s" and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["n_gpus"] == 2 and out["ranks_seen"] == 2
+    assert out["value"] > 0 and abs(out["value"] - 4 * 2 / (out["ms_per_step"] * 2e-3)) < 1e-2 * out["value"]
+    assert len(out["per_rank"]["ms_per_step"]) == 2 and abs(out["per_rank"]["ms_per_step_max"] - out["ms_per_step"]) < 1e-2 * out["ms_per_step"]
+    assert all(out[k] is None for k in ("roofline", "step_parts", "host_feed", "cpu_baseline", "secondary"))

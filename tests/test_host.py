@@ -344,3 +344,13 @@ def test_library_is_built_from_the_sources_as_they_are():
         assert b.needs_build()
     finally:
         b.sources_digest = real
+
+
+def test_bench_options_that_report_from_the_full_legs_need_full():
+    """--breakdown, --layers, --host-feed and --secondary-workload print what only a --full run measures: without --full the bench
+    refuses them at the command line (before it touches a GPU) instead of silently dropping them."""
+    import subprocess
+    for opt in (["--breakdown"], ["--layers"], ["--host-feed"], ["--secondary-workload", "tiny_3d64_f8_b2_bf16"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + opt, cwd=ROOT, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=120)
+        assert p.returncode == 2 and "--full" in p.stderr and opt[0] in p.stderr, (opt, p.stderr[-500:])

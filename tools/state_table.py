@@ -1,4 +1,4 @@
-"""Current-state table for DESIGN.md from `bench.py --layers --breakdown` stderr logs: per kernel label its launches per step,
+"""Current-state table for DESIGN.md from `bench.py --full --layers --breakdown` stderr logs: per kernel label its launches per step,
 ms per step, the fraction of its own roofline (sum of max(F / P, B / BW) over its launches / its measured time) and the achieved
 rates.  usage: python tools/state_table.py profiles/r04_layers_cfg3.log [profiles/r04_pmc_mfma_busy_cfg3.json]"""
 import collections
