@@ -89,7 +89,18 @@ int ursn_query_concat(const ursn_config* cfg, int32_t step, char* first, char* s
 /* Replaces graph construction (lib/ssnet.py:20-89 + lib/uresnet.py:22-123).  The four flat
  * fp32 buffers (n_params floats each) and the workspace are caller-owned device memory;
  * `grads` is the accum_vars set (lib/ssnet.py:53-55), adam_m/adam_v the Adam slots.
- * grads/adam_m/adam_v may be NULL when cfg->trainable == 0. */
+ * grads/adam_m/adam_v may be NULL when cfg->trainable == 0.
+ *
+ * Contract of the workspace and of the calls below (pinned by tests/test_state_independence_gpu.py):
+ *   - the workspace needs NO initialisation: it may hold anything (zeros, NaNs, the remains of another plan) when it is
+ *     handed over.  ursn_create clears the few regions no kernel writes and some kernel reads; every other byte a call reads
+ *     was written earlier in the same call;
+ *   - between ursn_create and ursn_destroy the workspace belongs to the handle: the caller neither writes it nor relies on
+ *     its contents (ursn_tensor is a debug view of the LAST call);
+ *   - a call's results depend only on its arguments, the parameter / gradient / Adam buffers and the Adam step counter: not
+ *     on what the workspace held at create, not on the calls (kinds, batch sizes, inputs) the handle served before, and not
+ *     on whether the host synchronised between enqueues.  Two such calls give the same BITS (no atomics, fixed-order
+ *     reductions, streams ordered by events). */
 int ursn_create(const ursn_config* cfg, float* params, float* grads, float* adam_m, float* adam_v,
                 void* workspace, size_t workspace_bytes, ursn_net** out);
 int ursn_destroy(ursn_net* net);
