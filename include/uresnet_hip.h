@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define URSN_ABI_VERSION 7
+#define URSN_ABI_VERSION 8
 
 typedef struct ursn_net ursn_net; /* opaque */
 
@@ -321,6 +321,37 @@ int ursn_softmax_ce(const float* logits, const float* data, const float* label, 
 /* TF-form Adam on a flat buffer: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); p -= lr_t*m/(sqrt(v)+eps). */
 int ursn_adam(float* p, const float* g, float* m, float* v, int64_t nelem, float lr, float b1, float b2,
               float eps, int64_t t, void* stream);
+
+/* ---- voxel-list I/O (ABI 8; voxel_io.hip) -------------------------------------------------------------------------
+ * LArTPC events are almost empty and larcv hands them over as voxel lists; the reference also WRITES its 3-D ana product as a
+ * voxel set (lib/ssnet_trainval.py:299-302: larcv.as_tensor3d(ssnet_result) into a sparse3d product).  The network stays
+ * dense: these two stateless passes sit at its boundary.  Like the calls above, their results depend only on their arguments
+ * (no atomics, fixed-order scans; the scratch buffer needs no initialisation). */
+typedef struct ursn_voxel_batch {   /* all pointers are DEVICE pointers */
+  int32_t n;                 /* events */
+  int64_t voxels;            /* prod(spatial) of one event; cin == 1 */
+  const int64_t* offsets;    /* [n+1], offsets[0] = 0: event i owns list entries [offsets[i], offsets[i+1]) */
+  const int32_t* index;      /* [M] row-major voxel index inside the event, strictly increasing per event */
+  const float* value;        /* [M] data */
+  const float* label;        /* [M] class index as float (lib/ssnet.py:32,40) */
+  const float* weight;       /* [M], NULL iff the dense weight output is NULL */
+  const float* bg_weight;    /* [n] weight of every voxel NOT listed (inverse-frequency weights are non-zero on background) */
+} ursn_voxel_batch;
+
+/* dense data/label/weight [n, voxels] fp32 = background (0, 0, bg_weight[i]) overwritten at the listed voxels: the tensors
+ * ursn_accum_step / ursn_eval / ursn_infer_labels read (lib/ssnet.py:141-153 feed_dict).  A fill pass (16-byte stores over every
+ * byte of the outputs) and a scatter pass (an index outside [0, voxels) is skipped, never written) on `stream`.
+ * Enqueues only; never synchronises.  label / weight may be NULL (inference feed). */
+int ursn_voxels_to_dense(const ursn_voxel_batch* b, float* data, float* label, float* weight, void* stream);
+
+/* Voxel set of a dense label volume (what larcv.as_tensor3d keeps, lib/ssnet_trainval.py:299-302): for each event, the voxels
+ * with labels != 0 in increasing index order.  offsets_out [n+1] (device); index_out / class_out hold at most `cap` entries --
+ * entries whose position is >= cap are not written, offsets_out still holds the true counts so the caller can see the overflow.
+ * Three launches (per-block counts, one-workgroup exclusive scan, write); scratch >= ursn_labels_to_voxels_scratch_bytes(n, voxels).
+ * Enqueues only. */
+int ursn_labels_to_voxels(const float* labels, int32_t n, int64_t voxels, int32_t* index_out, uint8_t* class_out,
+                          int64_t cap, int64_t* offsets_out, void* scratch, size_t scratch_bytes, void* stream);
+size_t ursn_labels_to_voxels_scratch_bytes(int32_t n, int64_t voxels);
 
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);

@@ -55,6 +55,11 @@ class ursn_bn_bf16_desc(C.Structure):
                 ("dres_accumulate", C.c_int32)]
 
 
+class ursn_voxel_batch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("voxels", C.c_int64), ("offsets", C.c_void_p), ("index", C.c_void_p),
+                ("value", C.c_void_p), ("label", C.c_void_p), ("weight", C.c_void_p), ("bg_weight", C.c_void_p)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -106,10 +111,13 @@ _SIGS = {
     "ursn_adam": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                             C.c_int64, _P]),
     "ursn_mfma_probe": (C.c_int, [C.c_int32, _P, _P]),
+    "ursn_voxels_to_dense": (C.c_int, [C.POINTER(ursn_voxel_batch), _P, _P, _P, _P]),
+    "ursn_labels_to_voxels": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "ursn_labels_to_voxels_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
 }
 EXPORTS = tuple(_SIGS.keys())
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _lib = None
 
 

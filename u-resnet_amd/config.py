@@ -47,6 +47,10 @@ class ssnet_config(object):
     # not in the reference (fp32 TensorFlow): 'fp32' | 'bf16' -- bf16 = mixed precision of BASELINE.json configs[4]
     # (activations / gradient tensors bf16 in HBM, fp32 parameters, statistics, accumulators and Adam)
     PRECISION = 'fp32'
+    # not in the reference (larcv fills dense arrays): True = events travel as voxel lists (synthetic_threadio.fetch_voxels ->
+    # the *_voxels methods of ssnet_base) and the ana output holds one (index, class) voxel set per event, the content of the
+    # sparse3d product of lib/ssnet_trainval.py:299-302, instead of the dense label volume
+    SPARSE_IO = False
 
     def __init__(self):
         pass

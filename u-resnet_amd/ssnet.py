@@ -42,6 +42,96 @@ class _Adam(object):
         self._beta1, self._beta2, self._epsilon = 0.9, 0.999, 1e-8
 
 
+class VoxelBatch(object):
+    """A minibatch as larcv-style voxel lists (not in the reference's Python surface, which only sees the dense arrays larcv
+    fills; its ana OUTPUT is this form: lib/ssnet_trainval.py:299-302).  Event i owns list entries
+    ``[offsets[i], offsets[i+1])``; ``index`` is the row-major voxel index inside the event, strictly increasing per event;
+    every voxel not listed is ``(data, label, weight) = (0, 0, bg_weight[i])``.  ``label`` / ``weight`` (with ``bg_weight``) may
+    be None.  Mirrors ``ursn_voxel_batch`` (include/uresnet_hip.h)."""
+
+    __slots__ = ('offsets', 'index', 'value', 'label', 'weight', 'bg_weight', 'voxels')
+
+    def __init__(self, offsets, index, value, label=None, weight=None, bg_weight=None, voxels=0):
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.index = np.ascontiguousarray(index, dtype=np.int32)
+        self.value = np.ascontiguousarray(value, dtype=np.float32)
+        self.label = None if label is None else np.ascontiguousarray(label, dtype=np.float32)
+        self.weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float32)
+        self.bg_weight = None if bg_weight is None else np.ascontiguousarray(bg_weight, dtype=np.float32)
+        self.voxels = int(voxels)
+
+    @property
+    def n(self):
+        return int(self.offsets.shape[0]) - 1
+
+    def validate(self):
+        """O(M) host check of everything the device passes take on trust; raises ValueError naming the first offence."""
+        off, idx, V = self.offsets, self.index, self.voxels
+        if not 1 <= V < 2 ** 31:
+            raise ValueError('VoxelBatch: voxels = %d outside [1, 2^31)' % V)
+        if off.ndim != 1 or off.shape[0] < 2:
+            raise ValueError('VoxelBatch: offsets must be a 1-D array of n + 1 >= 2 entries')
+        if off[0] != 0:
+            raise ValueError('VoxelBatch: offsets[0] = %d, must be 0' % off[0])
+        bad = np.flatnonzero(np.diff(off) < 0)
+        if bad.size:
+            raise ValueError('VoxelBatch: offsets decrease at event %d (%d -> %d)' % (bad[0], off[bad[0]], off[bad[0] + 1]))
+        M = int(off[-1])
+        for name in ('index', 'value', 'label', 'weight'):
+            a = getattr(self, name)
+            if a is not None and (a.ndim != 1 or a.shape[0] != M):
+                raise ValueError('VoxelBatch: %s has shape %s, offsets[-1] says %d entries' % (name, a.shape, M))
+        if (self.weight is None) != (self.bg_weight is None):
+            raise ValueError('VoxelBatch: weight and bg_weight must be given together')
+        if self.bg_weight is not None and self.bg_weight.shape != (self.n,):
+            raise ValueError('VoxelBatch: bg_weight has shape %s for %d events' % (self.bg_weight.shape, self.n))
+        bad = np.flatnonzero((idx < 0) | (idx >= V))
+        if bad.size:
+            j = int(bad[0])
+            raise ValueError('VoxelBatch: index[%d] = %d outside [0, %d) (event %d)'
+                             % (j, idx[j], V, int(np.searchsorted(off, j, side='right')) - 1))
+        if M > 1:
+            step = np.diff(idx) <= 0
+            seams = off[1:-1] - 1            # entry pairs that straddle two events carry no order
+            step[seams[(seams >= 0) & (seams < M - 1)]] = False
+            bad = np.flatnonzero(step)
+            if bad.size:
+                j = int(bad[0])
+                raise ValueError('VoxelBatch: indices must be strictly increasing inside an event: index[%d] = %d is followed '
+                                 'by %d (event %d)' % (j, idx[j], idx[j + 1], int(np.searchsorted(off, j, side='right')) - 1))
+        return self
+
+    def normalize_weights(self):
+        """The per-event normalisation of lib/ssnet_trainval.py:173 (weight /= sum over the event) on the list: ``weight`` and
+        ``bg_weight`` divided, in place, by sum(listed w) + (voxels - m_i) * bg_weight[i] formed in float64."""
+        for i in range(self.n):
+            a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+            total = float(np.sum(self.weight[a:b], dtype=np.float64)) + float(self.voxels - (b - a)) * float(self.bg_weight[i])
+            self.weight[a:b] = (self.weight[a:b].astype(np.float64) / total).astype(np.float32)
+            self.bg_weight[i] = np.float32(float(self.bg_weight[i]) / total)
+        return self
+
+    @staticmethod
+    def concat(batches):
+        """Events of several batches (same ``voxels``, same optional roles) as one batch."""
+        batches = list(batches)
+        V = batches[0].voxels
+        if any(b.voxels != V for b in batches):
+            raise ValueError('VoxelBatch.concat: events of different sizes')
+        counts = np.concatenate([np.diff(b.offsets) for b in batches])
+        off = np.zeros(counts.shape[0] + 1, np.int64)
+        np.cumsum(counts, out=off[1:])
+
+        def cat(name):
+            parts = [getattr(b, name) for b in batches]
+            if any(p is None for p in parts):
+                if not all(p is None for p in parts):
+                    raise ValueError('VoxelBatch.concat: %s present in some batches only' % name)
+                return None
+            return np.concatenate(parts)
+        return VoxelBatch(off, cat('index'), cat('value'), cat('label'), cat('weight'), cat('bg_weight'), V)
+
+
 class ssnet_base(object):
 
     def __init__(self, dims, num_class):
@@ -345,6 +435,165 @@ class ssnet_base(object):
                             ev = torch.cuda.Event()
                             ev.record(torch.cuda.current_stream(self._device))
                         slot.consumed[i] = ev
+
+    # ------------------------------------------------------------------------------------------
+    # voxel-list feed (not in the reference: larcv fills dense arrays; see VoxelBatch)
+    # ------------------------------------------------------------------------------------------
+    def _require_single_channel(self, what):
+        if int(self._dims[-1]) != 1:
+            raise ValueError('%s: voxel lists carry one value per voxel, so dims[-1] must be 1 (dims = %s)'
+                             % (what, [int(d) for d in self._dims]))
+
+    def _feed_voxels(self, vb, with_label=True, with_weight=None):
+        """VoxelBatch -> the dense device tensors of ``feed_dict``, without the dense arrays ever crossing PCIe.
+
+        Every array of the batch is packed into ONE page-locked staging buffer and travels in ONE copy on the copy stream,
+        under the discipline of ``_feed``: two device buffers used alternately, a buffer overwritten only after the launch
+        that last read it (``consumed``), the call returning once the copy is done (``copied``) and never waiting for compute.
+        ``ursn_voxels_to_dense`` then expands the list on the compute stream into per-role device tensors (two sets,
+        alternating, registered as feed slots so ``last_feed`` / ``_mark_consumed`` treat them like fed tensors)."""
+        import torch
+        self._require_single_channel('_feed_voxels')
+        vb.validate()
+        if vb.voxels != self._label_size:
+            raise ValueError('VoxelBatch of %d voxels per event fed to a network of %d' % (vb.voxels, self._label_size))
+        if with_weight is None:
+            with_weight = self._use_weight
+        if with_weight and vb.weight is None:
+            sys.stderr.write('Network configured to use loss pixel-weighting. Cannot run w/ weight=None...\n')
+            raise TypeError
+        if with_label and vb.label is None:
+            raise ValueError('_feed_voxels: the batch has no label list')
+        n, V = vb.n, vb.voxels
+        parts = [('offsets', vb.offsets), ('index', vb.index), ('value', vb.value)]
+        if with_label:
+            parts.append(('label', vb.label))
+        if with_weight:
+            parts += [('weight', vb.weight), ('bg_weight', vb.bg_weight)]
+        at, nbytes = {}, 0
+        for name, a in parts:                      # every section starts on a 16-byte boundary
+            at[name] = nbytes
+            nbytes += (a.nbytes + 15) & ~15
+        nbytes = max(nbytes, 16)
+        cs = self._copy_stream()
+        cur = torch.cuda.current_stream(self._device)
+        slot = self._feed_slots.setdefault('voxel_list', ssnet_base._FeedSlot())
+        i = slot.turn
+        slot.turn ^= 1
+        if slot.dev[i] is None or slot.dev[i].numel() < nbytes:
+            slot.dev[i] = torch.empty(nbytes + nbytes // 2, dtype=torch.uint8, device=self._device)
+            slot.consumed[i] = None
+            cs.wait_stream(cur)                    # as in _feed: the block may come back with kernels still pending on it
+            slot.dev[i].record_stream(cs)
+        if slot.pinned is None or slot.pinned.numel() < nbytes:
+            slot.pinned = torch.empty(nbytes + nbytes // 2, dtype=torch.uint8, pin_memory=True)
+        if slot.copied is not None:
+            slot.copied.synchronize()              # the previous copy out of the staging buffer
+        stage = slot.pinned.numpy()
+        for name, a in parts:
+            stage[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
+        dst = slot.dev[i][:nbytes]
+        with torch.cuda.stream(cs):
+            if slot.consumed[i] is not None:
+                cs.wait_event(slot.consumed[i])
+            dst.copy_(slot.pinned[:nbytes], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cs)
+        slot.copied = ev
+        cur.wait_event(ev)
+        ev.synchronize()                           # copy only; kernels of earlier minibatches keep running
+        self.feed_stats['h2d_bytes'] += nbytes
+        self.feed_stats['h2d_calls'] += 1
+        self.feed_stats['staged_bytes'] += nbytes
+
+        fd, roles = {}, ['data'] + (['label'] if with_label else []) + (['weight'] if with_weight else [])
+        for role in roles:
+            ds = self._feed_slots.setdefault('voxel_' + role, ssnet_base._FeedSlot())
+            k = ds.turn
+            ds.turn ^= 1
+            if ds.dev[k] is None or ds.dev[k].shape[0] < n:
+                ds.dev[k] = torch.empty((n, V), dtype=torch.float32, device=self._device)
+                ds.consumed[k] = None
+            fd['input_' + role] = ds.dev[k][:n]
+        base = dst.data_ptr()
+        b = _lib.ursn_voxel_batch()
+        b.n, b.voxels = n, V
+        b.offsets, b.index, b.value = base + at['offsets'], base + at['index'], base + at['value']
+        b.label = base + at['label'] if with_label else None
+        b.weight = base + at['weight'] if with_weight else None
+        b.bg_weight = base + at['bg_weight'] if with_weight else None
+        _lib.check(_lib.load().ursn_voxels_to_dense(ctypes.byref(b), self._ptr(fd['input_data']), self._ptr(fd.get('input_label')),
+                                                    self._ptr(fd.get('input_weight')), self._stream(None)))
+        done = torch.cuda.Event()
+        done.record(cur)
+        slot.consumed[i] = done                    # the list buffer is free once the expansion has read it
+        return fd
+
+    def accum_gradients_voxels(self, sess, voxels, fetch=True):
+        """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure."""
+        if not self._trainable:
+            raise RuntimeError('accum_gradients_voxels: constructed with trainable=False')
+        self._require_single_channel('accum_gradients_voxels')
+        fd = self._feed_voxels(voxels)
+        n = int(fd['input_data'].shape[0])
+        self._ensure_handle(n)
+        out = (ctypes.c_float * 3)()
+        w = fd.get('input_weight') if self._use_weight else None
+        _lib.check(_lib.load().ursn_accum_step(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
+                                               self._ptr(w), n, out if fetch else None, self._stream(sess)))
+        self._last_feed = fd
+        self._mark_consumed(fd)
+        doc = ['', 'loss', 'acc. all', 'acc. nonzero']
+        if not fetch:
+            return None, doc
+        return [None, float(out[0]), float(out[1]), float(out[2])], doc
+
+    def run_test_voxels(self, sess, voxels):
+        """``run_test`` fed a VoxelBatch."""
+        self._require_single_channel('run_test_voxels')
+        fd = self._feed_voxels(voxels)
+        n = int(fd['input_data'].shape[0])
+        self._ensure_handle(n)
+        out = (ctypes.c_float * 3)()
+        w = fd.get('input_weight') if self._use_weight else None
+        _lib.check(_lib.load().ursn_eval(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
+                                         self._ptr(w), n, out, self._stream(sess)))
+        self._mark_consumed(fd)
+        return [float(out[0]), float(out[1]), float(out[2])], ['loss', 'acc. all', 'acc. nonzero']
+
+    def inference_voxels(self, sess, voxels, with_labels=True):
+        """``inference_labels`` from a VoxelBatch to voxel sets: the label volume (lib/ssnet_trainval.py:285-287) stays on the
+        device and ``ursn_labels_to_voxels`` keeps its non-zeros, what the reference stores through larcv.as_tensor3d
+        (lib/ssnet_trainval.py:299-302).  Returns [list of (index int32[], class uint8[]) per event (, acc_all, acc_nonzero
+        with ``with_labels``)]; only offsets, index, class and the two accuracies come back to the host."""
+        import torch
+        self._require_single_channel('inference_voxels')
+        fd = self._feed_voxels(voxels, with_label=with_labels, with_weight=False)
+        n, V = int(fd['input_data'].shape[0]), self._label_size
+        self._ensure_handle(n)
+        lib = _lib.load()
+        labels = torch.empty((n, V), dtype=torch.float32, device=self._device)
+        acc = (ctypes.c_float * 2)()
+        _lib.check(lib.ursn_infer_labels(self._handle, self._ptr(fd['input_data']), self._ptr(fd.get('input_label')), n,
+                                         self._ptr(labels), None, acc, self._stream(sess)))
+        self._last_feed = fd
+        self._mark_consumed(fd)
+        # the label rule ends in "* (data > 1.0)" and every unlisted voxel holds 0: the host knows the exact upper bound
+        cap = int(np.count_nonzero(voxels.value > 1.0))
+        index = torch.empty(max(cap, 1), dtype=torch.int32, device=self._device)
+        cls = torch.empty(max(cap, 1), dtype=torch.uint8, device=self._device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self._device)
+        sbytes = int(lib.ursn_labels_to_voxels_scratch_bytes(n, V))
+        scratch = torch.empty(sbytes, dtype=torch.uint8, device=self._device)
+        _lib.check(lib.ursn_labels_to_voxels(self._ptr(labels), n, V, self._ptr(index), self._ptr(cls), cap, self._ptr(offsets),
+                                             self._ptr(scratch), sbytes, self._stream(sess)))
+        off = offsets.cpu().numpy()
+        assert 0 <= int(off[-1]) <= cap, 'labels_to_voxels: %d non-zero labels, at most %d expected' % (int(off[-1]), cap)
+        idx, cl = index[:int(off[-1])].cpu().numpy(), cls[:int(off[-1])].cpu().numpy()
+        res = [[(idx[off[i]:off[i + 1]].copy(), cl[off[i]:off[i + 1]].copy()) for i in range(n)]]
+        if with_labels:
+            res += [float(acc[0]), float(acc[1])]
+        return res
 
     # ------------------------------------------------------------------------------------------
     # fetch-sets (lib/ssnet.py:91-153)

@@ -125,6 +125,8 @@ class ssnet_trainval(object):
         d = _dist()
         if d is not None and d.get_world_size() > 1:
             io.shard(d.get_rank(), d.get_world_size())   # rank r reads entries r, r+W, r+2W, ...
+        if self._cfg.SPARSE_IO:
+            io.produce_voxels()
         io.start_manager(batch)
         return io
 
@@ -205,6 +207,14 @@ class ssnet_trainval(object):
             weight /= np.sum(weight, axis=1).reshape([weight.shape[0], 1])
         return data, label, weight
 
+    def _pull_voxels(self, io):
+        """SPARSE_IO: the batch as a voxel list; the normalisation of lib/ssnet_trainval.py:173 is done on the list (the sum
+        over an event = listed weights + unlisted voxels x background weight, in float64)."""
+        vb = io.fetch_voxels()
+        if self._cfg.USE_WEIGHTS:
+            vb.normalize_weights()
+        return vb
+
     def _run_minibatches(self, want_metrics):
         """zero -> NUM_MINIBATCHES x accumulate -> apply.  Returns the per-minibatch metrics [M, 3] when asked for
         (each read is a stream synchronisation), else None; in both cases ``self._last_minibatch`` holds the
@@ -213,9 +223,12 @@ class ssnet_trainval(object):
         rows = []
         net.zero_gradients(self._sess)
         for _ in range(c.NUM_MINIBATCHES):
-            data, label, weight = self._pull(self._input_main, c.KEYWORD_DATA, c.KEYWORD_LABEL, c.KEYWORD_WEIGHT)
-            res, doc = net.accum_gradients(sess=self._sess, input_data=data, input_label=label, input_weight=weight,
-                                           fetch=want_metrics)
+            if c.SPARSE_IO:
+                res, doc = net.accum_gradients_voxels(self._sess, self._pull_voxels(self._input_main), fetch=want_metrics)
+            else:
+                data, label, weight = self._pull(self._input_main, c.KEYWORD_DATA, c.KEYWORD_LABEL, c.KEYWORD_WEIGHT)
+                res, doc = net.accum_gradients(sess=self._sess, input_data=data, input_label=label, input_weight=weight,
+                                               fetch=want_metrics)
             # the copy has completed, the kernels are queued: the IO may refill this buffer while they run
             self._descr_metrics = doc[1:]
             if want_metrics:
@@ -243,12 +256,17 @@ class ssnet_trainval(object):
         if (plan.report or plan.summary) and self._input_test:
             c = self._cfg
             self._input_test.next()
-            test = self._pull(self._input_test, c.KEYWORD_TEST_DATA, c.KEYWORD_TEST_LABEL, c.KEYWORD_TEST_WEIGHT)
+            if c.SPARSE_IO:
+                test = self._pull_voxels(self._input_test)
+            else:
+                test = self._pull(self._input_test, c.KEYWORD_TEST_DATA, c.KEYWORD_TEST_LABEL, c.KEYWORD_TEST_WEIGHT)
 
         if plan.report:
             # report_step is the same on every rank, so the collective inside is safe
             train_mean = self._mean_over_ranks(per_minibatch.mean(axis=0))
-            tested = self._net.run_test(self._sess, *test) if test is not None else None
+            tested = None
+            if test is not None:
+                tested = self._net.run_test_voxels(self._sess, test) if self._cfg.SPARSE_IO else self._net.run_test(self._sess, *test)
             if _is_rank0():
                 stamp = datetime.datetime.fromtimestamp(time.time()).strftime('%Y-%m-%d %H:%M:%S')
                 sys.stdout.write('@ iteration {:d} LR {:g} Mem {:g} @ {:s}\n'.format(
@@ -264,7 +282,12 @@ class ssnet_trainval(object):
             if self._writer_train:
                 self._writer_train.add_summary(summ, plan.iteration)
             if self._writer_test and test is not None:
-                self._writer_test.add_summary(self._net.make_summary(self._sess, *test), plan.iteration)
+                if self._cfg.SPARSE_IO:
+                    t3, _ = self._net.run_test_voxels(self._sess, test)
+                    tsum = {'loss': t3[0], 'accuracy_all': t3[1], 'accuracy_nonzero': t3[2]}
+                else:
+                    tsum = self._net.make_summary(self._sess, *test)
+                self._writer_test.add_summary(tsum, plan.iteration)
         if plan.checkpoint and self._cfg.SAVE_FILE and _is_rank0():
             print('saved @', self.save_checkpoint())
 
@@ -285,8 +308,44 @@ class ssnet_trainval(object):
     def ana(self, input_data, input_label=None):
         return self._net.inference(sess=self._sess, input_data=input_data, input_label=input_label)
 
+    def _ana_step_voxels(self, batch_mode):
+        """SPARSE_IO ana_step: the event arrives as a voxel list and the record is the voxel set of the label volume -- per
+        event ``np.save(index)`` then ``np.save(class)``, the content of the reference's sparse3d product
+        (lib/ssnet_trainval.py:299-302).  In batch mode nothing dense crosses PCIe in either direction."""
+        from .synthetic_io import voxels_to_dense
+        io = self._input_main
+        vb = io.fetch_voxels()
+        entries = io.fetch_entries()
+        softmax = data = label = None
+        if batch_mode and self._output:
+            sets, acc_all, acc_nonzero = self._net.inference_voxels(self._sess, vb, with_labels=True)
+        else:
+            data, label, _ = voxels_to_dense(vb)
+            if self._output:
+                labels, acc_all, acc_nonzero, softmax = self._net.inference_labels(self._sess, data, label, with_softmax=True)
+                flat = labels.reshape(labels.shape[0], -1)
+                sets = [(np.flatnonzero(v).astype(np.int32), v[np.flatnonzero(v)].astype(np.uint8)) for v in flat]
+            else:
+                softmax, acc_all, acc_nonzero = self.ana(input_data=data, input_label=label)
+        if self._output:
+            for i, (index, cls) in enumerate(sets):
+                print('Entry', entries[i], 'Acc', acc_nonzero)
+                np.save(self._output, index)
+                np.save(self._output, cls)
+            self._output.flush()
+        result = None
+        if not batch_mode:
+            img_shape = list(softmax.shape)
+            img_shape[-1] = -1
+            result = {'entries': np.array(entries), 'input': data.reshape(img_shape), 'label': label.reshape(img_shape),
+                      'softmax': softmax, 'acc_all': acc_all, 'acc_nonzero': acc_nonzero}
+        self._advance_main()
+        return result
+
     def ana_step(self, batch_mode=False):
         self._iteration += 1
+        if self._cfg.SPARSE_IO:
+            return self._ana_step_voxels(batch_mode)
         c, io = self._cfg, self._input_main
         batch_data = io.fetch_data(c.KEYWORD_DATA).data()
         batch_label = io.fetch_data(c.KEYWORD_LABEL).data()

@@ -77,6 +77,45 @@ def lartpc_sparse(dims, num_class, entry):
     return data.reshape(-1), label.reshape(-1), weight.reshape(-1)
 
 
+def dense_to_voxels(data, label, weight=None):
+    """One event's dense arrays -> a one-event VoxelBatch (ssnet.py): ``bg_weight`` is the weight of the first voxel with
+    data == 0 and label == 0 (0.0 if there is none), and every voxel whose (data, label, weight) differs from
+    (0, 0, bg_weight) is listed, in increasing index order."""
+    from .ssnet import VoxelBatch
+    data = np.asarray(data, np.float32).reshape(-1)
+    label = np.asarray(label, np.float32).reshape(-1)
+    if data.size != label.size:
+        raise ValueError('dense_to_voxels: %d data values for %d voxels; voxel lists need one channel' % (data.size, label.size))
+    listed = (data != 0) | (label != 0)
+    bg = None
+    if weight is not None:
+        weight = np.asarray(weight, np.float32).reshape(-1)
+        empty = np.flatnonzero(~listed)
+        bg = np.float32(weight[empty[0]]) if empty.size else np.float32(0.0)
+        listed |= weight != bg
+    idx = np.flatnonzero(listed)
+    return VoxelBatch([0, idx.size], idx, data[idx], label[idx], None if weight is None else weight[idx],
+                      None if weight is None else [bg], data.size)
+
+
+def voxels_to_dense(vb):
+    """numpy inverse of ``dense_to_voxels`` for a whole batch (what ursn_voxels_to_dense computes on the device):
+    (data, label, weight) as [n, voxels] float32; label / weight are None when the batch does not carry them."""
+    n, V = vb.n, vb.voxels
+    data = np.zeros((n, V), np.float32)
+    label = None if vb.label is None else np.zeros((n, V), np.float32)
+    weight = None if vb.weight is None else np.repeat(vb.bg_weight.reshape(n, 1), V, axis=1)
+    for i in range(n):
+        a, b = int(vb.offsets[i]), int(vb.offsets[i + 1])
+        idx = vb.index[a:b]
+        data[i, idx] = vb.value[a:b]
+        if label is not None:
+            label[i, idx] = vb.label[a:b]
+        if weight is not None:
+            weight[i, idx] = vb.weight[a:b]
+    return data, label, weight
+
+
 GENERATORS = {'dense_uniform': dense_uniform, 'lartpc_sparse': lartpc_sparse}
 
 
@@ -115,6 +154,7 @@ class synthetic_threadio(object):
         self._ready = None
         self._cursor = 0
         self._batch = 0
+        self._voxels = False
 
     def configure(self, cfg):
         """cfg: dict with 'filler_cfg' = path of a synthetic input cfg or an inline dict
@@ -133,6 +173,10 @@ class synthetic_threadio(object):
     def shard(self, rank, world_size):
         """Data parallelism: this reader serves entries rank, rank + W, rank + 2W, ... (call before start_manager)."""
         self._offset, self._stride = int(rank), int(world_size)
+
+    def produce_voxels(self, on=True):
+        """Also build every batch as a VoxelBatch on the producer thread (``fetch_voxels``); call before start_manager."""
+        self._voxels = bool(on)
 
     def start_manager(self, batch_size):
         self._batch = int(batch_size)
@@ -165,7 +209,11 @@ class synthetic_threadio(object):
             d, l, w = self._gen(self._dims, self._num_class, e)
             data[i], label[i], weight[i] = d, l, w
             entries.append(e)
-        return dict(data=data, label=label, weight=weight, entries=entries)
+        out = dict(data=data, label=label, weight=weight, entries=entries)
+        if self._voxels:
+            from .ssnet import VoxelBatch
+            out['voxels'] = VoxelBatch.concat([dense_to_voxels(data[i], label[i], weight[i]) for i in range(n)])
+        return out
 
     def _spawn(self):
         first = self._cursor
@@ -199,6 +247,15 @@ class synthetic_threadio(object):
         n = self._batch
         dim = [n] + (self._dims if role == 'data' else self._dims[:-1])
         return _batch_data(self._ready[role], dim)
+
+    def fetch_voxels(self):
+        """The ready batch as a VoxelBatch with label, weight and bg_weight (not in larcv's protocol): built on the producer
+        thread and, like the dense buffers, valid until the ``next()`` after its use."""
+        if not self._voxels:
+            raise RuntimeError('fetch_voxels: call produce_voxels() before start_manager()')
+        if self._ready is None:
+            self.next()
+        return self._ready['voxels']
 
     def fetch_entries(self):
         return list(self._ready['entries'])
