@@ -354,3 +354,34 @@ def test_bench_options_that_report_from_the_full_legs_need_full():
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + opt, cwd=ROOT, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=120)
         assert p.returncode == 2 and "--full" in p.stderr and opt[0] in p.stderr, (opt, p.stderr[-500:])
+
+
+def test_switch_table_matches_sources():
+    """The A/B switches are read through the ursn_env_* helpers of ursn_common.h and nowhere else, and DESIGN.md's "A/B switches"
+    table names exactly the switches that something reads.  Source text only: no library is loaded."""
+    import glob
+    csrc = os.path.join(ROOT, "u-resnet_amd", "csrc")
+    texts = {}
+    for p in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        with open(p) as f:
+            texts[os.path.basename(p)] = f.read()
+    stray = sorted(n for n, t in texts.items() if n != "ursn_common.h" and "getenv(" in t)
+    assert not stray, "getenv( outside ursn_common.h: %s" % stray
+    read = set()
+    for t in texts.values():
+        read.update(re.findall(r'ursn_env_(?:str|on|set|int|i64)\(\s*"(URSN_[A-Z0-9_]+)"', t))
+    assert len(read) > 50, sorted(read)
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        design = f.read()
+    section = design.split("### A/B switches", 1)[1].split("\n## ", 1)[0]
+    rows = [l for l in section.splitlines() if l.startswith("|")]
+    table = set(re.findall(r"URSN_[A-Z0-9_]+", "\n".join(rows)))
+    assert not (read - table), "read in csrc/ but not in DESIGN.md's table: %s" % sorted(read - table)
+    py = ""
+    for p in [os.path.join(ROOT, "bench.py")] + sorted(glob.glob(os.path.join(ROOT, "u-resnet_amd", "*.py"))) + \
+            sorted(glob.glob(os.path.join(ROOT, "tools", "**", "*"), recursive=True)):
+        if os.path.isfile(p):
+            with open(p, errors="replace") as f:
+                py += f.read()
+    unread = sorted(n for n in table - read if not re.search(r"\b%s\b" % n, py))
+    assert not unread, "in DESIGN.md's table but read nowhere: %s" % unread

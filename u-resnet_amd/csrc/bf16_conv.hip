@@ -346,15 +346,15 @@ static bool bconv_plan(const GatherGeom& g, BPlan& p) {
   static int nbuf_env = 2;
   if (!env_done) {   // A/B: URSN_BCONV_BOX="z,y,x" replaces the first candidate, URSN_BCONV_LDS_KB caps the first-pass LDS budget
     env_done = true;
-    const char* e = getenv("URSN_BCONV_BOX");
+    const char* e = ursn_env_str("URSN_BCONV_BOX");
     if (e) sscanf(e, "%d,%d,%d", &cand[0][0], &cand[0][1], &cand[0][2]);
-    const char* l = getenv("URSN_BCONV_LDS_KB");
+    const char* l = ursn_env_str("URSN_BCONV_LDS_KB");
     if (l) lds_cap = (size_t)atoi(l) * 1024;
-    const char* nb = getenv("URSN_BCONV_NBUF");
+    const char* nb = ursn_env_str("URSN_BCONV_NBUF");
     if (nb) nbuf_env = atoi(nb) == 1 ? 1 : 2;
   }
   const int ncand = (int)(sizeof(cand) / sizeof(cand[0]));
-  static const int64_t minwg = getenv("URSN_BCONV_MINWG") ? atoi(getenv("URSN_BCONV_MINWG")) : 256;   // one workgroup per CU is enough to take the larger box (512: 77.7, 256: 78.6 img/s at cfg5)
+  static const int64_t minwg = ursn_env_int("URSN_BCONV_MINWG", 256);   // one workgroup per CU is enough to take the larger box (512: 77.7, 256: 78.6 img/s at cfg5)
   // Contraction channels per staged chunk: 32 where some box fits the LDS, else 16, else 8; per box candidate (largest first: the
   // packed weights of a chunk are re-read per box) two stage buffers (the next chunk's halo box and weights land while this one
   // computes), else one.  Measured and rejected (round 3): preferring 16-channel chunks with two buffers over 32-channel chunks
@@ -798,7 +798,7 @@ static bool bwgrad_plan(const GatherGeom& g, BWPlan& p) {
   p.ncob = (g.Nn + 16 * p.cot - 1) / (16 * p.cot);
   static const int cand[][3] = {{2, 8, 32}, {1, 8, 32}, {1, 4, 32}, {1, 2, 32}, {1, 1, 32}};
   const int ncand = (int)(sizeof(cand) / sizeof(cand[0]));
-  static size_t first_limit = getenv("URSN_BWGRAD_LDS_KB") ? (size_t)atoi(getenv("URSN_BWGRAD_LDS_KB")) * 1024 : 156 * 1024;   // as bconv: large boxes beat two workgroups per CU (52 KB: 73.2, 156 KB: 74.8 img/s at cfg5)
+  static const size_t first_limit = (size_t)ursn_env_int("URSN_BWGRAD_LDS_KB", 156) * 1024;   // as bconv: large boxes beat two workgroups per CU (52 KB: 73.2, 156 KB: 74.8 img/s at cfg5)
   const size_t limits[2] = {first_limit, 156 * 1024};
   for (size_t limit : limits)
     for (int ci = 0; ci < ncand; ++ci) {
@@ -816,7 +816,7 @@ static bool bwgrad_plan(const GatherGeom& g, BWPlan& p) {
       const int64_t boxes = (int64_t)g.N * p.nb[0] * p.nb[1] * p.nb[2];
       if (p.lds > limit || boxes <= 0 || boxes >= (1ll << 30)) continue;
       // smaller boxes when the problem is small, so that more than a handful of workgroups take part
-      static const int64_t wminwg = getenv("URSN_BWGRAD_MINWG") ? atoi(getenv("URSN_BWGRAD_MINWG")) : 256;   // A/B
+      static const int64_t wminwg = ursn_env_int("URSN_BWGRAD_MINWG", 256);   // A/B
       if (boxes * p.nchunks * p.ncob < wminwg && ci + 1 < ncand) continue;
       p.nboxes = (int)boxes;
       int64_t occ = (int64_t)(160 * 1024) / (p.lds + 2048);

@@ -349,10 +349,13 @@ bool c0_geom_ok(const GatherGeom& g) {
 
 }  // namespace
 
+static bool b0conv_on() {   // URSN_B0CONV=0: conv0 and its weight gradient on the general 8 -> 8 kernels
+  static const bool v = ursn_env_on("URSN_B0CONV");
+  return v;
+}
 // g: the layer's forward geometry seen as an 8 -> 8 layer (K = 8 with seven absent channels), as the callers build it
 bool b0conv_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_B0CONV") && getenv("URSN_B0CONV")[0] == '0';
-  return !off && g.K == 8 && (g.out_cs & 3) == 0 && c0_geom_ok(g);
+  return b0conv_on() && g.K == 8 && (g.out_cs & 3) == 0 && c0_geom_ok(g);
 }
 int b0conv_grid_blocks(const GatherGeom& g) { return c0_plan(g).grid; }
 size_t b0conv_pack_elems() { return 3 * 64 * 4 + 8; }
@@ -382,8 +385,7 @@ int launch_b0conv(const GatherGeom& g, const float* x, const float* w, int Nw, b
 
 // g: the layer's weight-gradient geometry (S = the input, C = dz)
 bool b0wgrad_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_B0CONV") && getenv("URSN_B0CONV")[0] == '0';
-  return !off && g.K == 8 && (g.out_cs & 7) == 0 && c0_geom_ok(g);
+  return b0conv_on() && g.K == 8 && (g.out_cs & 7) == 0 && c0_geom_ok(g);
 }
 size_t b0wgrad_scratch_bytes(const GatherGeom& g) { return (size_t)c0_plan(g).grid * 256 * sizeof(float) + 256; }
 

@@ -81,11 +81,11 @@ struct B3Args {
 // per CU (URSN_B3CONV_PF2, round 2: slower).  The wait that ends an iteration counts this wave's own younger VM operations
 // exactly (its stores of the plane just completed, the DMAs of the planes behind the next one), so it never drains the ring.
 template <int CI, int CO, bool STATS, bool PW = false, int BS = 0, bool AFF = false, bool DMA = false>
-// (BS == 1 on the DMA path -- opt-in, URSN_B3CONV_BS_DMA -- stays at two waves per SIMD: at three it spills 80 bytes per lane, and
-// compiler-placed scratch traffic between a DMA and its hand-counted s_waitcnt vmcnt(N) would make that count too loose)
-__global__ __launch_bounds__(256, ((BS == 1 && !DMA) || (CI == 8 && CO == 8 && BS == 0)) ? 3 : 2) void b3conv_kernel(B3Args a) {
+// (the BS forms stay on the register path: through the DMA ring they measured 0.91-1.53 ms per launch against 0.73-1.30 at cfg5 --
+// the epilogue's arithmetic, not the latency of its operands, is what that fusion costs)
+__global__ __launch_bounds__(256, (BS == 1 || (CI == 8 && CO == 8 && BS == 0)) ? 3 : 2) void b3conv_kernel(B3Args a) {
   static_assert(!AFF || (!PW && BS == 0), "normalise-on-load: plain forward instantiations");
-  static_assert(!DMA || (!AFF && !PW), "LDS-DMA staging: no transform on the way in (the BS operands belong to the epilogue)");
+  static_assert(!DMA || (!AFF && !PW && BS == 0), "LDS-DMA staging: no transform on the way in, no fused BatchNorm-backward epilogue");
   using G = B3<CI, CO>;
   static_assert(!PW || (CI == 8 && CO == 16 && !STATS), "fused shortcut term: the 8 -> 16 data gradient");
   static_assert(BS == 0 || (CO == 8 && !STATS && !PW), "fused BatchNorm-backward reductions: data gradients producing 8 channels");
@@ -528,9 +528,9 @@ B3Plan b3_plan(const GatherGeom& g) {
   // two halo planes per z segment: long segments, but enough workgroups to fill 256 CUs x 2 a few times over
   int zseg = Z;
   const int64_t tiles = (int64_t)g.N * p.nty * p.ntx;
-  static const int64_t minwg = getenv("URSN_B3_MINWG") ? atoi(getenv("URSN_B3_MINWG")) : 2048;   // A/B
+  static const int64_t minwg = ursn_env_int("URSN_B3_MINWG", 2048);   // A/B
   while (zseg > 16 && tiles * ((Z + zseg - 1) / zseg) < minwg) zseg = (zseg + 1) / 2;
-  static const int force_nz = getenv("URSN_B3_NZSEG") ? atoi(getenv("URSN_B3_NZSEG")) : 0;   // A/B
+  static const int force_nz = ursn_env_int("URSN_B3_NZSEG", 0);   // A/B
   if (force_nz > 0) zseg = (Z + force_nz - 1) / force_nz;
   p.zseg = zseg;
   p.nzseg = (Z + zseg - 1) / zseg;
@@ -541,7 +541,7 @@ B3Plan b3_plan(const GatherGeom& g) {
 }  // namespace
 
 bool b3conv_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_B3CONV") && getenv("URSN_B3CONV")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_B3CONV");
   if (off) return false;
   {   // buffer-path staging (buffer_stage.h): a z plane of either tensor must stay below the out-of-range marker
     const int64_t pv = (int64_t)g.in_d[1] * g.in_d[2], qv = (int64_t)g.out_d[1] * g.out_d[2];
@@ -564,7 +564,7 @@ bool b3conv_ok(const GatherGeom& g) {
 
 bool b3conv_aff_ok(const GatherGeom& g) { return b3conv_ok(g) && g.K == g.Nn; }
 bool b3conv_pw_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_B3CONV_PW") && getenv("URSN_B3CONV_PW")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_B3CONV_PW");
   return !off && b3conv_ok(g) && g.K == 8 && g.Nn == 16;
 }
 size_t b3conv_pack_elems() { return (size_t)B3<16, 16>::WPACK + 8; }
@@ -575,7 +575,7 @@ int b3conv_grid_blocks(const GatherGeom& g) { return b3_plan(g).grid; }
 // operands (z, z2, mask bytes) requested a whole MFMA block ahead: 168 VGPRs + 84 bytes of spills at three waves per SIMD, or
 // 226 VGPRs at two, cost this latency-bound kernel more than the 16 bytes per voxel of the separate pass.  Parity-tested.
 bool b3conv_bs_ok(const GatherGeom& g) {
-  static const bool on = getenv("URSN_BF16_FUSE_BN_BWD_REDUCE") && getenv("URSN_BF16_FUSE_BN_BWD_REDUCE")[0] == '1';
+  static const bool on = ursn_env_set("URSN_BF16_FUSE_BN_BWD_REDUCE");
   return on && b3conv_ok(g) && g.Nn == 8 && g.K == 8;
 }
 
@@ -645,15 +645,7 @@ int launch_b3conv(const GatherGeom& g, const bf16_t* in, const float* w, int Kw,
     a.bs_z_cs = bs->z_cs; a.bs_y_cs = bs->y_cs; a.bs_z2_cs = bs->z2_cs; a.bs_mode = bs->mode;
     URSN_TRY(pack(8, 8, B3<8, 8>::WPACK, B3<8, 8>::MT));
     ursn_note_kernel("b3conv_bf16<8,8>+bnred");
-    // URSN_B3CONV_BS_DMA=1: planes through the LDS-DMA ring.  Measured at cfg5 with the fusion on: 0.91-1.53 ms per launch against
-    // 0.73-1.30 on the register path (and 0.45 + 0.38 for the plain data gradient + the separate reduce pass): the epilogue's
-    // arithmetic, not the latency of its operands, is what the fusion costs -- off
-    static const bool bs_dma = getenv("URSN_B3CONV_BS_DMA") && getenv("URSN_B3CONV_BS_DMA")[0] == '1' &&
-                               !(getenv("URSN_B3CONV_DMA") && getenv("URSN_B3CONV_DMA")[0] == '0');
-    if (bs_dma) {
-      if (bs->z2) hipLaunchKernelGGL((b3conv_kernel<8, 8, false, false, 2, false, true>), dim3(p.grid), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((b3conv_kernel<8, 8, false, false, 1, false, true>), dim3(p.grid), dim3(256), 0, s, a);
-    } else if (bs->z2) hipLaunchKernelGGL((b3conv_kernel<8, 8, false, false, 2>), dim3(p.grid), dim3(256), 0, s, a);
+    if (bs->z2) hipLaunchKernelGGL((b3conv_kernel<8, 8, false, false, 2>), dim3(p.grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((b3conv_kernel<8, 8, false, false, 1>), dim3(p.grid), dim3(256), 0, s, a);
     URSN_HIP(hipGetLastError());
     return 0;
@@ -667,13 +659,13 @@ int launch_b3conv(const GatherGeom& g, const bf16_t* in, const float* w, int Kw,
   }
   // LDS-DMA ring (three planes in flight) for every plain instantiation; URSN_B3CONV_DMA=0: one register-staged plane ahead.
   // The scalar fp32 input of conv0 is converted on the way in and keeps the register path.
-  static const bool dma_off = getenv("URSN_B3CONV_DMA") && getenv("URSN_B3CONV_DMA")[0] == '0';
+  static const bool dma_off = !ursn_env_on("URSN_B3CONV_DMA");
   // measured (256^3 x 4 / 128^3 x 4, tools/bf16_op_bench.py): forward 8 -> 8 0.81 -> 0.70 ms, 16 -> 8 1.12 -> 1.04, 16 -> 16 0.254 ->
   // 0.235; data gradients 16 -> 8 1.00 -> 0.96, 16 -> 16 0.244 -> 0.232, 8 -> 8 0.553 -> 0.572 (no statistics epilogue to hide
   // behind: stays on the register path)
   // ... unless it accumulates: on the register path the old values are read inside the epilogue (0.85 ms); the DMA path requests
   // them a whole iteration ahead
-  static const bool acc_dma = !(getenv("URSN_B3CONV_ACC_DMA") && getenv("URSN_B3CONV_ACC_DMA")[0] == '0');
+  static const bool acc_dma = ursn_env_on("URSN_B3CONV_ACC_DMA");
   const bool pf2 = !dma_off && !in_f32 && (!(g.K == 8 && g.Nn == 8 && !stats_partial) || (acc_dma && (g.accumulate || res)));
 #define B3GO(ci, co, label)                                                                                              \
   if (g.K == ci && g.Nn == co) {                                                                                          \

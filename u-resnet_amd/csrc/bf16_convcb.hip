@@ -359,7 +359,7 @@ CBPlan cb_plan(const GatherGeom& g) {
   p.ncob = (g.Nn + 31) / 32;
   // one workgroup per CU: segments as long as possible (two halo planes each) while every CU still gets a column
   const int64_t cols = (int64_t)g.N * p.nty * p.ntx * p.ncob;
-  static const int64_t minwg = getenv("URSN_BCB_MINWG") ? atoi(getenv("URSN_BCB_MINWG")) : 256;   // A/B
+  static const int64_t minwg = ursn_env_int("URSN_BCB_MINWG", 256);   // A/B
   int zseg = Z;
   while (zseg > 4 && cols * ((Z + zseg - 1) / zseg) < minwg) zseg = (zseg + 1) / 2;
   p.zseg = zseg;
@@ -371,7 +371,7 @@ CBPlan cb_plan(const GatherGeom& g) {
 }  // namespace
 
 bool bcbconv_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_BCB") && getenv("URSN_BCB")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BCB");
   if (off) return false;
   {   // buffer-path staging (buffer_stage.h): a z plane of either tensor must stay below the out-of-range marker
     const int64_t pv = (int64_t)g.in_d[1] * g.in_d[2], qv = (int64_t)g.out_d[1] * g.out_d[2];
@@ -411,7 +411,7 @@ static int cb_launch(const CBPlan& p, const CBArgs& a, hipStream_t s) {
 }
 
 bool bcbconv_pw_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_BCB_PW") && getenv("URSN_BCB_PW")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BCB_PW");
   return !off && bcbconv_ok(g);
 }
 

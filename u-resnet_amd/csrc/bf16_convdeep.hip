@@ -379,9 +379,9 @@ bool bd_plan(const GatherGeom& g, BDPlan& p) {
   static int64_t minwg = 192;
   if (force_form == -2) {   // A/B: URSN_BDCONV_FORM="form,gsplit", URSN_BDCONV_MINWG
     force_form = -1;
-    const char* e = getenv("URSN_BDCONV_FORM");
+    const char* e = ursn_env_str("URSN_BDCONV_FORM");
     if (e) sscanf(e, "%d,%d", &force_form, &force_gs);
-    const char* m = getenv("URSN_BDCONV_MINWG");
+    const char* m = ursn_env_str("URSN_BDCONV_MINWG");
     if (m) minwg = atoi(m);
   }
   bool have = false;
@@ -452,7 +452,7 @@ bool bd_plan(const GatherGeom& g, BDPlan& p) {
 }  // namespace
 
 bool bdconv_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_BDCONV") && getenv("URSN_BDCONV")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BDCONV");
   if (off) return false;
   if (g.ntaps != 27 || g.K < 64 || (g.K & 31) || g.Nn < 64 || (g.Nn & 15) || (g.in_cs & 7) || (g.out_cs & 3)) return false;
   for (int j = 0; j < 3; ++j) {

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void bdeconv_kernel(D3Args a) {
 
 struct D3Plan { int zseg, nzseg, nty, ntx, grid, dmin[3]; };
 bool d3_plan(const GatherGeom* g, int cnt, D3Plan& p) {
-  static const bool off = getenv("URSN_BDECONV") && getenv("URSN_BDECONV")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BDECONV");
   if (off || cnt != 8) return false;
   const GatherGeom& g0 = g[0];
   if (g0.K != 16 || g0.Nn != 8 || (g0.in_cs & 7) || (g0.out_cs & 7)) return false;

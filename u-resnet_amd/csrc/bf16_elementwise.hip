@@ -24,7 +24,7 @@ BMap make_bmap(int64_t V, int C) {
   m.shift = 0;
   while ((1 << m.shift) < cp) ++m.shift;
   const int vpb = 256 >> m.shift;
-  static const int cap = getenv("URSN_BEW_GRID") ? atoi(getenv("URSN_BEW_GRID")) : 1024;   // rows of reduce partials (2048: 79.1, 1024: 79.5 img/s at cfg5)
+  static const int cap = ursn_env_int("URSN_BEW_GRID", 1024);   // rows of reduce partials (2048: 79.1, 1024: 79.5 img/s at cfg5)
   int64_t blocks = cdiv64(V, (int64_t)vpb * 8);
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
@@ -506,14 +506,14 @@ int launch_bbn_act(const BBnActArgs& a, hipStream_t s) {
   URSN_REQUIRE(piece_ok(a.C, {a.zcs, a.ycs, a.z2 ? a.z2cs : 0, a.res ? a.rescs : 0}, {a.z, a.y, a.z2, a.res}),
                "bf16 bn_act: channels / strides must be multiples of 8 and pointers 16-byte aligned (C = %d)", a.C);
   const BMap m = make_bmap(a.V, a.C);
-  static const int acap = getenv("URSN_BEW_AGRID") ? atoi(getenv("URSN_BEW_AGRID")) : (1 << 20);   // A/B
+  static const int acap = ursn_env_int("URSN_BEW_AGRID", 1 << 20);   // A/B
   const int grid = bew_grid(a.V, m.shift, acap);
 #define BACT(c8, h2, hr) hipLaunchKernelGGL((bbn_act_kernel<c8, h2, hr>), dim3(grid), dim3(256), 0, s, a, m.shift)
 #define BACT2(c8) do { if (a.z2 && a.res) BACT(c8, true, true); else if (a.z2) BACT(c8, true, false); \
                        else if (a.res) BACT(c8, false, true); else BACT(c8, false, false); } while (0)
   if (a.cat) {
     URSN_REQUIRE(a.C == 8 && a.z2 && !a.res && a.ycs >= 16, "bf16 bn_act: the concat form needs two 8-channel inputs and a 16-channel output voxel");
-    static const bool pairs = !(getenv("URSN_BBN_CAT_PAIRS") && getenv("URSN_BBN_CAT_PAIRS")[0] == '0');
+    static const bool pairs = ursn_env_on("URSN_BBN_CAT_PAIRS");
     if (pairs) hipLaunchKernelGGL(bbn_cat_kernel, dim3(bew_grid(a.V, 1, acap)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((bbn_act_kernel<true, true, false, true>), dim3(grid), dim3(256), 0, s, a, m.shift);
   } else if (a.C == 8) BACT2(true); else BACT2(false);
@@ -529,7 +529,7 @@ int launch_bbn_bwd(const BBnBwdArgs& a, hipStream_t s) {
                         {a.dy, (a.relu && !a.mask) ? a.y : nullptr, a.z, a.dz, a.z2, a.dz2, a.dres}),
                "bf16 bn_bwd: channels / strides must be multiples of 8 and pointers 16-byte aligned (C = %d)", a.C);
   const BMap m = make_bmap(a.V, a.C);   // m.grid: rows of the partial-sum scratch (bbn_scratch_bytes)
-  static const int acap = getenv("URSN_BEW_AGRID") ? atoi(getenv("URSN_BEW_AGRID")) : (1 << 20);   // A/B
+  static const int acap = ursn_env_int("URSN_BEW_AGRID", 1 << 20);   // A/B
   const int rgrid = bew_grid(a.V, m.shift, m.grid), agrid = bew_grid(a.V, m.shift, acap);
   double* partial = (double*)a.scratch;
   double* finals = partial + (size_t)m.grid * 3 * a.C;

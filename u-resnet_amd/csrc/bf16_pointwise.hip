@@ -127,7 +127,7 @@ int pw_grid(const GatherGeom& g) {
 }  // namespace
 
 bool bpw_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_BPW") && getenv("URSN_BPW")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BPW");
   if (off || g.ntaps != 1 || (g.in_cs & 7) || (g.out_cs & 7)) return false;
   if (!((g.K == 8 || g.K == 16) && (g.Nn == 8 || g.Nn == 16))) return false;
   for (int j = 0; j < 3; ++j)

@@ -15,6 +15,11 @@
 #include "bf16_pack.h"
 #include "buffer_stage.h"
 
+bool ursn_bs2k8_on() {   // URSN_BS2K8=0: off (this kernel and its weight gradient, bf16_s2k8w.hip)
+  static const bool v = ursn_env_on("URSN_BS2K8");
+  return v;
+}
+
 namespace {
 
 constexpr int S2_TX = 16, S2_TY = 8, S2_FX = 2 * S2_TX + 1, S2_FY = 2 * S2_TY + 1;
@@ -175,8 +180,7 @@ __global__ __launch_bounds__(256, 2) void bs2k8_kernel(S2KArgs a) {
 
 struct S2KPlan { int zseg, nzseg, nty, ntx, grid, dmin[3]; };
 bool s2k_plan(const GatherGeom& g, S2KPlan& p) {
-  static const bool off = getenv("URSN_BS2K8") && getenv("URSN_BS2K8")[0] == '0';
-  if (off) return false;
+  if (!ursn_bs2k8_on()) return false;
   if (g.ntaps != 27 || g.K != 8 || g.Nn != 16 || (g.in_cs & 7) || (g.out_cs & 3)) return false;
   for (int j = 0; j < 3; ++j) {
     if (g.so[j] != 1 || g.si[j] != 2 || g.po[j] != 0 || g.q_d[j] != g.out_d[j]) return false;

@@ -193,8 +193,7 @@ __global__ __launch_bounds__(256) void bs2k8w_reduce_kernel(W2RedArgs a) {
 
 struct W2Plan { int zseg, nzseg, nty, ntx, grid, dmin[3]; };
 bool w2_plan(const GatherGeom& g, W2Plan& p) {
-  static const bool off = getenv("URSN_BS2K8") && getenv("URSN_BS2K8")[0] == '0';
-  if (off) return false;
+  if (!ursn_bs2k8_on()) return false;
   if (g.ntaps != 27 || g.K != 8 || g.Nn != 16 || (g.in_cs & 7) || (g.out_cs & 7)) return false;
   for (int j = 0; j < 3; ++j) {
     if (g.si[j] != 2) return false;

@@ -277,7 +277,7 @@ struct BSPlan {
 };
 
 bool bs_plan(const GatherGeom* g, int cnt, BSPlan& p) {
-  static const bool off = getenv("URSN_BSCONV") && getenv("URSN_BSCONV")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BSCONV");
   if (off || cnt != 8) return false;
   const GatherGeom& g0 = g[0];
   if (g0.K < 32 || (g0.K & 31) || g0.Nn < 16 || (g0.Nn & 15) || (g0.in_cs & 7) || (g0.out_cs & 3)) return false;
@@ -309,8 +309,7 @@ bool bs_plan(const GatherGeom* g, int cnt, BSPlan& p) {
   if (p.mt == 3) p.mt = 4;
   p.ncob = (g0.Nn + 16 * p.mt - 1) / (16 * p.mt);
   p.nt = p.mt == 4 ? 4 : 8;
-  static int force_nt = -1;
-  if (force_nt < 0) { const char* e = getenv("URSN_BSCONV_NT"); force_nt = e ? atoi(e) : 0; }
+  static const int force_nt = ursn_env_int("URSN_BSCONV_NT", 0);
   if (force_nt == 4 || (force_nt == 8 && p.mt < 4)) p.nt = force_nt;   // (<4,8> does not fit the register file)
   // small volumes: the 64-voxel box where 128-voxel boxes would leave CUs idle
   const int64_t cvox = (int64_t)g0.N * Zc * Yc * Xc;

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void slab_fold_kernel(float* __restrict__ slab
 }
 static int slab_fold(float* slab, int& nslabs, int& stride, size_t per, hipStream_t s) {
   stride = 1;
-  static const int group = getenv("URSN_SLAB_FOLD") ? atoi(getenv("URSN_SLAB_FOLD")) : 16;   // A/B: 0 | 1 = off
+  static const int group = ursn_env_int("URSN_SLAB_FOLD", 16);   // A/B: 0 | 1 = off
   if (group < 2 || nslabs < 4 * group || (per & 3)) return 0;
   const int ng = (nslabs + group - 1) / group;
   hipLaunchKernelGGL(slab_fold_kernel, dim3((unsigned)((per / 4 + 255) / 256), ng), dim3(256), 0, s, slab, nslabs, per / 4, group);
@@ -463,7 +463,7 @@ __global__ __launch_bounds__(1024) void b3wgradz_reduce_kernel(W3ReduceArgs a) {
 
 struct W3Plan { int zseg, nzseg, nty, ntx, grid; };
 static bool w3_pair(const GatherGeom& g) {
-  static const bool off = getenv("URSN_B3WGRAD_PAIR") && getenv("URSN_B3WGRAD_PAIR")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_B3WGRAD_PAIR");
   return !off && g.K == 8 && g.Nn == 8;
 }
 W3Plan w3_plan(const GatherGeom& g) {
@@ -474,7 +474,7 @@ W3Plan w3_plan(const GatherGeom& g) {
   p.nty = (Y + TY - 1) / TY;
   const int64_t tiles = (int64_t)g.N * p.nty * p.ntx;
   // long columns (three prologue planes each, one slab each), but at least ~2 workgroups per CU slot
-  static const int64_t minwg = getenv("URSN_B3W_MINWG") ? atoi(getenv("URSN_B3W_MINWG")) : 1024;   // A/B
+  static const int64_t minwg = ursn_env_int("URSN_B3W_MINWG", 1024);   // A/B
   int nz = (int)((minwg + tiles - 1) / tiles);
   if (nz < 1) nz = 1;
   if (nz > (Z + 7) / 8) nz = (Z + 7) / 8;
@@ -487,7 +487,7 @@ W3Plan w3_plan(const GatherGeom& g) {
 }  // namespace
 
 bool b3wgrad_ok(const GatherGeom& g) {
-  static const bool off = getenv("URSN_B3WGRAD") && getenv("URSN_B3WGRAD")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_B3WGRAD");
   if (off) return false;
   {   // buffer-path staging (buffer_stage.h): a z plane of either tensor must stay below the out-of-range marker
     const int64_t pv = (int64_t)g.in_d[1] * g.in_d[2], qv = (int64_t)g.out_d[1] * g.out_d[2];
@@ -557,8 +557,8 @@ int launch_b3wgrad(const GatherGeom& g, const bf16_t* S, const bf16_t* C, float*
     // resident workgroups per CU of this weight-gradient kernel beside the main stream's kernels: 49 KB = three (147 of the CU's
     // 160 KB of LDS); URSN_B3WGRADZ_LDSPAD=<KB> pads the request (16: two, 32: one) -- A/B of the LDS share of the two streams.
     // Measured (round 4, cfg5, two rounds on one box): 39.11 / 39.19 ms per step at three, 39.00 / 39.12 at two, 39.12 / 39.09 at
-    // one -- unlike fp32's twgradz (conv_tiled.hip, URSN_WGRADZ_OCC3) the share does not matter here; default unchanged
-    static const int lds_z = WZ::LDS + 1024 * (getenv("URSN_B3WGRADZ_LDSPAD") ? atoi(getenv("URSN_B3WGRADZ_LDSPAD")) : 0);
+    // one -- unlike fp32's twgradz (conv_tiled.hip, make_wplan) the share does not matter here; default unchanged
+    static const int lds_z = WZ::LDS + 1024 * ursn_env_int("URSN_B3WGRADZ_LDSPAD", 0);
     if (!attr) {
       URSN_HIP(hipFuncSetAttribute((const void*)b3wgradz_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_z));
       URSN_HIP(hipFuncSetAttribute((const void*)b3wgradz_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_z));

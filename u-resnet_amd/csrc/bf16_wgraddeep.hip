@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void bdwgrad_reduce_kernel(DWRedArgs a) {
 struct DWPlan { int bq[3], nb[3], hy, hx, hvox, nboxes, per, nslices, ncib, ncob; size_t lds, scratch; };
 
 bool dw_plan(const GatherGeom& g, DWPlan& p) {
-  static const bool off = getenv("URSN_BDWGRAD") && getenv("URSN_BDWGRAD")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_BDWGRAD");
   if (off) return false;
   if (g.ntaps != 27 || g.K < 32 || (g.K & 31) || g.Nn < 64 || (g.Nn & 63) || (g.in_cs & 7) || (g.out_cs & 7)) return false;
   for (int j = 0; j < 3; ++j) {
@@ -230,7 +230,7 @@ bool dw_plan(const GatherGeom& g, DWPlan& p) {
   const int Z = g.in_d[0], Y = g.in_d[1], X = g.in_d[2];
   const int64_t vox = (int64_t)Z * Y * X;
   if (vox * (g.in_cs > g.out_cs ? g.in_cs : g.out_cs) * 2 >= (int64_t)0x40000000) return false;   // one buffer resource per image
-  static const int64_t maxvox = getenv("URSN_BDWGRAD_MAXVOX") ? atoll(getenv("URSN_BDWGRAD_MAXVOX")) : (1 << 18);
+  static const int64_t maxvox = ursn_env_i64("URSN_BDWGRAD_MAXVOX", 1 << 18);
   if ((int64_t)g.N * vox > maxvox || X < 4 || Y < 2) return false;
   p.bq[2] = X >= 16 ? 16 : 8;
   p.bq[1] = p.bq[2] == 16 ? 4 : 8;
@@ -246,7 +246,7 @@ bool dw_plan(const GatherGeom& g, DWPlan& p) {
   if (boxes < 1 || boxes > (1 << 24)) return false;
   p.nboxes = (int)boxes;
   const int nblk = p.ncib * p.ncob;
-  static const int target = getenv("URSN_BDWGRAD_WGS") ? atoi(getenv("URSN_BDWGRAD_WGS")) : 256;
+  static const int target = ursn_env_int("URSN_BDWGRAD_WGS", 256);
   int64_t ns = (target + nblk - 1) / nblk;
   if (ns < 1) ns = 1;
   if (ns > boxes) ns = boxes;

@@ -31,8 +31,7 @@ struct Roctx {
   roctx_push_fn push = nullptr;
   roctx_pop_fn pop = nullptr;
   Roctx() {
-    const char* e = getenv("URSN_ROCTX");
-    if (!(e && e[0] == '1')) return;
+    if (!ursn_env_set("URSN_ROCTX")) return;
     void* h = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_NOW | RTLD_GLOBAL);
     if (!h) h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
     if (!h) h = dlopen("libroctx64.so.4", RTLD_NOW | RTLD_GLOBAL);

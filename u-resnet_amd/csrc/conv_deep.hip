@@ -323,7 +323,7 @@ struct DCPlan {
 };
 
 bool dc_plan(const ursn_conv_desc& d, ConvPass pass, DCPlan& p) {
-  static const bool off = getenv("URSN_DCONV") && getenv("URSN_DCONV")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_DCONV");
   if (off || d.dtype != 0 || (d.ndim != 3 && d.ndim != 2) || d.transposed || d.k != 3 || d.stride != 1) return false;
   if (pass != PASS_FWD && pass != PASS_DGRAD) return false;
   if (d.in_split || d.in_mean || d.pw_dy || d.bs_partial || d.vdz_z) return false;   // the fused forms stay with their kernels
@@ -331,7 +331,7 @@ bool dc_plan(const ursn_conv_desc& d, ConvPass pass, DCPlan& p) {
   const int ics = d.in_cstride > 0 ? d.in_cstride : d.cin, ocs = d.out_cstride > 0 ? d.out_cstride : d.cout;
   p.K = flip ? d.cout : d.cin; p.Nn = flip ? d.cin : d.cout;
   p.ics = flip ? ocs : ics; p.ocs = flip ? ics : ocs;
-  static const int mink = getenv("URSN_DCONV_MINK") ? atoi(getenv("URSN_DCONV_MINK")) : 64;
+  static const int mink = ursn_env_int("URSN_DCONV_MINK", 64);
   if (p.K < mink || (p.K & 63) || p.Nn < 64 || (p.Nn & 15) || (p.ics & 3) || (p.ocs & 3)) return false;
   if (d.ndim == 3) { p.Z = d.in_sp[0]; p.Y = d.in_sp[1]; p.X = d.in_sp[2]; p.ntap = 27; }
   else { p.Z = 1; p.Y = d.in_sp[0]; p.X = d.in_sp[1]; p.ntap = 9; }   // 2-D: one z plane, the 9 in-plane taps
@@ -340,8 +340,8 @@ bool dc_plan(const ursn_conv_desc& d, ConvPass pass, DCPlan& p) {
   const int64_t V = (int64_t)d.n * Z * Y * X;
   // measured against the all-taps implicit GEMM (tools/op_bench.py, 128 channels): 3-D 12^3 x 4 1.45x, 16^3 1.08x, 24^3 1.02-1.05x,
   // 32^3 1.04-1.05x (127-136 TFLOP/s); 2-D 64^2 x 4 1.0x, 32^2 x 16 0.95x, 64^2 x 16 0.92-1.0x: 3-D always, 2-D up to 8192 voxels
-  static const int64_t maxv3 = getenv("URSN_DCONV_MAXVOX") ? atoll(getenv("URSN_DCONV_MAXVOX")) : ((int64_t)1 << 24);
-  static const int64_t maxv2 = getenv("URSN_DCONV_MAXVOX2D") ? atoll(getenv("URSN_DCONV_MAXVOX2D")) : 8192;
+  static const int64_t maxv3 = ursn_env_i64("URSN_DCONV_MAXVOX", (int64_t)1 << 24);
+  static const int64_t maxv2 = ursn_env_i64("URSN_DCONV_MAXVOX2D", 8192);
   if (V > (d.ndim == 3 ? maxv3 : maxv2)) return false;
   if (p.K < 128 && (d.ndim != 3 || V > 65536)) return false;   // 64 contraction channels: 24^3 x 4 1.02-1.06x, 48^3 1.0x, 2-D 0.87x
   if ((int64_t)Z * Y * X * (p.ics > p.ocs ? p.ics : p.ocs) * 4 >= ((int64_t)1 << 31)) return false;
@@ -375,7 +375,7 @@ bool dc_plan(const ursn_conv_desc& d, ConvPass pass, DCPlan& p) {
   if (p.lds > 150 * 1024) return false;
   p.boxes = d.n * p.nb[0] * p.nb[1] * p.nb[2];
   const int64_t tiles = (int64_t)p.boxes * p.tpb;
-  static const int64_t minwg = getenv("URSN_DCONV_MINWG") ? atoi(getenv("URSN_DCONV_MINWG")) : 160;
+  static const int64_t minwg = ursn_env_int("URSN_DCONV_MINWG", 160);
   p.gsplit = 0;
   for (int gs = 1; gs <= 8; gs *= 2) {
     if (p.nchunks % (gs * 4)) continue;

@@ -235,7 +235,7 @@ int launch_gconv_mfma(const GatherGeom& g, const float* in, const float* w, floa
   int64_t vtiles = cdiv64(Q, 16);
   {  // few voxel tiles (the 6^3 level: 54 tiles x 4 column blocks on 256 CUs): 32-column blocks double the workgroups and halve
      // each one's serial k loop -- 0.83 -> 0.62 ms per cfg3 step (16 columns: 0.68); URSN_GCONV_BN=4 restores the wide blocks
-    static const int narrow = getenv("URSN_GCONV_BN") ? atoi(getenv("URSN_GCONV_BN")) : 2;
+    static const int narrow = ursn_env_int("URSN_GCONV_BN", 2);
     if (narrow > 0 && narrow < bn && vtiles * ((g.Nn + 16 * bn - 1) / (16 * bn)) < 256) bn = narrow;
   }
   int gy = (g.Nn + 16 * bn - 1) / (16 * bn);

@@ -3,18 +3,13 @@
 
 #include "conv_igemm_kernel.h"
 
-static int igemm_mode() {  // URSN_IGEMM: 0 = off, 1 = on (default)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("URSN_IGEMM"); v = e ? atoi(e) : 1; }
+bool ursn_igemm_on() {  // URSN_IGEMM=0: off
+  static const bool v = ursn_env_on("URSN_IGEMM");
   return v;
 }
 
 static bool make_igplan(const ursn_conv_desc& d, ConvPass pass, IGPlan& p, int& kcin, int& kcout) {
-  {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("URSN_DISABLE_TILED"); off = (e && e[0] == '1') ? 1 : 0; }
-    if ((off || igemm_mode() == 0) && d.algo != 4) return false;
-  }
+  if ((ursn_tiled_disabled() || !ursn_igemm_on()) && d.algo != 4) return false;
   if (d.transposed || d.k != 3 || d.stride != 1 || d.in_split || d.in_mean) return false;
   if (pass != PASS_FWD && pass != PASS_DGRAD) return false;
   p.flip = (pass == PASS_DGRAD);
@@ -27,9 +22,9 @@ static bool make_igplan(const ursn_conv_desc& d, ConvPass pass, IGPlan& p, int& 
   p.mode = d.ndim;
   if (d.ndim == 3) { p.Z = d.in_sp[0]; p.Y = d.in_sp[1]; p.X = d.in_sp[2]; }
   else { p.Z = 1; p.Y = d.in_sp[0]; p.X = d.in_sp[1]; }
-  static const int min_x = getenv("URSN_IGEMM_MINX") ? atoi(getenv("URSN_IGEMM_MINX")) : 5;
+  static const int min_x = ursn_env_int("URSN_IGEMM_MINX", 5);
   if (p.X < min_x && d.algo != 4) return false;  // below that the gather kernel wastes less
-  static const int at = getenv("URSN_IGEMM_ALLTAPS") ? atoi(getenv("URSN_IGEMM_ALLTAPS")) : 1;
+  static const int at = ursn_env_int("URSN_IGEMM_ALLTAPS", 1);
   // small deep levels (3-D): boxes of 4x4x12 / 3x6x6 voxels with a per-lane voxel table (all-taps kernel, BM = 16)
   p.var = 0;
   if (at && p.mode == 3 && p.X <= 12) p.var = (p.X <= 6) ? 2 : 1;
@@ -64,7 +59,7 @@ static bool make_igplan(const ursn_conv_desc& d, ConvPass pass, IGPlan& p, int& 
       const int nv = BZ * BY * BX;
       p.lds += ((size_t)(kc / 4) * nv * 4 + (size_t)p.bm * kc) * sizeof(float);
     }
-    static const int pad_kb = getenv("URSN_IGEMM_LDS_KB") ? atoi(getenv("URSN_IGEMM_LDS_KB")) : 0;   // A/B: caps the occupancy
+    static const int pad_kb = ursn_env_int("URSN_IGEMM_LDS_KB", 0);   // A/B: caps the occupancy
     if (pad_kb > 0 && p.lds < (size_t)pad_kb * 1024) p.lds = (size_t)pad_kb * 1024;
   }
   return true;

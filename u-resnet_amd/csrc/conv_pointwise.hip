@@ -273,13 +273,8 @@ __global__ __launch_bounds__(256) void pwgrad_kernel(PWgradArgs a) {
 
 // ---- host --------------------------------------------------------------------------------------------------------
 static bool pw_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("URSN_DISABLE_TILED");
-    const char* f = getenv("URSN_POINTWISE");
-    v = ((e && e[0] == '1') || (f && f[0] == '0')) ? 0 : 1;
-  }
-  return v == 1;
+  static const bool v = !ursn_tiled_disabled() && ursn_env_on("URSN_POINTWISE");
+  return v;
 }
 
 static bool pw_geometry(const ursn_conv_desc& d, int lo[3], int sm[3], int64_t& nvox) {
@@ -320,7 +315,7 @@ int pointwise_conv_supported(const ursn_conv_desc& d, ConvPass pass, int accumul
 }
 
 static int pconv_grid_cap() {   // workgroups of the forward / data-gradient kernel (URSN_PCONV_GRID, A/B)
-  static const int cap = getenv("URSN_PCONV_GRID") ? atoi(getenv("URSN_PCONV_GRID")) : 1024;
+  static const int cap = ursn_env_int("URSN_PCONV_GRID", 1024);
   return cap < 1 ? 1 : cap;
 }
 

@@ -642,12 +642,7 @@ struct S2Plan {
 };
 
 static bool s2_enabled(const ursn_conv_desc& d) {
-  static int off = -1;
-  if (off < 0) {
-    const char* e = getenv("URSN_DISABLE_TILED");
-    const char* f = getenv("URSN_STRIDE2");
-    off = ((e && e[0] == '1') || (f && f[0] == '0')) ? 1 : 0;
-  }
+  static const bool off = ursn_tiled_disabled() || !ursn_env_on("URSN_STRIDE2");
   return !off || d.algo == 6;
 }
 
@@ -681,7 +676,7 @@ static bool make_s2plan(const ursn_conv_desc& d, S2Plan& p) {
   g.IZ = hi[0]; g.IY = hi[1]; g.IX = hi[2];
   g.OZ = lo[0]; g.OY = lo[1]; g.OX = lo[2];
   g.pz = pb[0]; g.py = pb[1]; g.px = pb[2];
-  static const int minx = getenv("URSN_S2_MINX") ? atoi(getenv("URSN_S2_MINX")) : 8;
+  static const int minx = ursn_env_int("URSN_S2_MINX", 8);
   if (g.OX < minx && d.algo != 6) return false;   // 16-wide lo-res x tiles: below that the gather kernel wastes less
   const int BZ = p.mode == 3 ? 2 : 1, BY = p.mode == 3 ? 4 : 16, BX = 16;
   g.nbz = (g.OZ + BZ - 1) / BZ;
@@ -770,7 +765,7 @@ int launch_stride2_conv(const ursn_conv_desc& d, ConvPass pass, const float* in,
   // 16 -> 32: 0.182 vs 0.175, 64^2 x 16 128 -> 256: 0.156 vs 0.131 -- except where the old kernel's four / eight 8-channel chunk
   // items per box stall it: 2-D 256^2 x 16 32 -> 64: 0.173 vs 0.321, 128^2 x 16 64 -> 128: 0.173 vs 0.231 (and their transposed
   // twins).  Default: those shapes only.  URSN_S2CONV_V2=0 never, =2 wherever the channel count allows
-  static const int v2mode = getenv("URSN_S2CONV_V2") ? atoi(getenv("URSN_S2CONV_V2")) : 1;
+  static const int v2mode = ursn_env_int("URSN_S2CONV_V2", 1);
   const bool v2 = v2mode == 2 || (v2mode == 1 && p.mode == 2 && (p.K == 32 || p.K == 64));
   if (v2) {
     const bool c16 = (p.K % 16) == 0;

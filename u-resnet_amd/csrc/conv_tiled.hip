@@ -6,12 +6,9 @@
 // of the input (channel stride = the tensor's) and accumulates into a 16-channel slice of the output, so a
 // 32->16 conv is two launches, 32->32 four.  The extra read-modify-write of the output is cheap next to
 // falling back to the gather kernel (25-35 TFLOP/s vs ~90).
-#include <stdlib.h>
-
 #include "conv_tiled_kernel.h"
 #include "wgrad_tiled_kernel.h"
 
-int twgradq_dispatch(const TWPlan& p, const TWgradArgs& a, hipStream_t s);
 int twgrad4_dispatch_3d(const TWPlan& p, const TWgradArgs& a, hipStream_t s);
 int twgrad4_dispatch_2d(const TWPlan& p, const TWgradArgs& a, hipStream_t s);
 int twgradz_dispatch(const TWPlan& p, const TWgradArgs& a, hipStream_t s);
@@ -25,10 +22,9 @@ static bool tiled_shape_ok(int cin, int cout, int mode) {
          (cin == 4 && cout == 8);
 }
 
-static bool tiled_disabled() {  // URSN_DISABLE_TILED=1: route everything through the generic kernels (A/B debugging)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("URSN_DISABLE_TILED"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1;
+bool ursn_tiled_disabled() {  // URSN_DISABLE_TILED=1: route everything through the generic kernels (A/B debugging)
+  static const bool v = ursn_env_set("URSN_DISABLE_TILED");
+  return v;
 }
 
 struct Blocking {
@@ -36,11 +32,6 @@ struct Blocking {
   int bsz = 16;          // block size when > 1 block (16; in_split for a split input)
   bool split = false;    // the blocked side is a split input: block 1 lives in x2 / dx2
 };
-
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 
 // z-segments per (image, xy tile) for the marching kernels.  All workgroups of a launch take about the same time
 // (~ zseg + prologue planes), so the launch costs rounds x (zseg + 3) with rounds = ceil(workgroups / resident slots):
@@ -56,23 +47,16 @@ int ursn_cu_count() {
   return n;
 }
 void ursn_pick_zseg(int64_t base, int Z, int occ, int min_seg, int& zseg, int& nzseg) {
-  static const int legacy = getenv("URSN_ZSEG_LEGACY") ? atoi(getenv("URSN_ZSEG_LEGACY")) : 0;
   const int64_t slots = (int64_t)(occ > 0 ? occ : 1) * ursn_cu_count();
   int best_seg = Z;
   int64_t best_cost = -1;
-  if (legacy) {   // powers of two up to `legacy` workgroups (A/B)
-    int nz = 1;
-    while (base * nz < legacy && Z / (nz * 2) >= min_seg) nz *= 2;
-    best_seg = (Z + nz - 1) / nz;
-  } else {
-    for (int nz = 1; nz <= Z; ++nz) {
-      const int seg = (Z + nz - 1) / nz;
-      if (seg < min_seg && nz > 1) break;
-      const int ns = (Z + seg - 1) / seg;
-      const int64_t rounds = (base * ns + slots - 1) / slots;
-      const int64_t cost = rounds * (seg + 3);
-      if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_seg = seg; }
-    }
+  for (int nz = 1; nz <= Z; ++nz) {
+    const int seg = (Z + nz - 1) / nz;
+    if (seg < min_seg && nz > 1) break;
+    const int ns = (Z + seg - 1) / seg;
+    const int64_t rounds = (base * ns + slots - 1) / slots;
+    const int64_t cost = rounds * (seg + 3);
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_seg = seg; }
   }
   zseg = best_seg;
   nzseg = (Z + zseg - 1) / zseg;
@@ -123,7 +107,7 @@ static bool spatial_tiles(const ursn_conv_desc& d, int& Z, int& Y, int& X, int& 
 }
 
 static bool make_plan(const ursn_conv_desc& d, ConvPass pass, TPlan& p, Blocking& b) {
-  if (tiled_disabled() && d.algo != 3) return false;
+  if (ursn_tiled_disabled() && d.algo != 3) return false;
   if (d.transposed || d.k != 3 || d.stride != 1) return false;
   if (pass != PASS_FWD && pass != PASS_DGRAD) return false;
   p.mode = d.ndim;
@@ -288,36 +272,24 @@ int launch_tiled_conv(const ursn_conv_desc& d, ConvPass pass, const float* in, c
 // weight gradient
 // ---------------------------------------------------------------------------------------------------------
 static bool wgrad4_enabled() {  // URSN_WGRAD4=0: keep the 16x16x4 kernel for Cout <= 8 too (A/B)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("URSN_WGRAD4"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
+  static const bool v = ursn_env_on("URSN_WGRAD4");
+  return v;
 }
 static bool use_wgrad4(const ursn_conv_desc& d, const TWPlan& p) {
   // measured (profiles/r01): the 4x4x1 form needs one LDS operand per 8-cycle MFMA and loses to the 16x16x4 kernel
-  // at Cout = 8 (37 vs 42 TFLOP/s) but wins for the 3|4-channel logits layer (1.4 vs 2.0 ms); URSN_WGRAD4=8 forces it
-  static int force8 = -1;
-  if (force8 < 0) { const char* e = getenv("URSN_WGRAD4"); force8 = (e && e[0] == '8') ? 1 : 0; }
+  // at Cout = 8 (37 vs 42 TFLOP/s) but wins for the 3|4-channel logits layer (1.4 vs 2.0 ms)
   if (!wgrad4_enabled() || !(d.cin == 8 || d.cin == 16)) return false;
   if (d.ndim == 3 && d.cin == 16 && p.cout == 4) return false;
-  return p.cout == 4 || (force8 && p.cout == 8);
+  return p.cout == 4;
 }
 
 static bool use_wgradz(const ursn_conv_desc& d) {  // Cout == 8: plane-pair kernel (URSN_WGRADZ=0 disables, A/B)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("URSN_WGRADZ"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1 && d.cout == 8 && (d.cin == 8 || d.cin == 16);
-}
-
-// 3-D Cout == 8: 4x4-block kernel, no padded MFMA rows (wgradq_tiled_kernel.h).  Measured equal to the plane-pair kernel
-// (1.24 vs 1.225 ms at 192^3 x 4), so it is opt-in: URSN_WGRADQ=1
-static bool use_wgradq(const ursn_conv_desc& d) {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("URSN_WGRADQ"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1 && d.ndim == 3 && use_wgradz(d);
+  static const bool v = ursn_env_on("URSN_WGRADZ");
+  return v && d.cout == 8 && (d.cin == 8 || d.cin == 16);
 }
 
 static bool make_wplan(const ursn_conv_desc& d, TWPlan& p, Blocking& b) {
-  if (tiled_disabled() && d.algo != 3) return false;
+  if (ursn_tiled_disabled() && d.algo != 3) return false;
   if (d.transposed || d.k != 3 || d.stride != 1) return false;
   p.mode = d.ndim; p.cin = d.cin; p.cout = (d.cout + 3) & ~3;
   const int ics = d.in_cstride > 0 ? d.in_cstride : d.cin, ocs = d.out_cstride > 0 ? d.out_cstride : d.cout;
@@ -352,34 +324,25 @@ static bool make_wplan(const ursn_conv_desc& d, TWPlan& p, Blocking& b) {
     }
     const int py = ty + (p.mode == 3 ? 2 : 0);
     p.lds = ((size_t)6 * PX * py * 8 + (size_t)2 * TX * ty * 8) * sizeof(float) + 256;   // 6 x planes, 2 dz planes
-    if (use_wgradq(d)) p.lds = ((size_t)4 * 6 * 8 * 48 + (size_t)2 * 4 * 8 * 48) * sizeof(float);   // QTile::LDS: 4 x planes, 2 dz planes, channel-major rows of 48
-    // 3-D, plain input: 159 VGPRs and 46.5 KB would run THREE workgroups per CU (URSN_WGRADZ_OCC3=1).  Measured (round 4, three
-    // A/B pairs on one box): the kernel alone 1.125 -> 1.08 ms per launch (0.552 -> 0.576 of the MFMA peak), but the step with the
-    // weight gradients beside the main stream 58.48 -> 58.70 ms -- three resident workgroups hold 140 of the CU's 160 KB of LDS
-    // and the main stream's kernels (43.5 KB per workgroup) wait for a slot.  Default: LDS padded to two workgroups per CU.
-    static const bool occ3 = getenv("URSN_WGRADZ_OCC3") && getenv("URSN_WGRADZ_OCC3")[0] == '1';
-    vg = (p.mode == 3 && !d.in_mean && !use_wgradq(d) && occ3) ? 3 : 2;
-    // (A/B of the other direction, URSN_WGRADZ_LDSPAD=40 = ONE workgroup per CU: the kernel alone 7.0 -> 8.2 ms per step, the
-    // overlapped step 58.86 -> 58.74 ms, two pairs on one box -- the main stream gains what the weight gradients lose; not the
-    // default: 0.2 % against a fifth of the dominant kernel's rate when it runs alone)
-    static const int pad_kb = getenv("URSN_WGRADZ_LDSPAD") ? atoi(getenv("URSN_WGRADZ_LDSPAD")) : 8;
-    if (p.mode == 3 && !use_wgradq(d) && !occ3) p.lds += (size_t)pad_kb * 1024;
+    // 3-D, plain input: 159 VGPRs and 46.5 KB would run THREE workgroups per CU.  Measured (round 4, three A/B pairs on one
+    // box): the kernel alone 1.125 -> 1.08 ms per launch (0.552 -> 0.576 of the MFMA peak), but the step with the weight
+    // gradients beside the main stream 58.48 -> 58.70 ms -- three resident workgroups hold 140 of the CU's 160 KB of LDS and
+    // the main stream's kernels (43.5 KB per workgroup) wait for a slot.  So the LDS is padded by 8 KB to two workgroups per CU.
+    // (The other direction, padded by 40 KB to ONE workgroup per CU: the kernel alone 7.0 -> 8.2 ms per step, the overlapped
+    // step 58.86 -> 58.74 ms, two pairs on one box -- 0.2 % against a fifth of the dominant kernel's rate when it runs alone.)
+    vg = 2;
+    if (p.mode == 3) p.lds += (size_t)8 * 1024;
   } else if (!blocked_shape && use_wgrad4(d, p)) vg = 2;
   {  // the per-wave accumulator copies of the final cross-wave sum reuse the plane rings
     const int taps = p.mode == 3 ? 27 : 9;
-    size_t red = use_wgradq(d) ? 0
-                 : use_wgradz(d) ? (size_t)(p.mode == 3 ? 2 : 8) * 2 * taps * 64 * sizeof(float)
-                                 : (size_t)4 * taps * p.cin * p.cout * sizeof(float);
+    size_t red = use_wgradz(d) ? (size_t)(p.mode == 3 ? 2 : 8) * 2 * taps * 64 * sizeof(float)
+                               : (size_t)4 * taps * p.cin * p.cout * sizeof(float);
     if (red > p.lds) p.lds = red;
   }
   if (p.lds > 160 * 1024) return false;
   if (d.in_mean && (blocked_shape || (!use_wgradz(d) && use_wgrad4(d, p)))) return false;   // kernels without the staging affine
   ursn_pick_zseg(p.grid, p.Z, occ_limit(vg, p.lds), 8, p.zseg, p.nzseg);
-  if (use_wgradz(d) && !use_wgradq(d)) {
-    static const int force_nz = getenv("URSN_WGRADZ_NZ") ? atoi(getenv("URSN_WGRADZ_NZ")) : 0;   // A/B
-    if (force_nz > 0) { p.zseg = (p.Z + force_nz - 1) / force_nz; p.nzseg = (p.Z + p.zseg - 1) / p.zseg; }
-    if ((p.zseg & 1) && p.nzseg > 1) { p.zseg += 1; p.nzseg = (p.Z + p.zseg - 1) / p.zseg; }   // plane pairs
-  }
+  if (use_wgradz(d) && (p.zseg & 1) && p.nzseg > 1) { p.zseg += 1; p.nzseg = (p.Z + p.zseg - 1) / p.zseg; }   // plane pairs
   p.grid *= p.nzseg;
   return true;
 }
@@ -396,7 +359,6 @@ size_t tiled_wgrad_scratch_bytes(const ursn_conv_desc& d) {
   if (!make_wplan(d, p, b)) return 0;
   int taps = d.ndim == 3 ? 27 : 9;
   int ci = (b.nbi > 1 || b.nbo > 1) ? 16 : d.cin, co = (b.nbi > 1 || b.nbo > 1) ? 16 : d.cout;
-  if (use_wgradq(d)) return (size_t)p.grid * taps * 8 * 8 * sizeof(float);
   if (use_wgradz(d)) return (size_t)p.grid * 2 * taps * 8 * 8 * sizeof(float);   // two slabs per workgroup
   return (size_t)p.grid * taps * ci * co * sizeof(float);   // one slab per workgroup
 }
@@ -430,9 +392,8 @@ int launch_tiled_wgrad(const ursn_conv_desc& d, const float* x, const float* dy,
         a.x = d.x2;
         a.x_cs = d.in2_cstride > 0 ? d.in2_cstride : d.cin - d.in_split;
       }
-      const bool quad = use_wgradq(d);
-      const int nslab = quad ? p.grid : p.grid * 2;
-      URSN_TRY(quad ? twgradq_dispatch(p, a, s) : twgradz_dispatch(p, a, s));
+      const int nslab = p.grid * 2;
+      URSN_TRY(twgradz_dispatch(p, a, s));
       if (d.cin == 8) return launch_reduce_accum(dw, (const float*)scratch, (int64_t)taps * 64, nslab, s);
       URSN_TRY(launch_reduce_accum_blocked(dw + (size_t)8 * bi * 8, (const float*)scratch, taps, 8, 8, (int64_t)d.cin * 8,
                                            8, nslab, s));

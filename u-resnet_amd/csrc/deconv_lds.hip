@@ -216,12 +216,7 @@ struct ScPlan {
 
 static bool make_scplan(const ursn_conv_desc& d, ConvPass pass, ScPlan& p) {
   {
-    static int off = -1;
-    if (off < 0) {
-      const char* e = getenv("URSN_DISABLE_TILED");
-      const char* f = getenv("URSN_SCATTER_LDS");
-      off = ((e && e[0] == '1') || (f && f[0] == '0')) ? 1 : 0;
-    }
+    static const bool off = ursn_tiled_disabled() || !ursn_env_on("URSN_SCATTER_LDS");
     if (off && d.algo != 7) return false;
   }
   if (d.in_split || d.pw_dy || d.in_mean) return false;

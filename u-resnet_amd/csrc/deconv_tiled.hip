@@ -20,11 +20,7 @@ int tdeconv_dispatch_2d(const TDPlan& p, const TDeconvArgs& a, hipStream_t s) {
 struct DBlocking { int nbk = 1, nbp = 1, pb = 0; };  // contraction blocks of 16, produced blocks of pb channels
 
 static bool make_dplan(const ursn_conv_desc& d, ConvPass pass, TDPlan& p, DBlocking& b) {
-  {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("URSN_DISABLE_TILED"); off = (e && e[0] == '1') ? 1 : 0; }
-    if (off && d.algo != 3) return false;
-  }
+  if (ursn_tiled_disabled() && d.algo != 3) return false;
   // transposed conv forward, or data gradient of a k3 stride-2 conv
   if (d.in_split || d.in_mean) return false;
   if (d.pw_dy && (pass != PASS_DGRAD || d.transposed || !d.pw_w)) return false;

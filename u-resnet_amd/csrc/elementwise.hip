@@ -56,7 +56,7 @@ static Map make_map(int64_t V, int C, int VEC) {
   m.shift = 0;
   while ((1 << m.shift) < m.CP) ++m.shift;
   m.VPB = 256 / m.CP;
-  static const int cap = getenv("URSN_EW_GRID") ? atoi(getenv("URSN_EW_GRID")) : 512;   // two long-lived workgroups per CU (tools/lib_ab.sh)
+  static const int cap = ursn_env_int("URSN_EW_GRID", 512);   // two long-lived workgroups per CU (tools/lib_ab.sh)
   int64_t blocks = cdiv64(V, (int64_t)m.VPB * 8);
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
@@ -649,7 +649,7 @@ int launch_head_final(const double* partial, int nblocks, int n, int64_t pix, fl
 }
 
 int head_blocks(int n, int64_t pix) {
-  static const int cap = getenv("URSN_HEAD_GRID") ? atoi(getenv("URSN_HEAD_GRID")) : 4096;
+  static const int cap = ursn_env_int("URSN_HEAD_GRID", 4096);
   int64_t b = cdiv64((int64_t)n * pix, 256 * 4);
   if (b > cap) b = cap;
   if (b < 1) b = 1;

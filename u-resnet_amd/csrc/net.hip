@@ -20,20 +20,6 @@ int wgrad_dispatch(const ursn_conv_desc& d, const float* x, const float* dy, flo
 
 namespace {
 
-struct Arena {
-  char* base = nullptr;
-  size_t off = 0;
-  void* take(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    void* p = base ? (void*)(base + off) : nullptr;
-    off += bytes;
-    return p;
-  }
-  float* floats(int64_t n) { return (float*)take((size_t)n * sizeof(float)); }
-};
-
-const char* g_last_kernel_dummy = "";
-
 struct Act {       // activation tensor view (+ gradient view with identical layout)
   float* p = nullptr;
   float* g = nullptr;
@@ -219,7 +205,7 @@ int plan(ursn_net* n, Arena& A) {
   for (int i = 0; i < ns; ++i) {
     const int lvl = ns - 1 - i, co = F << (ns - 1 - i);
     {
-      const char* e = getenv("URSN_SPLIT_CAT");
+      const bool split_on = ursn_env_on("URSN_SPLIT_CAT");
       ursn_conv_desc d3;
       memset(&d3, 0, sizeof(d3));
       d3.ndim = c.ndim; d3.n = c.max_batch;
@@ -227,7 +213,7 @@ int plan(ursn_net* n, Arena& A) {
       d3.cin = 2 * co; d3.cout = co; d3.k = 3; d3.stride = 1; d3.in_split = co;
       ursn_conv_desc d1 = d3;
       d1.k = 1;
-      split[i] = !(e && e[0] == '0') && co <= 8 && tiled_conv_supported(d3, PASS_FWD) && tiled_conv_supported(d3, PASS_DGRAD) &&
+      split[i] = split_on && co <= 8 && tiled_conv_supported(d3, PASS_FWD) && tiled_conv_supported(d3, PASS_DGRAD) &&
                  pointwise_conv_supported(d1, PASS_FWD, 0) && pointwise_conv_supported(d1, PASS_DGRAD, 1) &&
                  (!tr || (tiled_wgrad_supported(d3) && pointwise_wgrad_supported(d1)));
     }
@@ -261,8 +247,7 @@ int plan(ursn_net* n, Arena& A) {
        // is never written.  Rounds 1-2 measured it neutral (-0.7 ms of bn_act passes, +0.3..0.5 ms in the conv kernels) and
        // left it off; with the buffer-path staging of round 3 the affine instantiations lost their spills and gained a
        // workgroup per CU: 65.2 -> 65.9 images/s at cfg3, on by default.
-      const char* e = getenv("URSN_NORM_ON_LOAD");
-      const int nol = e ? atoi(e) : 1;
+      const int nol = ursn_env_int("URSN_NORM_ON_LOAD", 1);
       ursn_conv_desc d2;
       memset(&d2, 0, sizeof(d2));
       d2.ndim = c.ndim; d2.n = c.max_batch;
@@ -278,11 +263,8 @@ int plan(ursn_net* n, Arena& A) {
     u.a1 = make_act(n, A, lout, co, tr, u.a1_virtual);
     u.c2 = add_layer(n, A, scope + "/resnet_conv2", 0, 3, 1, co, co, lout, lout, poff);
     u.out = out_view ? *out_view : make_act(n, A, lout, co, tr);
-    {
-      const char* e = getenv("URSN_RELU_MASK");
-      if (tr && bn_mask_ok(co) && !(e && e[0] == '0'))
-        u.jmask = (unsigned long long*)A.take(bn_mask_words((int64_t)c.max_batch * n->lvox[lout], co) * sizeof(unsigned long long));
-    }
+    if (tr && bn_mask_ok(co) && ursn_env_on("URSN_RELU_MASK"))
+      u.jmask = (unsigned long long*)A.take(bn_mask_words((int64_t)c.max_batch * n->lvox[lout], co) * sizeof(unsigned long long));
     n->units.push_back(u);
     n->named[u.scope] = u.out;
     n->named[n->layers[u.c1].name] = u.a1;
@@ -547,7 +529,7 @@ int unit_fwd(ursn_net* n, Unit& u, int N, hipStream_t s) {
   // the 1x1 shortcut is HBM-bound and independent of conv1 / conv2 until the join: it runs beside them on the second stream
   hipEvent_t side_done = nullptr;
   if (u.sc >= 0) {
-    static const bool side_off = getenv("URSN_FWD_SIDE_STREAM") && getenv("URSN_FWD_SIDE_STREAM")[0] == '0';
+    static const bool side_off = !ursn_env_on("URSN_FWD_SIDE_STREAM");
     hipEvent_t fork = (n->s2 && !side_off) ? fwd_event(n) : nullptr;
     hipEvent_t join = fork ? fwd_event(n) : nullptr;
     if (fork && join) {
@@ -614,7 +596,7 @@ int head(ursn_net* n, const float* data, const float* label, const float* weight
   a.ana_out = ana_out;
   a.scratch = n->head_scratch; a.metrics = n->metrics;
   // the logits layer's BatchNorm-backward sums ride in the head (dlogits and z are in its registers): one pass of two tensors less
-  static const bool fuse = !(getenv("URSN_HEAD_BN_BWD") && getenv("URSN_HEAD_BN_BWD")[0] == '0');
+  static const bool fuse = ursn_env_on("URSN_HEAD_BN_BWD");
   n->bs_layer = -1;
   if (want_grad && fuse && n->bs_scratch && L.zcs == 4 && a.ncls <= 4 && head_blocks(N, n->lvox[0]) <= 16384) {
     a.bs_partial = n->bs_scratch;
@@ -672,7 +654,7 @@ int conv_bwd(ursn_net* n, int li, const Act& in, bool need_dgrad, int N, hipStre
     ursn_conv_desc t = bwd_desc(n, li, in, N, nullptr, -1);
     t.vdz_z = L.z; t.vdz_coef = L.coef; t.vdz_out = L.dz; t.vdz_relu = n->vdz_relu;
     n->bs_layer = -1;
-    static const bool bs_off = getenv("URSN_FUSE_BN_BWD_REDUCE") && getenv("URSN_FUSE_BN_BWD_REDUCE")[0] == '0';
+    static const bool bs_off = !ursn_env_on("URSN_FUSE_BN_BWD_REDUCE");
     if (bs && bs->li >= 0 && !bs_off) {
       const Layer& T = n->layers[bs->li];
       ursn_conv_desc u = t;
@@ -720,7 +702,7 @@ int conv_bwd(ursn_net* n, int li, const Act& in, bool need_dgrad, int N, hipStre
     if (in2) URSN_REQUIRE(take_flag(n, *in2) == acc, "split input: the two halves disagree on gradient initialisation");
     d = bwd_desc(n, li, in, N, in2, fused_sc);   // the data gradient does not read x: no normalise-on-load fields
     n->bs_layer = -1;
-    static const bool bs_off = getenv("URSN_FUSE_BN_BWD_REDUCE") && getenv("URSN_FUSE_BN_BWD_REDUCE")[0] == '0';
+    static const bool bs_off = !ursn_env_on("URSN_FUSE_BN_BWD_REDUCE");
     if (bs && bs->li >= 0 && !bs_off) {
       const Layer& T = n->layers[bs->li];
       ursn_conv_desc t = d;
@@ -754,10 +736,10 @@ int conv_bwd(ursn_net* n, int li, const Act& in, bool need_dgrad, int N, hipStre
 // Measured (round 4, cfg3): the data gradient pays for the extra staging in matrix-pipe issue slots -- conv1's launch 0.97 ->
 // 1.29 ms for 0.47 ms of apply pass removed (net -0.15 ms), but the launch that ALSO carries the two-z reductions of a
 // residual join below drops from 3 to 2 waves per SIMD (190 VGPRs) and goes 1.18 -> 1.84 ms: by default only launches
-// without a second z take the fusion (URSN_FUSE_BN_BWD_APPLY=2: all, 0: none).
+// without a second z take the fusion.
 bool vdz_ok(ursn_net* n, int li, const Act& in, int N, bool two_z_target) {
-  static const int mode = getenv("URSN_FUSE_BN_BWD_APPLY") ? atoi(getenv("URSN_FUSE_BN_BWD_APPLY")) : 1;
-  const bool off = mode == 0 || (mode == 1 && two_z_target);
+  static const bool on = ursn_env_on("URSN_FUSE_BN_BWD_APPLY");
+  const bool off = !on || two_z_target;
   const Layer& L = n->layers[li];
   if (off || n->cfg.ndim != 3 || L.kind || L.k != 3 || L.stride != 1 || L.cin != 8 || L.cout != 8 || L.zcs != 8 || in.C != 8 || in.cs != 8 || !in.g)
     return false;
@@ -822,7 +804,7 @@ int unit_bwd(ursn_net* n, Unit& u, int N, hipStream_t s, const BsTarget* in_targ
   // stride-1 shortcut next to a tiled conv1: its data gradient rides in conv1's data-gradient kernel
   bool fuse = false;
   if (u.sc >= 0 && n->layers[u.sc].stride == 1) {
-    static const bool off = getenv("URSN_FUSE_SHORTCUT_DGRAD") && getenv("URSN_FUSE_SHORTCUT_DGRAD")[0] == '0';
+    static const bool off = !ursn_env_on("URSN_FUSE_SHORTCUT_DGRAD");
     ursn_conv_desc d = bwd_desc(n, u.c1, u.in, N, in2, u.sc), d0 = bwd_desc(n, u.c1, u.in, N, in2, -1);
     // where conv1's dgrad runs on the all-taps implicit GEMM it carries the term itself; else only where it is tiled anyway
     fuse = !off && ((!in2 && igemm_conv_supported(d, PASS_DGRAD)) ||
@@ -831,7 +813,7 @@ int unit_bwd(ursn_net* n, Unit& u, int N, hipStream_t s, const BsTarget* in_targ
   // stride-2 unit on the lane-per-low-res-voxel kernel: the shortcut's data gradient (it touches the even-even-even voxels only)
   // rides in conv1's scatter-type data gradient (deconv_tiled_kernel.h, PW); URSN_FUSE_SHORTCUT_DGRAD_S2=0: the separate pass
   if (u.sc >= 0 && n->layers[u.sc].stride == 2 && !in2) {
-    static const bool off2 = getenv("URSN_FUSE_SHORTCUT_DGRAD_S2") && getenv("URSN_FUSE_SHORTCUT_DGRAD_S2")[0] == '0';
+    static const bool off2 = !ursn_env_on("URSN_FUSE_SHORTCUT_DGRAD_S2");
     ursn_conv_desc d = bwd_desc(n, u.c1, u.in, N, nullptr, u.sc);
     fuse = !off2 && n->layers[u.sc].zcs == n->layers[u.sc].cout && tiled_deconv_supported(d, PASS_DGRAD);
   }
@@ -984,12 +966,10 @@ extern "C" int ursn_create(const ursn_config* cfg, float* params, float* grads, 
   if (rc) { delete n; return rc; }
   n->params = params; n->grads = grads; n->adam_m = adam_m; n->adam_v = adam_v;
   {
-    const char* e = getenv("URSN_WGRAD_STREAM");
-    if (!(e && e[0] == '0')) {   // also for inference-only nets: the forward pass runs the shortcut convs on it
+    if (ursn_env_on("URSN_WGRAD_STREAM")) {   // also for inference-only nets: the forward pass runs the shortcut convs on it
       int prio_lo = 0, prio_hi = 0;   // lowest priority: the dgrad / BN chain on the caller's stream is the critical path
       (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-      const char* pe = getenv("URSN_WGRAD_PRIO");
-      int prio = pe ? atoi(pe) : prio_lo;
+      const int prio = ursn_env_int("URSN_WGRAD_PRIO", prio_lo);
       if (hipStreamCreateWithPriority(&n->s2_owned, hipStreamNonBlocking, prio) != hipSuccess ||
           hipEventCreateWithFlags(&n->s2_done, hipEventDisableTiming) != hipSuccess) {
         ursn_set_error("create: could not create the weight-gradient stream");
@@ -1089,7 +1069,7 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
   // second stream off, one chain of nodes: for a graph with forked branches the HIP 7.0 runtime's hipGraphLaunch reads past its
   // pool of branch streams and faults on the host.
   // URSN_GRAPH=1: when the batch holds <= 2^20 voxels, 2: always.  Never while profiling (events per launch).
-  static const int gmode = getenv("URSN_GRAPH") ? atoi(getenv("URSN_GRAPH")) : 0;
+  static const int gmode = ursn_env_int("URSN_GRAPH", 0);
   bool geligible = gmode > 0 && !net->profile && !net->graph_broken && !ursn_roctx_on() &&
                    (gmode > 1 || (int64_t)n * net->lvox[0] <= ((int64_t)1 << 20));
   auto run_on = [&](hipStream_t rs) -> int {
@@ -1140,7 +1120,7 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
       if (ok) ok = hipStreamEndCapture(net->gstream, &graph) == hipSuccess && graph != nullptr;
       if (ok && rc == 0) ok = hipGraphInstantiate(&sg->exec, graph, nullptr, nullptr, 0) == hipSuccess;
       if (graph) (void)hipGraphDestroy(graph);
-      if (getenv("URSN_GRAPH_DEBUG")) fprintf(stderr, "ursn graph capture: ok=%d rc=%d\n", (int)ok, rc);
+      if (ursn_env_str("URSN_GRAPH_DEBUG")) fprintf(stderr, "ursn graph capture: ok=%d rc=%d\n", (int)ok, rc);
       if (ok && rc == 0) {
         URSN_TRY(graph_launch(sg->exec));
       } else {   // nothing of the captured step ran: give up on graphs and run it the ordinary way

@@ -19,21 +19,9 @@
 
 #include "bf16_common.h"
 #include "bf16_pack.h"
-#include <functional>
 #include "net_bf16.h"
 
 namespace {
-
-struct Arena {
-  char* base = nullptr;
-  size_t off = 0;
-  void* take(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    void* p = base ? (void*)(base + off) : nullptr;
-    off += bytes;
-    return p;
-  }
-};
 
 struct BAct {              // activation view + its gradient view (same layout)
   bf16_t* p = nullptr;
@@ -111,8 +99,6 @@ struct ursn_bnet {
   void* head_scratch = nullptr;
   void* wg_scratch = nullptr; size_t wg_bytes = 0;
   double* stats2 = nullptr;
-  std::vector<std::function<int()>> deferred;   // weight-gradient launches held back while the decoder is at level 0
-  bool defer_on = true, defer_open = false;
   hipStream_t s2 = nullptr;
   hipEvent_t s2_done = nullptr;
   std::vector<hipEvent_t> evs;
@@ -226,15 +212,15 @@ int plan(ursn_bnet* n, Arena& A) {
   {
     GatherGeom g[8];
     const BLayer& L0 = n->layers[n->conv0];
-    n->scalar_in = c.cin == 1 && !(getenv("URSN_BF16_SCALAR_IN") && getenv("URSN_BF16_SCALAR_IN")[0] == '0') &&
+    n->scalar_in = c.cin == 1 && ursn_env_on("URSN_BF16_SCALAR_IN") &&
                    layer_geoms(n, L0, PASS_FWD, c.max_batch, L0.kin, L0.kout, g) == 1 && b3conv_ok(g[0]) && g[0].K == 8 &&
                    (!tr || (layer_geoms(n, L0, PASS_WGRAD, c.max_batch, L0.kin, L0.kout, g) == 1 && b3wgrad_scalar_ok(g[0])));
   }
-  n->skip0_own = F == 8 && !(getenv("URSN_BF16_SKIP0_OWN") && getenv("URSN_BF16_SKIP0_OWN")[0] == '0');
+  n->skip0_own = F == 8 && ursn_env_on("URSN_BF16_SKIP0_OWN");
   // ... and the skip's half IS the gradient tensor of conv0's activation: the encoder's data gradients (module0, run later in
   // the backward pass) accumulate into it, so conv0's BatchNorm backward reads one gradient tensor in each of its two passes
   // instead of two (URSN_BF16_SKIP0_MERGE=0: a tensor of its own for the encoder's share)
-  n->skip0_merge = n->skip0_own && tr && !(getenv("URSN_BF16_SKIP0_MERGE") && getenv("URSN_BF16_SKIP0_MERGE")[0] == '0');
+  n->skip0_merge = n->skip0_own && tr && ursn_env_on("URSN_BF16_SKIP0_MERGE");
   n->a_conv0 = n->skip0_own ? make_act(n, A, 0, F, tr && !n->skip0_merge) : fmap_view(0);
   if (n->skip0_own && tr) {
     const size_t bytes = (size_t)c.max_batch * n->lvox[0] * 8 * sizeof(bf16_t);
@@ -244,7 +230,7 @@ int plan(ursn_bnet* n, Arena& A) {
   }
   // can the consumer layer L (k3 s1, C -> C) apply its producer's BatchNorm while staging (forward and weight gradient)?
   auto virtual_ok = [&](const BLayer& L) {
-    static const bool off = getenv("URSN_BF16_NORM_ON_LOAD") && getenv("URSN_BF16_NORM_ON_LOAD")[0] == '0';
+    static const bool off = !ursn_env_on("URSN_BF16_NORM_ON_LOAD");
     if (off) return false;
     GatherGeom g[8];
     if (layer_geoms(n, L, PASS_FWD, c.max_batch, L.kin, L.kout, g) != 1 || !b3conv_aff_ok(g[0])) return false;
@@ -261,7 +247,7 @@ int plan(ursn_bnet* n, Arena& A) {
     u.a1 = make_act(n, A, lout, co, tr, !virt);
     if (virt) { u.a1.aff_layer = u.c1; u.a1.aff_relu = 0; }
     u.out = out_view ? *out_view : make_act(n, A, lout, co, tr);
-    if (tr && !(getenv("URSN_BF16_RELU_MASK") && getenv("URSN_BF16_RELU_MASK")[0] == '0'))
+    if (tr && ursn_env_on("URSN_BF16_RELU_MASK"))
       u.jmask = (unsigned char*)A.take((size_t)c.max_batch * n->lvox[lout] * (pad8(co) / 8) + 256);
     n->units.push_back(u);
     n->named["UResNet/" + scope] = u.out;
@@ -555,7 +541,7 @@ int unit_fwd(ursn_bnet* n, BUnit& u, int N, hipStream_t s) {
   // The 1x1 shortcut conv reads the unit's input like conv1 and is needed at the join only: it runs on the second stream beside
   // conv1 -> BatchNorm -> conv2 (these passes sit at 4-5 TB/s each, latency-bound; together they use more of the HBM).
   // URSN_BF16_FWD_OVERLAP=0: in line.
-  static const bool overlap = !(getenv("URSN_BF16_FWD_OVERLAP") && getenv("URSN_BF16_FWD_OVERLAP")[0] == '0');
+  static const bool overlap = ursn_env_on("URSN_BF16_FWD_OVERLAP");
   hipEvent_t joined = nullptr;
   bool fused_sc = false;
   if (u.sc >= 0) {   // stride-2 conv 8 -> 16 with its 1x1 stride-2 shortcut: ONE pass over the fine tensor (bf16_s2k8.hip)
@@ -601,7 +587,7 @@ int forward(ursn_bnet* n, const float* data, int N, hipStream_t s) {
   // Weight packing: every (layer, pass) has its own packed buffer; from the second step at a batch size on, ONE launch here
   // fills them all and the launchers find their job done (bf16_pack.h).  URSN_BF16_PREPACK=0: every launcher packs for itself.
   n->ev_used = 0;
-  static const bool prepack = !(getenv("URSN_BF16_PREPACK") && getenv("URSN_BF16_PREPACK")[0] == '0');
+  static const bool prepack = ursn_env_on("URSN_BF16_PREPACK");
   if (prepack && n->pack.d_jobs) {
     if (n->pack_N != N) { n->pack.clear(); n->pack_N = N; }
     bpack_set_ctx(&n->pack);
@@ -655,7 +641,7 @@ int head(ursn_bnet* n, const float* data, const float* label, const float* weigh
   a.softmax_out = softmax_out; a.dlogits = want_grad ? n->dlog : nullptr; a.dl_cs = 8; a.ana_out = ana_out;
   a.metrics = n->metrics; a.scratch = n->head_scratch;
   // the logits layer's BatchNorm-backward sums ride in the head (dlogits and z are in its registers): one pass of two tensors less
-  static const bool fuse = !(getenv("URSN_BF16_HEAD_BN_BWD") && getenv("URSN_BF16_HEAD_BN_BWD")[0] == '0');
+  static const bool fuse = ursn_env_on("URSN_BF16_HEAD_BN_BWD");
   n->bs_layer = -1;
   if (want_grad && fuse && n->bs_scratch && L.kout == 8 && bhead_blocks(N, n->lvox[0]) <= 16384) {
     a.bs_partial = n->bs_scratch;
@@ -687,52 +673,38 @@ int conv_bwd(ursn_bnet* n, int li, const BAct& in, bool need_dgrad, int N, hipSt
   GatherGeom g[8];
   int Kw, Nw;
   if (!skip_wgrad) {  // weight gradient on the second stream, ordered after the dz it reads
-    const BAct inw = in;   // (by value: a deferred launch outlives the caller's reference)
-    auto wgrad = [n, li, inw, N, s, wgrad_sc]() -> int {
-      BLayer& L = n->layers[li];
-      const BAct& in = inw;
-      GatherGeom g[8];
-      int Kw, Nw;
-      URSN_REQUIRE(layer_geoms(n, L, PASS_WGRAD, N, in.cs, L.kout, g) == 1, "bf16 backward: bad weight-gradient geometry");
-      real_extents(L, PASS_WGRAD, Kw, Nw);
-      hipStream_t ws = s;
-      if (n->s2 && n->s2_on) {
-        hipEvent_t e = next_event(n);
-        URSN_REQUIRE(e, "bf16 backward: no event for the weight-gradient stream");
-        URSN_HIP(hipEventRecord(e, s));
-        URSN_HIP(hipStreamWaitEvent(n->s2, e, 0));
-        ws = n->s2;
-      }
-      BProf pw(n, ws, li, 2, blayer_flops(n, L, N), blayer_bytes(n, L, N));
-      if (in.in_f32 && !L.kind && b0wgrad_ok(g[0])) {
-        URSN_TRY(launch_b0wgrad(g[0], in.in_f32, L.dz, n->grads + L.w_off, Nw, n->wg_scratch, n->wg_bytes, ws));
-      } else if (in.in_f32) {
-        URSN_REQUIRE(!L.kind && b3wgrad_scalar_ok(g[0]), "bf16 backward: %s cannot read a scalar fp32 input", L.name.c_str());
-        URSN_TRY(launch_b3wgrad(g[0], nullptr, L.dz, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, ws, nullptr, in.in_f32));
-      } else if (in.aff_layer >= 0) {
-        const BLayer& P = n->layers[in.aff_layer];
-        URSN_REQUIRE(!L.kind && layer_geoms(n, L, PASS_WGRAD, N, P.kout, L.kout, g) == 1 && b3wgrad_ok(g[0]), "bf16 backward: %s cannot normalise its input on load", L.name.c_str());
-        B3Affine af = {P.mean, P.rstd, beta_of(n, P), in.aff_relu};
-        URSN_TRY(launch_b3wgrad(g[0], P.z, L.dz, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, ws, &af));
-      } else if (wgrad_sc >= 0) {
-        const BLayer& SL = n->layers[wgrad_sc];
-        URSN_REQUIRE(!L.kind && bs2k8w_sc_ok(g[0]), "bf16 backward: %s cannot take its shortcut's weight gradient along", L.name.c_str());
-        URSN_TRY(launch_bs2k8w(g[0], in.p, L.dz, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, SL.dz, SL.kout, n->grads + SL.w_off, ws));
-      } else {
-        const bf16_t* S = L.kind ? L.dz : in.p;
-        const bf16_t* Cq = L.kind ? in.p : L.dz;
-        URSN_TRY(launch_bwgrad(g[0], S, Cq, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, ws));
-      }
-      return 0;
-    };
-    // The level-0 weight gradients are HBM-heavy (2-3 GB each) and so is everything the main stream does at level 0: launched
-    // at once they run BESIDE it and both slow down (32.4 ms of main-stream kernels + 9.9 ms of weight gradients take 39.6 ms).
-    // Opt-in experiment (URSN_BF16_DEFER_WGRAD=L): queue them while the decoder is at level 0 and release them when the main stream
-    // reaches decoder level L (small latency-bound kernels that leave the HBM idle).  Measured at cfg5: L = 1 / 2 / 3 / 4: 98.0 /
-    // 98.5 / 98.7 / 98.5 images/s against 101.1 launched at once -- the deep levels are too short (5 ms) to absorb 4.8 ms of level-0
-    // weight gradients, which then land beside the encoder's level-1 / level-0 passes instead.  Off.
-    if (n->defer_open && n->s2 && n->s2_on && L.lout == 0) n->deferred.push_back(wgrad);
-    else URSN_TRY(wgrad());
+    // (launched at once, level 0 too: held back until the main stream reached a deep decoder level they measured 98.0-98.7
+    // against 101.1 images/s at cfg5 -- the deep levels are too short to absorb them)
+    URSN_REQUIRE(layer_geoms(n, L, PASS_WGRAD, N, in.cs, L.kout, g) == 1, "bf16 backward: bad weight-gradient geometry");
+    real_extents(L, PASS_WGRAD, Kw, Nw);
+    hipStream_t ws = s;
+    if (n->s2 && n->s2_on) {
+      hipEvent_t e = next_event(n);
+      URSN_REQUIRE(e, "bf16 backward: no event for the weight-gradient stream");
+      URSN_HIP(hipEventRecord(e, s));
+      URSN_HIP(hipStreamWaitEvent(n->s2, e, 0));
+      ws = n->s2;
+    }
+    BProf pw(n, ws, li, 2, blayer_flops(n, L, N), blayer_bytes(n, L, N));
+    if (in.in_f32 && !L.kind && b0wgrad_ok(g[0])) {
+      URSN_TRY(launch_b0wgrad(g[0], in.in_f32, L.dz, n->grads + L.w_off, Nw, n->wg_scratch, n->wg_bytes, ws));
+    } else if (in.in_f32) {
+      URSN_REQUIRE(!L.kind && b3wgrad_scalar_ok(g[0]), "bf16 backward: %s cannot read a scalar fp32 input", L.name.c_str());
+      URSN_TRY(launch_b3wgrad(g[0], nullptr, L.dz, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, ws, nullptr, in.in_f32));
+    } else if (in.aff_layer >= 0) {
+      const BLayer& P = n->layers[in.aff_layer];
+      URSN_REQUIRE(!L.kind && layer_geoms(n, L, PASS_WGRAD, N, P.kout, L.kout, g) == 1 && b3wgrad_ok(g[0]), "bf16 backward: %s cannot normalise its input on load", L.name.c_str());
+      B3Affine af = {P.mean, P.rstd, beta_of(n, P), in.aff_relu};
+      URSN_TRY(launch_b3wgrad(g[0], P.z, L.dz, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, ws, &af));
+    } else if (wgrad_sc >= 0) {
+      const BLayer& SL = n->layers[wgrad_sc];
+      URSN_REQUIRE(!L.kind && bs2k8w_sc_ok(g[0]), "bf16 backward: %s cannot take its shortcut's weight gradient along", L.name.c_str());
+      URSN_TRY(launch_bs2k8w(g[0], in.p, L.dz, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, SL.dz, SL.kout, n->grads + SL.w_off, ws));
+    } else {
+      const bf16_t* S = L.kind ? L.dz : in.p;
+      const bf16_t* Cq = L.kind ? in.p : L.dz;
+      URSN_TRY(launch_bwgrad(g[0], S, Cq, n->grads + L.w_off, Kw, Nw, n->wg_scratch, n->wg_bytes, ws));
+    }
   }
   if (!need_dgrad) return 0;
   BProf pd(n, s, li, 1, blayer_flops(n, L, N), blayer_bytes(n, L, N));
@@ -845,7 +817,7 @@ int unit_bwd(ursn_bnet* n, BUnit& u, int N, hipStream_t s, const BBsTarget* in_t
     // input-stationary kernel and nothing has been written to d(in) yet, that kernel adds the second term itself (it reads g(out)
     // and the mask bytes instead of old values) and the join's BatchNorm backward writes one tensor less
     // (URSN_BF16_RESIDUAL_IN_DGRAD=0: written here, accumulated there)
-    static const bool fuse_res = !(getenv("URSN_BF16_RESIDUAL_IN_DGRAD") && getenv("URSN_BF16_RESIDUAL_IN_DGRAD")[0] == '0');
+    static const bool fuse_res = ursn_env_on("URSN_BF16_RESIDUAL_IN_DGRAD");
     GatherGeom gg[8];
     const BLayer& C1 = n->layers[u.c1];
     const int gc = layer_geoms(n, C1, PASS_DGRAD, N, u.in.cs, C1.kout, gg);
@@ -891,23 +863,11 @@ int unit_bwd(ursn_bnet* n, BUnit& u, int N, hipStream_t s, const BBsTarget* in_t
   return 0;
 }
 
-int flush_deferred(ursn_bnet* n) {
-  n->defer_open = false;
-  for (auto& f : n->deferred) URSN_TRY(f());
-  n->deferred.clear();
-  return 0;
-}
-
 int backward(ursn_bnet* n, int N, hipStream_t s) {
   const int ns = n->cfg.num_strides;
   for (size_t i = 0; i < n->ginit.size(); ++i) n->ginit[i] = 0;
   n->ev_used = 0;
   n->split0_done = false;
-  // URSN_BF16_DEFER_WGRAD=L: the level-0 weight gradients of the decoder are released when the main stream starts decoder level L
-  // (default 0: launched at once -- measured faster, see conv_bwd)
-  static const int defer_level = getenv("URSN_BF16_DEFER_WGRAD") ? atoi(getenv("URSN_BF16_DEFER_WGRAD")) : 0;
-  n->deferred.clear();
-  n->defer_open = defer_level > 0 && n->s2 && n->s2_on;
   URSN_TRY(bn_back(n, n->conv2, n->dlog, 8, nullptr, 0, 0, -1, nullptr, 0, 0, N, s));
   BBsTarget tc;
   tc.li = n->conv1; tc.mode = 2;
@@ -922,7 +882,6 @@ int backward(ursn_bnet* n, int N, hipStream_t s) {
   tc = join_of(n->units[ui - 1]);
   URSN_TRY(conv_bwd(n, n->conv1, n->a_pre1, true, N, s, -1, &tc));
   for (int i = ns - 1; i >= 0; --i) {
-    if (ns - 1 - i == defer_level) URSN_TRY(flush_deferred(n));
     tc = join_of(n->units[ui - 2]);
     URSN_TRY(unit_bwd(n, n->units[--ui], N, s, &tc));
     URSN_TRY(unit_bwd(n, n->units[--ui], N, s));
@@ -931,7 +890,6 @@ int backward(ursn_bnet* n, int N, hipStream_t s) {
     else URSN_TRY(bn_back(n, n->deconv[i], dout.g, dout.cs, nullptr, 0, 1, -1, nullptr, 0, 0, N, s));
     URSN_TRY(conv_bwd(n, n->deconv[i], n->deconv_in[i], true, N, s));
   }
-  URSN_TRY(flush_deferred(n));   // (a shallow network never reached the level)
   for (int step = ns - 1; step >= 0; --step) {
     tc = join_of(n->units[ui - 2]);
     URSN_TRY(unit_bwd(n, n->units[--ui], N, s, &tc));
@@ -999,8 +957,7 @@ int bnet_create(const ursn_config* cfg, float* params, float* grads, void* works
   n->params = params; n->grads = grads;
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  const char* e2 = getenv("URSN_WGRAD_STREAM");
-  if (e2 && e2[0] == '0') { *out = n; return 0; }   // weight gradients on the caller's stream (per-kernel profiling)
+  if (!ursn_env_on("URSN_WGRAD_STREAM")) { *out = n; return 0; }   // weight gradients on the caller's stream (per-kernel profiling)
   if (hipStreamCreateWithPriority(&n->s2, hipStreamNonBlocking, lo) != hipSuccess ||
       hipEventCreateWithFlags(&n->s2_done, hipEventDisableTiming) != hipSuccess) {
     ursn_set_error("create: could not create the weight-gradient stream");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 
 #include "../../include/uresnet_hip.h"
 
@@ -78,6 +79,33 @@ void ursn_roctx_pop();
   } while (0)
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- A/B switches ("A/B switches") -----------------------------------------------------------------------
+// The only readers of the environment in csrc/.  They do not cache: a call site that wants its value once per process
+// holds it in a `static const`; the net plans read theirs at every create.
+static inline const char* ursn_env_str(const char* name) { return getenv(name); }
+static inline bool ursn_env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }    // default on
+static inline bool ursn_env_set(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }      // opt-in
+static inline int ursn_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline int64_t ursn_env_i64(const char* name, int64_t dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+// switches that more than one file reads (conv_tiled.hip, conv_igemm.hip, bf16_s2k8.hip): once per process
+bool ursn_tiled_disabled();   // URSN_DISABLE_TILED=1: route everything through the generic kernels
+bool ursn_igemm_on();         // URSN_IGEMM=0: no implicit-GEMM kernels (forward, data and weight gradient)
+bool ursn_bs2k8_on();         // URSN_BS2K8=0: no bf16 8 -> 16 stride-2 kernels (forward and weight gradient)
+
+// Workspace carving of the two net plans (net.hip, net_bf16.hip): 256-byte aligned pieces of one caller-owned allocation; with
+// base == nullptr it only counts (the size query).
+struct Arena {
+  char* base = nullptr;
+  size_t off = 0;
+  void* take(size_t bytes) {
+    off = (off + 255) & ~(size_t)255;
+    void* p = base ? (void*)(base + off) : nullptr;
+    off += bytes;
+    return p;
+  }
+  float* floats(int64_t n) { return (float*)take((size_t)n * sizeof(float)); }
+};
 
 // ---------------------------------------------------------------------------------------
 // Gather-convolution geometry.  Every conv-like op of the path (conv s1/s2, 1x1, transposed

@@ -159,7 +159,7 @@ struct DWPlan {
 };
 
 bool dw_plan(const ursn_conv_desc& d, DWPlan& p) {
-  static const bool off = getenv("URSN_DWGRAD") && getenv("URSN_DWGRAD")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_DWGRAD");
   if (off || d.dtype != 0 || (d.ndim != 2 && d.ndim != 3) || d.transposed || d.k != 3 || d.stride != 1 || d.in_split || d.in_mean) return false;
   if (d.cin < 64 || d.cout < 64 || (d.cin & 3) || (d.cout & 3)) return false;
   const int ics = d.in_cstride > 0 ? d.in_cstride : d.cin, ocs = d.out_cstride > 0 ? d.out_cstride : d.cout;
@@ -171,7 +171,7 @@ bool dw_plan(const ursn_conv_desc& d, DWPlan& p) {
   // work per 16 MFMAs and the L2 round trips of 8 quads in flight -- the box kernels climb from 16-26 at the last level to 100+):
   // 6^3 x 4 x 256 channels 0.117 -> 0.054 ms, 2-D 8^2 x 4 x 512 0.075 -> 0.030; 12^3 0.084 -> 0.103, 2-D 16^2 0.031 -> 0.040: only
   // the last level takes it
-  static const int64_t maxv = getenv("URSN_DWGRAD_MAXVOX") ? atoll(getenv("URSN_DWGRAD_MAXVOX")) : 1024;
+  static const int64_t maxv = ursn_env_i64("URSN_DWGRAD_MAXVOX", 1024);
   if (V * (d.ndim == 3 ? 1 : 4) > maxv || p.X < 2) return false;
   if ((int64_t)p.Z * p.Y * p.X * (ics > ocs ? ics : ocs) * 4 >= ((int64_t)1 << 31)) return false;
   p.ncib = (d.cin + 63) / 64;

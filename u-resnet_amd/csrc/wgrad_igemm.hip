@@ -246,15 +246,7 @@ struct IGWPlan {
 };
 
 static bool make_igwplan(const ursn_conv_desc& d, IGWPlan& p) {
-  {
-    static int off = -1;
-    if (off < 0) {
-      const char* e = getenv("URSN_DISABLE_TILED");
-      const char* f = getenv("URSN_IGEMM");
-      off = ((e && e[0] == '1') || (f && f[0] == '0')) ? 1 : 0;
-    }
-    if (off && d.algo != 4) return false;
-  }
+  if ((ursn_tiled_disabled() || !ursn_igemm_on()) && d.algo != 4) return false;
   if (d.transposed || d.k != 3 || d.stride != 1 || d.in_split || d.in_mean) return false;
   if ((d.cin % 16) || (d.cout % 16)) return false;
   if (d.cin <= 16 && d.cout <= 16 && d.algo != 4) return false;
@@ -265,7 +257,7 @@ static bool make_igwplan(const ursn_conv_desc& d, IGWPlan& p) {
   else { p.Z = 1; p.Y = d.in_sp[0]; p.X = d.in_sp[1]; }
   // buffer-path staging (buffer_stage.h): 32-bit byte offsets inside one image, below the out-of-range marker
   if ((int64_t)p.Z * p.Y * p.X * (ics > ocs ? ics : ocs) * 4 >= (int64_t)0x80000000ll) return false;
-  static const int min_x = getenv("URSN_IGEMM_MINX") ? atoi(getenv("URSN_IGEMM_MINX")) : 12;
+  static const int min_x = ursn_env_int("URSN_IGEMM_MINX", 12);
   if (p.X < min_x && d.algo != 4) return false;
   p.var = (p.mode == 3 && (p.X % 16) != 0 && (p.X % 16) <= 12 && (p.X % 12) == 0) ? 1 : 0;
   const int BZ = p.mode == 3 ? 4 : 1, BY = p.mode == 3 ? 4 : 16, BX = p.var ? 12 : 16;

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(VW_NTHR, 2) void vwgrad_kernel(VWArgs a) {
 
 struct VWPlan { int Z, Y, X, ntx, nty, zseg, nzseg, grid; };
 bool vw_plan(const ursn_conv_desc& d, VWPlan& p) {
-  static const bool off = getenv("URSN_WGRAD_VALU") && getenv("URSN_WGRAD_VALU")[0] == '0';
+  static const bool off = !ursn_env_on("URSN_WGRAD_VALU");
   if (off || d.ndim != 3 || d.transposed || d.k != 3 || d.stride != 1 || d.cin != 8 || d.cout != 3) return false;
   if (d.in_mean || d.in_split || (d.algo != 0 && d.algo != 3)) return false;
   const int ics = d.in_cstride > 0 ? d.in_cstride : d.cin, ocs = d.out_cstride > 0 ? d.out_cstride : d.cout;
