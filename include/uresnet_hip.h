@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define URSN_ABI_VERSION 8
+#define URSN_ABI_VERSION 9
 
 typedef struct ursn_net ursn_net; /* opaque */
 
@@ -153,7 +153,8 @@ int ursn_tensor(const ursn_net* net, const char* name, float** ptr, int64_t* vox
 
 /* Per-launch timing with HIP events recorded on the launch stream (bench.py roofline leg; the
  * reference has no counterpart: lib/ssnet_trainval.py:48-49 only reports peak bytes).
- * pass: 0 conv fwd, 1 conv dgrad, 2 conv wgrad, 3 bn stats, 4 bn apply, 5 bn backward, 6 head. */
+ * pass: 0 conv fwd, 1 conv dgrad, 2 conv wgrad, 3 bn stats, 4 bn apply, 5 bn backward, 6 head (the dense head records
+ * kernel "head" / "bhead", the gather head of ursn_infer_voxels "vscores"). */
 typedef struct ursn_prof_rec {
   char kernel[48];
   char layer[96];
@@ -352,6 +353,40 @@ int ursn_voxels_to_dense(const ursn_voxel_batch* b, float* data, float* label, f
 int ursn_labels_to_voxels(const float* labels, int32_t n, int64_t voxels, int32_t* index_out, uint8_t* class_out,
                           int64_t cap, int64_t* offsets_out, void* scratch, size_t scratch_bytes, void* stream);
 size_t ursn_labels_to_voxels_scratch_bytes(int32_t n, int64_t voxels);
+
+/* ---- voxel-list scores (ABI 9; voxel_io.hip) -----------------------------------------------------------------------
+ * The output side of the voxel-list boundary: the reference's consumers read the softmax at an event's own voxels
+ * (example_scripts/ana_csv.py per-class score means, the score renormalisation at lib/ssnet_trainval.py:280-283), so the class
+ * scores, the argmax class and the ana label are gathered AT THE LISTED VOXELS from the stored raw logits of conv2 and the dense
+ * [N, *spatial, num_class] softmax is never written.  For list entry m of event i, p = i * voxels + index[m]:
+ *     logit[k] = fma(z[p][k], rstd[k], beta[k] - mean[k] * rstd[k]),  e[k] = exp(logit[k] - max),  score[k] = e[k] * (1 / sum e)
+ * -- the arithmetic of the dense head of the same plan, in the same order (expf on fp32 logits, elementwise.hip; the fast
+ * __expf on bf16 logits, bf16_elementwise.hip), so the scores carry the BITS of ursn_infer's softmax at those voxels. */
+typedef struct ursn_vscores_desc {
+  int32_t n; int64_t voxels; int32_t ncls;           /* events, prod(spatial) of one event, 1..8 classes              */
+  const void* z; int32_t z_cstride; int32_t dtype;   /* 0 fp32 (stride >= ncls; 4 with <= 4 classes and a 16-byte aligned z: one
+                                                      * 16-byte load), 1 bf16 bit patterns (stride 8, 16-byte aligned)    */
+  const float *mean, *rstd, *beta;                   /* NULL mean: z already holds logits */
+  const float* data;                                 /* [n, voxels], needed iff ana_out */
+  const int64_t* offsets; const int32_t* index;      /* as in ursn_voxel_batch */
+} ursn_vscores_desc;
+
+/* scores_out [M, ncls] fp32, pred_out [M] uint8 (argmax, lowest index on ties), ana_out [M] uint8
+ * (((p1 > p2) * 1 + (p2 >= p1) * 2) * (data[p] > 1.0), lib/ssnet_trainval.py:285-287; needs ncls >= 3); M = offsets[n].  Each
+ * output may be NULL, not all three.  An entry whose index lies outside [0, voxels) reads nothing and gets zeros in every
+ * requested row; events without entries are legal.  One launch of one thread per entry (the list length lives on the device,
+ * so the grid is sized from `voxels` like the scatter pass of ursn_voxels_to_dense); no atomics, no scratch: the result depends
+ * only on the arguments.  Enqueues only; never synchronises. */
+int ursn_scores_at_voxels(const ursn_vscores_desc* d, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, void* stream);
+
+/* Forward pass, then the gather head on conv2's stored z / mean / rstd for the voxel list (offsets [n+1], index [m_total], device
+ * pointers, as in ursn_voxel_batch; rows at or beyond m_total are never written, m_total = 0 launches no gather).  Outputs as in
+ * ursn_scores_at_voxels.  label != NULL and out2 != NULL: the dense head also runs, without a softmax output, for out2 =
+ * {acc_all, acc_nonzero} exactly as ursn_infer_labels gives them; label == NULL: the dense head is not launched at all.
+ * Needs cin == 1 (ana_out: >= 3 classes).  Both plans.  Always synchronises, like ursn_infer. */
+int ursn_infer_voxels(ursn_net* net, const float* data, const float* label, int32_t n, const int64_t* offsets,
+                      const int32_t* index, int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out,
+                      float* out2, void* stream);
 
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);

@@ -7,12 +7,18 @@
     (d) compact      ursn_labels_to_voxels alone on the label volume of one inference
     (e) bytes        H2D / D2H bytes per step (training feed) and per ana batch for each form
 
+    (f) ana_scores   with --ana-scores, INSTEAD of (a)-(e): per-batch wall time and D2H bytes of inference_voxel_scores (class
+                     scores, argmax class and ana label at the event's own voxels) against what the dense path must do for the
+                     same information -- inference() with the dense softmax copied back plus a host gather -- on the same events in
+                     the same session, alternating; plus the size of the vscores launch from ursn_profile_read
+
 (a) and (b) are host clocks around `--steps` steps that end in a device synchronise, taken `--repeats` times in alternation
 (a b a b ...) after a warm-up of both; (c) and (d) are HIP events around `--calls` back-to-back calls, `--repeats` times.
 Every figure is reported as median with (min .. max).  `--lib PATH` times (c) a second time through another build of the
 library (e.g. one compiled with -DURSN_VOXEL_FILL_NT=1), alternating with the default one.  Prints one JSON line.
 
     python tools/voxel_feed_bench.py [--steps 20] [--repeats 5] [--calls 50] [--lib other/liburesnet_hip.so]
+    python tools/voxel_feed_bench.py --ana-scores [--steps 5] [--repeats 5]
 """
 import argparse
 import ctypes
@@ -34,6 +40,81 @@ def stat(xs, digits=3):
     return {"median": round(float(np.median(xs)), digits), "min": round(xs[0], digits), "max": round(xs[-1], digits)}
 
 
+def ana_scores(args):
+    """Leg (f): the voxel-list output side against the dense softmax + host gather."""
+    import torch
+    import uresnet_amd  # noqa: F401
+    from uresnet_amd import _lib, uresnet
+    from uresnet_amd import synthetic_io as sio
+    from uresnet_amd.ssnet import VoxelBatch
+    assert torch.cuda.is_available(), "voxel_feed_bench.py needs a HIP device"
+    lib = _lib.load()
+    dims, ncls, n = (args.size,) * 3 + (1,), 3, args.batch
+    V = args.size ** 3
+    ev = [sio.lartpc_sparse(dims, ncls, e) for e in range(n)]
+    data, label = (np.stack([e[j] for e in ev]) for j in range(2))
+    vb = VoxelBatch.concat([sio.dense_to_voxels(e[0], e[1]) for e in ev]).validate()
+    off, M = vb.offsets, int(vb.offsets[-1])
+    pin = [torch.from_numpy(a).pin_memory().numpy() for a in (data, label)]
+    net = uresnet(dims=list(dims), num_class=ncls, base_num_outputs=8)
+    net.construct(trainable=False, use_weight=False, seed=1234)
+
+    def dense():        # the softmax crosses PCIe whole; scores / class / ana label of the listed voxels on the host
+        sm, acc_all, acc_nz = net.inference(None, pin[0], pin[1])
+        out = []
+        for i in range(n):
+            idx = vb.index[off[i]:off[i + 1]]
+            sc = sm[i].reshape(V, ncls)[idx]
+            ana = ((sc[:, 1] > sc[:, 2]) * 1 + (sc[:, 2] >= sc[:, 1]) * 2) * (vb.value[off[i]:off[i + 1]] > 1.0)
+            out.append((sc, sc.argmax(axis=1).astype(np.uint8), ana.astype(np.uint8)))
+        return out
+
+    def voxel():
+        return net.inference_voxel_scores(None, vb)
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            call()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
+
+    want, got = dense(), voxel()        # warm-up of both, and the two forms agree bit for bit
+    for i in range(n):
+        assert np.array_equal(want[i][0].view(np.uint32), got['scores'][i].view(np.uint32))
+        assert np.array_equal(want[i][1], got['pred'][i]) and np.array_equal(want[i][2], got['ana'][i])
+    h0 = net.feed_stats['h2d_bytes']
+    dense()
+    h1 = net.feed_stats['h2d_bytes']
+    voxel()
+    h2 = net.feed_stats['h2d_bytes']
+    ms = {"dense": [], "voxel": []}
+    for _ in range(args.repeats):
+        ms["dense"].append(timed(dense))
+        ms["voxel"].append(timed(voxel))
+
+    _lib.check(lib.ursn_profile_enable(net._handle, 1))
+    kern = {}
+    for name, call in (("voxel", voxel), ("dense", dense)):
+        call()
+        cnt = ctypes.c_int64(0)
+        _lib.check(lib.ursn_profile_read(net._handle, None, 0, ctypes.byref(cnt)))
+        recs = (_lib.ursn_prof_rec * max(int(cnt.value), 1))()
+        _lib.check(lib.ursn_profile_read(net._handle, recs, int(cnt.value), ctypes.byref(cnt)))
+        rows = [(r.kernel.decode(), r.pass_, r.ms, r.launches) for r in recs[:int(cnt.value)]]
+        kern[name] = {"forward_ms": round(sum(r[2] for r in rows if r[1] != 6), 3),
+                      "pass6": {r[0]: {"ms": round(r[2], 4), "launches": r[3]} for r in rows if r[1] == 6}}
+    _lib.check(lib.ursn_profile_enable(net._handle, 0))
+    print(json.dumps({
+        "shape": "%d^3 F=8 batch %d fp32 inference, lartpc_sparse" % (args.size, n), "steps": args.steps, "repeats": args.repeats,
+        "listed_voxels": M, "occupancy": round(M / float(n * V), 6),
+        "dense_ana_ms": stat(ms["dense"]), "voxel_ana_ms": stat(ms["voxel"]),
+        "bytes": {"d2h_dense": n * V * ncls * 4, "d2h_voxel": M * (4 * ncls + 2), "h2d_dense": h1 - h0, "h2d_voxel": h2 - h1},
+        "kernels": kern,
+    }))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--steps", type=int, default=20)
@@ -42,7 +123,10 @@ def main():
     ap.add_argument("--size", type=int, default=192, help="edge of the cubic volume (192 = cfg3)")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--lib", default=None, help="second build of liburesnet_hip.so for leg (c)")
+    ap.add_argument("--ana-scores", action="store_true", help="leg (f) instead of (a)-(e)")
     args = ap.parse_args()
+    if args.ana_scores:
+        return ana_scores(args)
 
     import torch
     import uresnet_amd  # noqa: F401

@@ -60,6 +60,12 @@ class ursn_voxel_batch(C.Structure):
                 ("value", C.c_void_p), ("label", C.c_void_p), ("weight", C.c_void_p), ("bg_weight", C.c_void_p)]
 
 
+class ursn_vscores_desc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("voxels", C.c_int64), ("ncls", C.c_int32), ("z", C.c_void_p), ("z_cstride", C.c_int32),
+                ("dtype", C.c_int32), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("beta", C.c_void_p), ("data", C.c_void_p),
+                ("offsets", C.c_void_p), ("index", C.c_void_p)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -114,10 +120,12 @@ _SIGS = {
     "ursn_voxels_to_dense": (C.c_int, [C.POINTER(ursn_voxel_batch), _P, _P, _P, _P]),
     "ursn_labels_to_voxels": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ursn_labels_to_voxels_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "ursn_scores_at_voxels": (C.c_int, [C.POINTER(ursn_vscores_desc), _P, _P, _P, _P]),
+    "ursn_infer_voxels": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_float), _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -51,6 +51,10 @@ class ssnet_config(object):
     # the *_voxels methods of ssnet_base) and the ana output holds one (index, class) voxel set per event, the content of the
     # sparse3d product of lib/ssnet_trainval.py:299-302, instead of the dense label volume
     SPARSE_IO = False
+    # only meaningful with SPARSE_IO: True = the ana output side is a voxel list too (ssnet_base.inference_voxel_scores): class
+    # scores, argmax class and ana label come back at the event's own voxels, no dense softmax is written or copied, batch mode
+    # appends a third record per event (the class scores of the voxel set) and the interactive result dict holds per-event lists
+    SPARSE_SCORES = False
 
     def __init__(self):
         pass

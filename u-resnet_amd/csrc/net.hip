@@ -1198,6 +1198,44 @@ extern "C" int ursn_infer_labels(ursn_net* net, const float* data, const float* 
   return 0;
 }
 
+// Forward, then the gather head at the listed voxels on conv2's stored z / mean / rstd (voxel_io.hip).  The dense head runs only
+// for the accuracies (label and out2 given), never with a softmax output.
+extern "C" int ursn_infer_voxels(ursn_net* net, const float* data, const float* label, int32_t n, const int64_t* offsets,
+                                 const int32_t* index, int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out,
+                                 float* out2, void* stream) {
+  URSN_REQUIRE(offsets && index, "infer_voxels: null offsets / index");
+  URSN_REQUIRE(scores_out || pred_out || ana_out, "infer_voxels: all three outputs are null");
+  URSN_REQUIRE(m_total >= 0, "infer_voxels: m_total = %lld < 0", (long long)m_total);
+  URSN_TRY(check_call(net, data, n));
+  URSN_REQUIRE(net->cfg.cin == 1, "infer_voxels: needs one input channel (a voxel list carries one value per voxel)");
+  URSN_REQUIRE(!ana_out || net->cfg.num_class >= 3, "infer_voxels: ana_out needs >= 3 classes");
+  hipStream_t s = (hipStream_t)stream;
+  net->last_n = n;
+  const bool dense_head = label && out2;
+  if (net->bf) {
+    URSN_TRY(bnet_infer_voxels(net->bf, data, dense_head ? label : nullptr, n, offsets, index, m_total, scores_out, pred_out,
+                               ana_out, s));
+  } else {
+    URSN_TRY(forward(net, data, n, s));
+    if (dense_head) URSN_TRY(head(net, data, label, nullptr, n, nullptr, false, s));
+    const Layer& L = net->layers[net->conv2];
+    ursn_vscores_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = n; d.voxels = net->lvox[0]; d.ncls = net->cfg.num_class;
+    d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
+    d.mean = L.mean; d.rstd = L.rstd; d.beta = net->params + L.b_off;
+    d.data = data; d.offsets = offsets; d.index = index;
+    if (m_total > 0) {
+      ProfScope ps(net, s, net->conv2, 6, 0.0, (double)m_total * (4.0 * L.zcs + 4.0 + 4.0 * d.ncls + 6.0));
+      URSN_TRY(launch_vscores(&d, scores_out, pred_out, ana_out, m_total, s));
+      ps.done("vscores");
+    }
+  }
+  if (dense_head) URSN_TRY(read_metrics(net, out2, 2, s));
+  else URSN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 extern "C" int ursn_read_metrics(ursn_net* net, float* out3, void* stream) {
   URSN_REQUIRE(net && out3, "read_metrics: null argument");
   return read_metrics(net, out3, 3, (hipStream_t)stream);

@@ -13,6 +13,10 @@ int bnet_param(const ursn_bnet* n, int64_t index, ursn_param_info* out);
 // mode 0: forward + loss + backward (gradients accumulate); 1: forward + loss; 2: forward + softmax / ana labels
 int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, int mode, float* softmax_out,
               float* labels_out, hipStream_t s);
+// ursn_infer_voxels: forward, the dense head for the accuracies only when label != nullptr, the gather head (voxel_io.hip) on
+// conv2's operands; enqueues only
+int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N, const int64_t* offsets, const int32_t* index,
+                      int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, hipStream_t s);
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride);
 // per-launch HIP-event records (as ursn_profile_enable / ursn_profile_read of the fp32 plan) and the weight-gradient stream switch
 int bnet_profile_enable(ursn_bnet* n, int on);

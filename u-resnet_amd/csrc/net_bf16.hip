@@ -1043,6 +1043,25 @@ int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* 
   return head(n, data, label, nullptr, N, softmax_out, false, s, labels_out);
 }
 
+// bnet_step's inference mode that stops before the dense head's softmax: forward, the dense head only for the accuracies
+// (label != nullptr, no softmax / label volume), then the gather head on conv2's z / mean / rstd and the padded beta
+int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N, const int64_t* offsets, const int32_t* index,
+                      int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, hipStream_t s) {
+  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  URSN_TRY(forward(n, data, N, s));
+  if (label) URSN_TRY(head(n, data, label, nullptr, N, nullptr, false, s));
+  const BLayer& L = n->layers[n->conv2];
+  ursn_vscores_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
+  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
+  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  d.data = data; d.offsets = offsets; d.index = index;
+  if (m_total == 0) return 0;
+  BProf ps(n, s, n->conv2, 6, 0.0, (double)m_total * (16.0 + 4.0 + 4.0 * d.ncls + 6.0), "vscores");
+  return launch_vscores(&d, scores_out, pred_out, ana_out, m_total, s);
+}
+
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride) {
   // <scope>:z / :dz raw conv output and its gradient (bf16), <scope>:mean / :rstd the BatchNorm statistics (fp32, voxels = 0),
   // <scope> / <scope>:grad a materialised activation and the gradient tensor of the same layout (bf16), logits:grad the head's

@@ -307,6 +307,10 @@ int launch_bn_bwd_final(const double* partial, int nblocks, int C, int64_t V, do
                         int Cw, hipStream_t s, float* coef_out = nullptr, const float* mean = nullptr, const float* rstd = nullptr,
                         const float* beta = nullptr);
 int launch_head(const HeadArgs& a, hipStream_t s);
+// Gather head (voxel_io.hip): ursn_scores_at_voxels with the list length when the host knows it (m_total < 0: unknown; rows at or
+// beyond m_total are never written, 0 launches nothing).  Validates like the C entry point.
+int launch_vscores(const ursn_vscores_desc* d, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, int64_t m_total,
+                   hipStream_t s);
 
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2,
                 float eps, hipStream_t s);

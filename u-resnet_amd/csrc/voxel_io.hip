@@ -1,9 +1,10 @@
 // Voxel-list I/O at the boundary of the dense network (gfx950): ursn_voxels_to_dense expands a batch of larcv-style voxel
 // lists into the dense fp32 tensors the kernels read, ursn_labels_to_voxels compacts a dense label volume into the voxel
-// set the reference writes (larcv.as_tensor3d into a sparse3d product, lib/ssnet_trainval.py:299-302).  Both are stateless
+// set the reference writes (larcv.as_tensor3d into a sparse3d product, lib/ssnet_trainval.py:299-302), ursn_scores_at_voxels
+// gathers class scores / argmax / ana label at an event's own voxels from the stored logits.  All are stateless
 // op-level passes: HBM-bound streaming kernels, no atomics, no workgroup waits on another, nothing read that the same call
 // did not write (the scratch buffer needs no initialisation), so the same arguments give the same bits.
-#include "ursn_common.h"
+#include "bf16_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -248,4 +249,139 @@ extern "C" int ursn_labels_to_voxels(const float* labels, int32_t n, int64_t vox
                      (const int64_t*)offsets_out, index_out, class_out, cap);
   URSN_HIP(hipGetLastError());
   return 0;
+}
+
+// ---- ursn_scores_at_voxels -----------------------------------------------------------------------------------------------
+// The gather head: one thread per list entry, blockIdx.y = event (its entries are [offsets[e], offsets[e + 1])), grid-stride
+// inside the event.  The arithmetic RESTATES the dense heads' (head_kernel in elementwise.hip, bhead_kernel in
+// bf16_elementwise.hip) statement by statement -- fmaf(raw, sc, sh) with sh = beta - mean * sc, strict '>' argmax, exp(z - m)
+// summed in class order, e * (1 / sum), the ana rule on the products -- so the scores are the bits the dense softmax holds at
+// the same voxel; tests/test_voxel_scores_gpu.py compares them bit for bit on both plans.  (Restated, not shared through a
+// __device__ helper: the heads are the benchmark's kernels and their generated code stays untouched.)  DT: 0 fp32 logits and
+// expf (fp32 head), 1 bf16 logits and __expf (bf16 head).  V4: <= 4 classes in 4-padded, 16-byte aligned fp32 logits, one
+// 16-byte load.
+struct VScoreArgs {
+  ursn_vscores_desc d;
+  float* scores;
+  uint8_t* pred;
+  uint8_t* ana;
+  int64_t cap;   // rows at or beyond cap are never written (the caller's buffers hold cap rows)
+};
+
+template <int DT, bool V4>
+__global__ __launch_bounds__(256) void vscores_kernel(VScoreArgs a) {
+  const ursn_vscores_desc& d = a.d;
+  const int e = blockIdx.y;
+  int64_t lo = d.offsets[e], hi = d.offsets[e + 1];
+  if (lo < 0) lo = 0;
+  if (hi > a.cap) hi = a.cap;
+  const int ncls = d.ncls;
+  float sc[8], sh[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    sc[k] = 1.f;
+    sh[k] = 0.f;
+    if (k < ncls && d.mean) {
+      sc[k] = d.rstd[k];
+      sh[k] = d.beta[k] - d.mean[k] * sc[k];
+    }
+  }
+  const int64_t base = (int64_t)e * d.voxels;
+  for (int64_t j = lo + (int64_t)blockIdx.x * 256 + threadIdx.x; j < hi; j += (int64_t)gridDim.x * 256) {
+    const int32_t i = d.index[j];
+    float pr[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) pr[k] = 0.f;
+    int arg = 0, lab = 0;
+    if ((uint32_t)i < (uint32_t)d.voxels) {   // an index outside [0, voxels) reads nothing: its rows are zeros
+      const int64_t p = base + i;
+      float raw[8];
+      if constexpr (DT == 1) {
+        unpack8(*(const u32x4*)((const bf16_t*)d.z + p * 8), raw);
+      } else if constexpr (V4) {
+        const f32x4 zv = *(const f32x4*)((const float*)d.z + p * 4);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) raw[k] = k < 4 ? zv[k & 3] : 0.f;
+      } else {
+        const float* zp = (const float*)d.z + p * d.z_cstride;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) raw[k] = k < ncls ? zp[k] : 0.f;
+      }
+      float z[8], ex[8];
+      float m = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (k < ncls) {
+          z[k] = fmaf(raw[k], sc[k], sh[k]);
+          if (z[k] > m) { m = z[k]; arg = k; }   // strict '>' keeps the lowest index on ties
+        }
+      float ssum = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (k < ncls) {
+          if constexpr (DT == 1) ex[k] = __expf(z[k] - m);
+          else ex[k] = expf(z[k] - m);
+          ssum += ex[k];
+        }
+      const float inv = 1.0f / ssum;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (k < ncls) pr[k] = ex[k] * inv;
+      if (a.ana) {   // (shower > track) * 1 + (track >= shower) * 2, masked by data > 1.0 (lib/ssnet_trainval.py:285-287)
+        const float shower = ex[1] * inv, track = ex[2] * inv;
+        const int rule = (shower > track ? 1 : 0) + (track >= shower ? 2 : 0);
+        lab = d.data[p] > 1.0f ? rule : 0;
+      }
+    }
+    if (a.scores) {
+      float* o = a.scores + j * ncls;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (k < ncls) o[k] = pr[k];
+    }
+    if (a.pred) a.pred[j] = (uint8_t)arg;
+    if (a.ana) a.ana[j] = (uint8_t)lab;
+  }
+}
+
+// m_total < 0: the list length is not known on the host (op level): grid sized from `voxels`, every row an entry names may be
+// written.  m_total >= 0 (net level): no event holds more than m_total entries, rows >= m_total are never written, 0 launches nothing.
+int launch_vscores(const ursn_vscores_desc* d, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, int64_t m_total,
+                   hipStream_t s) {
+  URSN_REQUIRE(d && d->offsets && d->index && d->z, "scores_at_voxels: null desc / offsets / index / z");
+  URSN_REQUIRE(scores_out || pred_out || ana_out, "scores_at_voxels: all three outputs are null");
+  URSN_TRY(check_dims("scores_at_voxels", d->n, d->voxels));
+  URSN_REQUIRE(d->ncls >= 1 && d->ncls <= 8, "scores_at_voxels: num_class %d not in [1,8]", (int)d->ncls);
+  URSN_REQUIRE(!ana_out || d->ncls >= 3, "scores_at_voxels: ana_out needs >= 3 classes (num_class = %d)", (int)d->ncls);
+  URSN_REQUIRE(!ana_out || d->data, "scores_at_voxels: ana_out needs data (the data > 1.0 mask)");
+  URSN_REQUIRE(d->dtype == 0 || d->dtype == 1, "scores_at_voxels: dtype %d not in {0 fp32, 1 bf16}", (int)d->dtype);
+  if (d->dtype == 1) {
+    URSN_REQUIRE(d->z_cstride == 8, "scores_at_voxels: bf16 logits need channel stride 8 (z_cstride = %d)", (int)d->z_cstride);
+    URSN_REQUIRE(((uintptr_t)d->z & 15) == 0, "scores_at_voxels: bf16 logits must be 16-byte aligned");
+  } else {
+    URSN_REQUIRE(d->z_cstride >= d->ncls, "scores_at_voxels: z_cstride %d < num_class %d", (int)d->z_cstride, (int)d->ncls);
+    URSN_REQUIRE(((uintptr_t)d->z & 3) == 0, "scores_at_voxels: fp32 logits must be 4-byte aligned");
+  }
+  URSN_REQUIRE(!d->mean || (d->rstd && d->beta), "scores_at_voxels: mean without rstd / beta");
+  URSN_REQUIRE(((uintptr_t)scores_out & 3) == 0 && ((uintptr_t)d->offsets & 7) == 0 && ((uintptr_t)d->index & 3) == 0,
+               "scores_at_voxels: scores_out / index must be 4-byte, offsets 8-byte aligned");
+  if (m_total == 0) return 0;
+  VScoreArgs a;
+  a.d = *d;
+  a.scores = scores_out, a.pred = pred_out, a.ana = ana_out;
+  a.cap = m_total < 0 ? INT64_MAX : m_total;
+  int64_t gx = m_total < 0 ? cdiv64(d->voxels, 256 * 8) : cdiv64(m_total, 256);
+  gx = gx < 1 ? 1 : gx > 1024 ? 1024 : gx;
+  const dim3 grid((unsigned)gx, (unsigned)d->n);
+  ursn_note_kernel("vscores");
+  if (d->dtype == 1) hipLaunchKernelGGL((vscores_kernel<1, false>), grid, dim3(256), 0, s, a);
+  else if (d->z_cstride == 4 && d->ncls <= 4 && ((uintptr_t)d->z & 15) == 0) hipLaunchKernelGGL((vscores_kernel<0, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((vscores_kernel<0, false>), grid, dim3(256), 0, s, a);
+  URSN_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ursn_scores_at_voxels(const ursn_vscores_desc* d, float* scores_out, uint8_t* pred_out, uint8_t* ana_out,
+                                     void* stream) {
+  return launch_vscores(d, scores_out, pred_out, ana_out, -1, (hipStream_t)stream);
 }

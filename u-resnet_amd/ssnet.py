@@ -527,6 +527,8 @@ class ssnet_base(object):
         done = torch.cuda.Event()
         done.record(cur)
         slot.consumed[i] = done                    # the list buffer is free once the expansion has read it
+        # inference_voxel_scores reads offsets / index again after the forward pass and moves `consumed` behind its own launch
+        self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
         return fd
 
     def accum_gradients_voxels(self, sess, voxels, fetch=True):
@@ -593,6 +595,48 @@ class ssnet_base(object):
         res = [[(idx[off[i]:off[i + 1]].copy(), cl[off[i]:off[i + 1]].copy()) for i in range(n)]]
         if with_labels:
             res += [float(acc[0]), float(acc[1])]
+        return res
+
+    def inference_voxel_scores(self, sess, voxels, with_labels=True, want=('scores', 'pred', 'ana')):
+        """The output side of the voxel-list boundary: class scores, argmax class and ana label (lib/ssnet_trainval.py:285-287) AT
+        THE VOXELS THE EVENT CAME IN AS, gathered on the device from conv2's stored logits by one ``ursn_infer_voxels`` call.  No
+        dense softmax is written and nothing dense crosses PCIe in either direction: only the [M]-sized arrays (and the two
+        accuracies) come back.  Returns a dict of per-event lists, split at ``offsets``: ``index`` int32 [m_i], ``scores`` float32
+        [m_i, num_class] (the bits ``inference`` holds at those voxels), ``pred`` uint8 [m_i], ``ana`` uint8 [m_i] -- those named in
+        ``want`` -- plus ``acc_all`` / ``acc_nonzero`` with ``with_labels`` (the dense head then runs without a softmax output;
+        without labels it is not launched at all)."""
+        import torch
+        self._require_single_channel('inference_voxel_scores')
+        want = tuple(want)
+        if not want or any(w not in ('scores', 'pred', 'ana') for w in want):
+            raise ValueError("inference_voxel_scores: want = %r, expected a non-empty subset of ('scores', 'pred', 'ana')" % (want,))
+        if 'ana' in want and self._num_class < 3:
+            raise ValueError('inference_voxel_scores: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
+        fd = self._feed_voxels(voxels, with_label=with_labels, with_weight=False)
+        n = int(fd['input_data'].shape[0])
+        self._ensure_handle(n)
+        slot, turn, d_offsets, d_index = self._fed_list
+        off = voxels.offsets
+        M = int(off[-1])
+        kinds = {'scores': ((max(M, 1), self._num_class), torch.float32), 'pred': ((max(M, 1),), torch.uint8),
+                 'ana': ((max(M, 1),), torch.uint8)}
+        dev = {w: torch.empty(kinds[w][0], dtype=kinds[w][1], device=self._device) for w in want}
+        acc = (ctypes.c_float * 2)()
+        _lib.check(_lib.load().ursn_infer_voxels(self._handle, self._ptr(fd['input_data']), self._ptr(fd.get('input_label')), n,
+                                                 ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_index), M, self._ptr(dev.get('scores')),
+                                                 self._ptr(dev.get('pred')), self._ptr(dev.get('ana')),
+                                                 acc if with_labels else None, self._stream(sess)))
+        self._last_feed = fd
+        self._mark_consumed(fd)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self._device))
+        slot.consumed[turn] = done                 # the gather head has read offsets / index: the list buffer is free again
+        res = {'index': [voxels.index[off[i]:off[i + 1]].copy() for i in range(n)]}
+        for w in want:
+            host = dev[w][:M].cpu().numpy()
+            res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
+        if with_labels:
+            res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
 
     # ------------------------------------------------------------------------------------------

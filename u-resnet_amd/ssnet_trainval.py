@@ -316,6 +316,8 @@ class ssnet_trainval(object):
         io = self._input_main
         vb = io.fetch_voxels()
         entries = io.fetch_entries()
+        if self._cfg.SPARSE_SCORES:
+            return self._ana_step_voxel_scores(vb, entries, batch_mode)
         softmax = data = label = None
         if batch_mode and self._output:
             sets, acc_all, acc_nonzero = self._net.inference_voxels(self._sess, vb, with_labels=True)
@@ -339,6 +341,33 @@ class ssnet_trainval(object):
             img_shape[-1] = -1
             result = {'entries': np.array(entries), 'input': data.reshape(img_shape), 'label': label.reshape(img_shape),
                       'softmax': softmax, 'acc_all': acc_all, 'acc_nonzero': acc_nonzero}
+        self._advance_main()
+        return result
+
+    def _ana_step_voxel_scores(self, vb, entries, batch_mode):
+        """SPARSE_IO + SPARSE_SCORES: the output side is a voxel list too (``inference_voxel_scores``), nothing dense is built on
+        the host or copied in either direction.  Records per event: ``np.save(index)``, ``np.save(class)`` -- byte for byte those of
+        ``_ana_step_voxels`` (the label rule ends in ``* (data > 1.0)``, so the voxel set lies inside the event's list) -- then
+        ``np.save(scores[ana != 0])``, the class scores of the voxels in the set, in set order.  Interactive mode returns
+        ``entries`` / ``acc_all`` / ``acc_nonzero`` and ``voxels``, the per-event list of index / value / label / scores / pred."""
+        want = ('scores',) + (('ana',) if self._output else ()) + (() if batch_mode else ('pred',))
+        r = self._net.inference_voxel_scores(self._sess, vb, with_labels=True, want=want)
+        acc_all, acc_nonzero = r['acc_all'], r['acc_nonzero']
+        if self._output:
+            for i in range(vb.n):
+                keep = r['ana'][i] != 0
+                print('Entry', entries[i], 'Acc', acc_nonzero)
+                np.save(self._output, r['index'][i][keep])
+                np.save(self._output, r['ana'][i][keep])
+                np.save(self._output, r['scores'][i][keep])
+            self._output.flush()
+        result = None
+        if not batch_mode:
+            off = vb.offsets
+            events = [{'index': r['index'][i], 'value': vb.value[off[i]:off[i + 1]].copy(),
+                       'label': vb.label[off[i]:off[i + 1]].copy(), 'scores': r['scores'][i], 'pred': r['pred'][i]}
+                      for i in range(vb.n)]
+            result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
         self._advance_main()
         return result
 
