@@ -388,6 +388,19 @@ int ursn_infer_voxels(ursn_net* net, const float* data, const float* label, int3
                       const int32_t* index, int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out,
                       float* out2, void* stream);
 
+/* ---- per-event weight normalisation (weight_norm.hip) ----------------------------------------------------------------
+ * Appended functions only: no existing declaration or struct layout changes, so URSN_ABI_VERSION stays 9. */
+
+/* Per-event weight normalisation (lib/ssnet_trainval.py:173,204): out[e][v] = weight[e][v] / (float)S_e,
+ * S_e = sum_v weight[e][v] in fp64, fixed order.  out may equal weight (in place).  sums_out [n] optional (device).
+ * Two launches, no atomics, the scratch needs no initialisation; enqueues only, never synchronises.
+ * The division is the IEEE correctly rounded fp32 one and nothing is special-cased: an event whose weights sum to zero gets
+ * what numpy gives it (0/0 = NaN, x/0 = inf).  scratch: 8-byte aligned, >= ursn_normalize_weights_scratch_bytes(n, voxels)
+ * (0 for n outside [1, 65535] or voxels outside [1, 2^31)); out must not overlap weight unless it equals it. */
+int ursn_normalize_weights(const float* weight, float* out, int32_t n, int64_t voxels, float* sums_out,
+                           void* scratch, size_t scratch_bytes, void* stream);
+size_t ursn_normalize_weights_scratch_bytes(int32_t n, int64_t voxels);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

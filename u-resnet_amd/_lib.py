@@ -122,6 +122,8 @@ _SIGS = {
     "ursn_labels_to_voxels_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "ursn_scores_at_voxels": (C.c_int, [C.POINTER(ursn_vscores_desc), _P, _P, _P, _P]),
     "ursn_infer_voxels": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_float), _P]),
+    "ursn_normalize_weights": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "ursn_normalize_weights_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -55,6 +55,10 @@ class ssnet_config(object):
     # scores, argmax class and ana label come back at the event's own voxels, no dense softmax is written or copied, batch mode
     # appends a third record per event (the class scores of the voxel set) and the interactive result dict holds per-event lists
     SPARSE_SCORES = False
+    # not in the reference (lib/ssnet_trainval.py:173,204 normalise the pixel weights per event on the host): True = the driver
+    # hands the raw weights on and the network calls divide them by their per-event sums on the device (ursn_normalize_weights:
+    # fp64 sum, correctly rounded fp32 division); the IO buffer is then not written.  False = the reference's host pass
+    DEVICE_WEIGHT_NORM = False
 
     def __init__(self):
         pass

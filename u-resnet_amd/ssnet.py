@@ -437,6 +437,42 @@ class ssnet_base(object):
                         slot.consumed[i] = ev
 
     # ------------------------------------------------------------------------------------------
+    # per-event weight normalisation on the device (lib/ssnet_trainval.py:173,204 do it on the host)
+    # ------------------------------------------------------------------------------------------
+    def _normalize_fed_weight(self, fd, sess):
+        """``fd['input_weight'] /= its per-event sums`` by ``ursn_normalize_weights`` on the compute stream, which ``_feed`` has
+        already made wait for the copy.  A tensor in one of the net's own feed slots (the voxel expansion's dense weight buffer
+        is one) is normalised in place; anything else is a caller's device tensor that ``_feed`` handed through, and is
+        normalised into one of two private buffers used alternately, never written.  The caller's host array is never written
+        either -- on purpose unlike the reference, which mutates its IO buffer.  ``fd`` then holds the normalised tensor, so
+        whoever re-runs ``last_feed()`` passes ``normalize_weight=False``."""
+        import torch
+        w = fd.get('input_weight') if self._use_weight else None
+        if w is None:
+            return
+        n, V = int(w.shape[0]), int(w.shape[1])
+        lib = _lib.load()
+        need = int(lib.ursn_normalize_weights_scratch_bytes(n, V))
+        scratch = getattr(self, '_wnorm_scratch', None)
+        if scratch is None or scratch.numel() * 8 < need:
+            scratch = self._wnorm_scratch = torch.empty(max(need // 8, 1), dtype=torch.float64, device=self._device)
+        own = any(d is not None and d.data_ptr() == w.data_ptr()
+                  for slot in getattr(self, '_feed_slots', {}).values() for d in slot.dev)
+        out = w
+        if not own:
+            bufs = getattr(self, '_wnorm_out', None)
+            if bufs is None:
+                bufs = self._wnorm_out = [None, None, 0]
+            k = bufs[2]
+            bufs[2] ^= 1
+            if bufs[k] is None or bufs[k].numel() < n * V:
+                bufs[k] = torch.empty(n * V, dtype=torch.float32, device=self._device)
+            out = bufs[k][:n * V].view(n, V)
+        _lib.check(lib.ursn_normalize_weights(self._ptr(w), self._ptr(out), n, V, None, self._ptr(scratch),
+                                              scratch.numel() * 8, self._stream(sess)))
+        fd['input_weight'] = out
+
+    # ------------------------------------------------------------------------------------------
     # voxel-list feed (not in the reference: larcv fills dense arrays; see VoxelBatch)
     # ------------------------------------------------------------------------------------------
     def _require_single_channel(self, what):
@@ -531,12 +567,16 @@ class ssnet_base(object):
         self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
         return fd
 
-    def accum_gradients_voxels(self, sess, voxels, fetch=True):
-        """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure."""
+    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False):
+        """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure.  ``normalize_weight``: the expanded dense
+        weight tensor is normalised per event on the device (``_normalize_fed_weight``), the same definition of the sum as the
+        dense feed's; ``voxels.weight`` / ``bg_weight`` are not written and ``VoxelBatch.normalize_weights`` is not needed."""
         if not self._trainable:
             raise RuntimeError('accum_gradients_voxels: constructed with trainable=False')
         self._require_single_channel('accum_gradients_voxels')
         fd = self._feed_voxels(voxels)
+        if normalize_weight:
+            self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
@@ -550,10 +590,12 @@ class ssnet_base(object):
             return None, doc
         return [None, float(out[0]), float(out[1]), float(out[2])], doc
 
-    def run_test_voxels(self, sess, voxels):
-        """``run_test`` fed a VoxelBatch."""
+    def run_test_voxels(self, sess, voxels, normalize_weight=False):
+        """``run_test`` fed a VoxelBatch (``normalize_weight`` as in ``accum_gradients_voxels``)."""
         self._require_single_channel('run_test_voxels')
         fd = self._feed_voxels(voxels)
+        if normalize_weight:
+            self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
@@ -661,9 +703,9 @@ class ssnet_base(object):
     def _ptr(t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
-    def make_summary(self, sess, input_data, input_label, input_weight=None):
+    def make_summary(self, sess, input_data, input_label, input_weight=None, normalize_weight=False):
         """The reference returns a serialized TensorBoard summary; here the three scalars it holds."""
-        res, _ = self.run_test(sess, input_data, input_label, input_weight)
+        res, _ = self.run_test(sess, input_data, input_label, input_weight, normalize_weight=normalize_weight)
         return {'loss': res[0], 'accuracy_all': res[1], 'accuracy_nonzero': res[2]}
 
     def zero_gradients(self, sess=None):
@@ -673,10 +715,15 @@ class ssnet_base(object):
         _lib.check(_lib.load().ursn_zero_grad(self._handle, self._stream(sess)))
         return [None]
 
-    def accum_gradients(self, sess, input_data, input_label, input_weight=None, fetch=True):
+    def accum_gradients(self, sess, input_data, input_label, input_weight=None, fetch=True, normalize_weight=False):
+        """``normalize_weight`` (not in the reference, whose driver normalises on the host, lib/ssnet_trainval.py:173): the fed
+        weights are divided by their per-event sums on the device before the step (``_normalize_fed_weight``); ``input_weight``
+        itself, host array or device tensor, is left as it is."""
         if not self._trainable:
             raise RuntimeError('accum_gradients: constructed with trainable=False')
         fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
+        if normalize_weight:
+            self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
@@ -716,8 +763,10 @@ class ssnet_base(object):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.all_reduce(self._grads, op=dist.ReduceOp.SUM)
 
-    def run_test(self, sess, input_data, input_label, input_weight=None):
+    def run_test(self, sess, input_data, input_label, input_weight=None, normalize_weight=False):
         fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
+        if normalize_weight:
+            self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()

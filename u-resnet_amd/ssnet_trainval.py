@@ -198,22 +198,30 @@ class ssnet_trainval(object):
 
     def _pull(self, io, kd, kl, kw):
         """One batch off an IO stream; the per-event weight normalisation mutates the IO buffer in place
-        (lib/ssnet_trainval.py:173)."""
+        (lib/ssnet_trainval.py:173).  With DEVICE_WEIGHT_NORM the raw weights are handed on and the network call normalises
+        them on the device (``normalize_weight=True``); the IO buffer is then not written."""
         data = io.fetch_data(kd).data()
         label = io.fetch_data(kl).data()
         weight = None
         if self._cfg.USE_WEIGHTS:
             weight = io.fetch_data(kw).data()
-            weight /= np.sum(weight, axis=1).reshape([weight.shape[0], 1])
+            if not self._cfg.DEVICE_WEIGHT_NORM:
+                weight /= np.sum(weight, axis=1).reshape([weight.shape[0], 1])
         return data, label, weight
 
     def _pull_voxels(self, io):
         """SPARSE_IO: the batch as a voxel list; the normalisation of lib/ssnet_trainval.py:173 is done on the list (the sum
-        over an event = listed weights + unlisted voxels x background weight, in float64)."""
+        over an event = listed weights + unlisted voxels x background weight, in float64).  With DEVICE_WEIGHT_NORM the list is
+        handed on as it is and the expanded dense tensor is normalised on the device."""
         vb = io.fetch_voxels()
-        if self._cfg.USE_WEIGHTS:
+        if self._cfg.USE_WEIGHTS and not self._cfg.DEVICE_WEIGHT_NORM:
             vb.normalize_weights()
         return vb
+
+    def _norm_kw(self):
+        """Keyword of the network calls that are fed what ``_pull`` / ``_pull_voxels`` returned.  Empty with the default
+        DEVICE_WEIGHT_NORM False: those calls are then made exactly as before."""
+        return {'normalize_weight': True} if self._cfg.DEVICE_WEIGHT_NORM and self._cfg.USE_WEIGHTS else {}
 
     def _run_minibatches(self, want_metrics):
         """zero -> NUM_MINIBATCHES x accumulate -> apply.  Returns the per-minibatch metrics [M, 3] when asked for
@@ -221,14 +229,15 @@ class ssnet_trainval(object):
         device-resident tensors of the last minibatch for a summary."""
         c, net = self._cfg, self._net
         rows = []
+        norm = self._norm_kw()
         net.zero_gradients(self._sess)
         for _ in range(c.NUM_MINIBATCHES):
             if c.SPARSE_IO:
-                res, doc = net.accum_gradients_voxels(self._sess, self._pull_voxels(self._input_main), fetch=want_metrics)
+                res, doc = net.accum_gradients_voxels(self._sess, self._pull_voxels(self._input_main), fetch=want_metrics, **norm)
             else:
                 data, label, weight = self._pull(self._input_main, c.KEYWORD_DATA, c.KEYWORD_LABEL, c.KEYWORD_WEIGHT)
                 res, doc = net.accum_gradients(sess=self._sess, input_data=data, input_label=label, input_weight=weight,
-                                               fetch=want_metrics)
+                                               fetch=want_metrics, **norm)
             # the copy has completed, the kernels are queued: the IO may refill this buffer while they run
             self._descr_metrics = doc[1:]
             if want_metrics:
@@ -266,7 +275,9 @@ class ssnet_trainval(object):
             train_mean = self._mean_over_ranks(per_minibatch.mean(axis=0))
             tested = None
             if test is not None:
-                tested = self._net.run_test_voxels(self._sess, test) if self._cfg.SPARSE_IO else self._net.run_test(self._sess, *test)
+                norm = self._norm_kw()
+                tested = (self._net.run_test_voxels(self._sess, test, **norm) if self._cfg.SPARSE_IO
+                          else self._net.run_test(self._sess, *test, **norm))
             if _is_rank0():
                 stamp = datetime.datetime.fromtimestamp(time.time()).strftime('%Y-%m-%d %H:%M:%S')
                 sys.stdout.write('@ iteration {:d} LR {:g} Mem {:g} @ {:s}\n'.format(
@@ -277,16 +288,16 @@ class ssnet_trainval(object):
                     sys.stdout.write('Test set: ')
                     self._report(*tested)
         if plan.summary:
-            last = self._last_minibatch
+            last = self._last_minibatch   # already normalised, on the host or on the device: never again here
             summ = self._net.make_summary(self._sess, last['input_data'], last['input_label'], last.get('input_weight'))
             if self._writer_train:
                 self._writer_train.add_summary(summ, plan.iteration)
             if self._writer_test and test is not None:
                 if self._cfg.SPARSE_IO:
-                    t3, _ = self._net.run_test_voxels(self._sess, test)
+                    t3, _ = self._net.run_test_voxels(self._sess, test, **self._norm_kw())
                     tsum = {'loss': t3[0], 'accuracy_all': t3[1], 'accuracy_nonzero': t3[2]}
                 else:
-                    tsum = self._net.make_summary(self._sess, *test)
+                    tsum = self._net.make_summary(self._sess, *test, **self._norm_kw())
                 self._writer_test.add_summary(tsum, plan.iteration)
         if plan.checkpoint and self._cfg.SAVE_FILE and _is_rank0():
             print('saved @', self.save_checkpoint())
