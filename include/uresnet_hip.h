@@ -154,7 +154,7 @@ int ursn_tensor(const ursn_net* net, const char* name, float** ptr, int64_t* vox
 /* Per-launch timing with HIP events recorded on the launch stream (bench.py roofline leg; the
  * reference has no counterpart: lib/ssnet_trainval.py:48-49 only reports peak bytes).
  * pass: 0 conv fwd, 1 conv dgrad, 2 conv wgrad, 3 bn stats, 4 bn apply, 5 bn backward, 6 head (the dense head records
- * kernel "head" / "bhead", the gather head of ursn_infer_voxels "vscores"). */
+ * kernel "head" / "bhead", the gather head of ursn_infer_voxels "vscores", the statistics of ursn_infer_stats "cstats"). */
 typedef struct ursn_prof_rec {
   char kernel[48];
   char layer[96];
@@ -400,6 +400,42 @@ int ursn_infer_voxels(ursn_net* net, const float* data, const float* label, int3
 int ursn_normalize_weights(const float* weight, float* out, int32_t n, int64_t voxels, float* sums_out,
                            void* scratch, size_t scratch_bytes, void* stream);
 size_t ursn_normalize_weights_scratch_bytes(int32_t n, int64_t voxels);
+
+/* ---- per-event, per-class analysis statistics (ana_stats.hip) --------------------------------------------------------
+ * Appended functions and one struct only: URSN_ABI_VERSION stays 9.
+ * What example_scripts/ana_csv.py:67-116 computes per event on the host from the dense softmax, reduced on the device from conv2's
+ * stored logits: for voxel p of event e the logits, the prediction (strict '>' argmax, lowest index on ties: tf.argmax) and the
+ * scores are formed exactly as ursn_scores_at_voxels forms them (same layouts, same bits), t = (int)label[p] truncates toward
+ * zero like the dense head, and
+ *   t in [0, C):  conf[e][t][pred] += 1, score_sum[e][t] += (double)score[t], score_sq[e][t] += (double)score[t] * score[t]
+ *   otherwise  :  other[e][label > 0 ? 0 : 1] += 1 (a NaN label lands in other[e][1]); the voxel matches no prediction
+ *   nonzero[e] = {voxels with data > 0, of those pred == t} (lib/ssnet.py:59; one input channel). */
+typedef struct ursn_class_stats_out {      /* all DEVICE pointers, 8-byte aligned; each may be NULL except conf */
+  int64_t* conf;      /* [n][C][C]  conf[e][t][p] = voxels of event e with label t and prediction p                */
+  int64_t* other;     /* [n][2]     labels outside [0,C): {those > 0, the rest (<= 0 after the cast, NaN)}          */
+  int64_t* nonzero;   /* [n][2]     {voxels with data > 0, of those pred == label}; needs d->data                  */
+  double*  score_sum; /* [n][C]     sum over voxels with label k of score[k]                                       */
+  double*  score_sq;  /* [n][C]     sum over the same voxels of score[k]^2                                         */
+} ursn_class_stats_out;
+
+/* d: n, voxels, ncls, z / z_cstride / dtype, mean / rstd / beta and data as in ursn_scores_at_voxels; offsets / index are unused and
+ * may be NULL.  label [n, voxels] fp32.  Two launches: a workgroup owns a fixed compile-time span of 4096 consecutive voxels of one
+ * event and writes its partial counts and fp64 sums to the scratch; a second launch reduces each event's partials in a fixed
+ * tree.  No global atomics, the scratch needs no initialisation, the same arguments give the same bits; integer counts are
+ * exact.  An event with no voxel of class k leaves zeros in row k.  Enqueues only; never synchronises.
+ * scratch: 8-byte aligned, >= ursn_class_stats_scratch_bytes(n, voxels, ncls) (0 for n outside [1, 65535], voxels outside
+ * [1, 2^31) or ncls outside [1, 8]).  Null, misaligned, out-of-domain and too-small arguments are refused before any launch. */
+int ursn_class_stats(const ursn_vscores_desc* d, const float* label, const ursn_class_stats_out* out, void* scratch,
+                     size_t scratch_bytes, void* stream);
+size_t ursn_class_stats_scratch_bytes(int32_t n, int64_t voxels, int32_t ncls);
+
+/* ursn_infer_labels with every dense output optional, plus the statistics: one forward pass, then ursn_class_stats on conv2's
+ * stored z / mean / rstd (both plans) with scratch from the handle's workspace.  label and stats (stats->conf) are required.  The
+ * dense head is launched only if one of labels_out / softmax_out / out2 is given and then writes exactly what ursn_infer_labels
+ * writes (labels_out: >= 3 classes and cin == 1).  The statistics work for any num_class in 1..8 and any cin; with cin != 1
+ * stats->nonzero must be NULL.  Recorded as pass 6, kernel "cstats", when profiling.  Always synchronises, like ursn_infer. */
+int ursn_infer_stats(ursn_net* net, const float* data, const float* label, int32_t n, float* labels_out, float* softmax_out,
+                     float* out2, const ursn_class_stats_out* stats, void* stream);
 
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);

@@ -66,6 +66,11 @@ class ursn_vscores_desc(C.Structure):
                 ("offsets", C.c_void_p), ("index", C.c_void_p)]
 
 
+class ursn_class_stats_out(C.Structure):
+    _fields_ = [("conf", C.c_void_p), ("other", C.c_void_p), ("nonzero", C.c_void_p), ("score_sum", C.c_void_p),
+                ("score_sq", C.c_void_p)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -124,6 +129,9 @@ _SIGS = {
     "ursn_infer_voxels": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_float), _P]),
     "ursn_normalize_weights": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_size_t, _P]),
     "ursn_normalize_weights_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "ursn_class_stats": (C.c_int, [C.POINTER(ursn_vscores_desc), _P, C.POINTER(ursn_class_stats_out), _P, C.c_size_t, _P]),
+    "ursn_class_stats_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
+    "ursn_infer_stats": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.POINTER(C.c_float), C.POINTER(ursn_class_stats_out), _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

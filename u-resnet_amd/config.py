@@ -59,6 +59,11 @@ class ssnet_config(object):
     # hands the raw weights on and the network calls divide them by their per-event sums on the device (ursn_normalize_weights:
     # fp64 sum, correctly rounded fp32 division); the IO buffer is then not written.  False = the reference's host pass
     DEVICE_WEIGHT_NORM = False
+    # not in the reference (example_scripts/ana_csv.py computes its CSV on the host from the dense softmax): a file name = ana_step
+    # makes its one forward pass through ssnet_base.inference_stats* and appends the reference's CSV row per entry (per-event
+    # accuracies, per-class pixel count / accuracy / score mean / score std, reduced on the device); '' = off.  Ignored with
+    # TRAIN; refused together with SPARSE_SCORES
+    ANA_CSV = ''
 
     def __init__(self):
         pass

@@ -71,6 +71,8 @@ struct ursn_net {
   void* red_scratch = nullptr;
   void* red_scratch2 = nullptr;   // statistics partials of the shortcut convs running on the second stream (forward)
   void* head_scratch = nullptr;
+  void* cs_scratch = nullptr;   // ursn_infer_stats: per-span partials of the class statistics (ana_stats.hip)
+  size_t cs_scratch_bytes = 0;
   void* wg_scratch = nullptr;
   size_t wg_scratch_bytes = 0;
   float* dc_scratch = nullptr;   // packed weights (+ split-K slabs) of the deep-level kernel (conv_deep.hip), main stream only
@@ -371,6 +373,8 @@ int plan(ursn_net* n, Arena& A) {
   n->wg_scratch_bytes = wg;
   n->wg_scratch = tr ? A.take(wg + 256) : nullptr;
   n->bs_scratch = tr ? (double*)A.take((size_t)16384 * 3 * 8 * sizeof(double)) : nullptr;
+  n->cs_scratch_bytes = ursn_class_stats_scratch_bytes(c.max_batch, n->lvox[0], c.num_class);
+  n->cs_scratch = A.take(n->cs_scratch_bytes);
 
   n->sizes.n_params = poff;
   n->sizes.n_layers = (int64_t)n->layers.size();
@@ -1232,6 +1236,43 @@ extern "C" int ursn_infer_voxels(ursn_net* net, const float* data, const float* 
     }
   }
   if (dense_head) URSN_TRY(read_metrics(net, out2, 2, s));
+  else URSN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// Forward, the dense head only when one of its outputs is asked for, then the class statistics on conv2's stored z / mean / rstd
+// (ana_stats.hip) with the partials in the handle's workspace.
+extern "C" int ursn_infer_stats(ursn_net* net, const float* data, const float* label, int32_t n, float* labels_out,
+                                float* softmax_out, float* out2, const ursn_class_stats_out* stats, void* stream) {
+  URSN_TRY(check_call(net, data, n));
+  URSN_REQUIRE(label, "infer_stats: label is null");
+  URSN_REQUIRE(stats && stats->conf, "infer_stats: stats / stats->conf is null");
+  URSN_REQUIRE(!labels_out || (net->cfg.num_class >= 3 && net->cfg.cin == 1),
+               "infer_stats: labels_out needs >= 3 classes and one input channel");
+  URSN_REQUIRE(!stats->nonzero || net->cfg.cin == 1, "infer_stats: stats->nonzero needs one input channel (cin = %d)",
+               (int)net->cfg.cin);
+  URSN_REQUIRE(net->cfg.num_class >= 1 && net->cfg.num_class <= 8, "infer_stats: num_class %d not in [1, 8]",
+               (int)net->cfg.num_class);
+  hipStream_t s = (hipStream_t)stream;
+  net->last_n = n;
+  const bool dense_head = labels_out || softmax_out || out2;
+  if (net->bf) {
+    URSN_TRY(bnet_infer_stats(net->bf, data, label, n, dense_head, labels_out, softmax_out, stats, s));
+  } else {
+    URSN_TRY(forward(net, data, n, s));
+    if (dense_head) URSN_TRY(head(net, data, label, nullptr, n, softmax_out, false, s, labels_out));
+    const Layer& L = net->layers[net->conv2];
+    ursn_vscores_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = n; d.voxels = net->lvox[0]; d.ncls = net->cfg.num_class;
+    d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
+    d.mean = L.mean; d.rstd = L.rstd; d.beta = net->params + L.b_off;
+    d.data = net->cfg.cin == 1 ? data : nullptr;
+    ProfScope ps(net, s, net->conv2, 6, 0.0, (double)n * net->lvox[0] * (4.0 * L.zcs + 4.0 + (d.data ? 4.0 : 0.0)));
+    URSN_TRY(launch_cstats(&d, label, stats, net->cs_scratch, net->cs_scratch_bytes, s));
+    ps.done("cstats");
+  }
+  if (out2) URSN_TRY(read_metrics(net, out2, 2, s));
   else URSN_HIP(hipStreamSynchronize(s));
   return 0;
 }

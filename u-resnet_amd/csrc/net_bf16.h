@@ -17,6 +17,9 @@ int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* 
 // conv2's operands; enqueues only
 int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N, const int64_t* offsets, const int32_t* index,
                       int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, hipStream_t s);
+// ursn_infer_stats: forward, the dense head only with dense_head, the class statistics (ana_stats.hip) on conv2's z / mean / rstd
+int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N, bool dense_head, float* labels_out,
+                     float* softmax_out, const ursn_class_stats_out* stats, hipStream_t s);
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride);
 // per-launch HIP-event records (as ursn_profile_enable / ursn_profile_read of the fp32 plan) and the weight-gradient stream switch
 int bnet_profile_enable(ursn_bnet* n, int on);

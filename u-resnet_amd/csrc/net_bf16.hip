@@ -97,6 +97,8 @@ struct ursn_bnet {
   double* stats = nullptr; size_t stats_doubles = 0;
   void* bn_scratch = nullptr;
   void* head_scratch = nullptr;
+  void* cs_scratch = nullptr;   // ursn_infer_stats: per-span partials of the class statistics (ana_stats.hip)
+  size_t cs_scratch_bytes = 0;
   void* wg_scratch = nullptr; size_t wg_bytes = 0;
   double* stats2 = nullptr;
   hipStream_t s2 = nullptr;
@@ -383,6 +385,8 @@ int plan(ursn_bnet* n, Arena& A) {
   n->wg_bytes = wg;
   n->wg_scratch = tr ? A.take(wg + 256) : nullptr;
   n->bs_scratch = tr ? (double*)A.take((size_t)16384 * 24 * sizeof(double)) : nullptr;
+  n->cs_scratch_bytes = ursn_class_stats_scratch_bytes(c.max_batch, n->lvox[0], c.num_class);
+  n->cs_scratch = A.take(n->cs_scratch_bytes);
 
   n->sizes.n_params = poff;
   n->sizes.n_layers = (int64_t)n->layers.size();
@@ -1060,6 +1064,24 @@ int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N
   if (m_total == 0) return 0;
   BProf ps(n, s, n->conv2, 6, 0.0, (double)m_total * (16.0 + 4.0 + 4.0 * d.ncls + 6.0), "vscores");
   return launch_vscores(&d, scores_out, pred_out, ana_out, m_total, s);
+}
+
+// ursn_infer_stats: forward, the dense head when one of its outputs is asked for (as bnet_step's inference mode runs it), then the
+// class statistics (ana_stats.hip) on conv2's z / mean / rstd and the padded beta
+int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N, bool dense_head, float* labels_out,
+                     float* softmax_out, const ursn_class_stats_out* stats, hipStream_t s) {
+  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  URSN_TRY(forward(n, data, N, s));
+  if (dense_head) URSN_TRY(head(n, data, label, nullptr, N, softmax_out, false, s, labels_out));
+  const BLayer& L = n->layers[n->conv2];
+  ursn_vscores_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
+  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
+  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  d.data = data;
+  BProf ps(n, s, n->conv2, 6, 0.0, (double)N * n->lvox[0] * (16.0 + 4.0 + 4.0), "cstats");
+  return launch_cstats(&d, label, stats, n->cs_scratch, n->cs_scratch_bytes, s);
 }
 
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride) {

@@ -132,6 +132,56 @@ class VoxelBatch(object):
         return VoxelBatch(off, cat('index'), cat('value'), cat('label'), cat('weight'), cat('bg_weight'), V)
 
 
+def class_stats_from_counts(conf, other, score_sum, score_sq, nonzero=None):
+    """The per-event quantities of example_scripts/ana_csv.py:67-116 from what ``ursn_class_stats`` returns: ``conf`` [n, C, C]
+    (label, prediction) counts, ``other`` [n, 2] labels outside [0, C) {> 0, the rest}, ``score_sum`` / ``score_sq`` [n, C] fp64 sums
+    of each class's score over the voxels that carry it, ``nonzero`` [n, 2] {data > 0, of those correct} or None.  Returns a dict
+    of numpy arrays; the reference's sentinels: -1.0 in ``acc_class`` / ``score_mean`` / ``score_std`` where ``npx == 0``
+    (ana_csv.py:99-101), NaN where an accuracy has no voxel to be taken over.  A label that is not an integer counts as the class
+    it truncates to (the network's cast), where the reference's ``prediction == label`` never holds for it."""
+    conf = np.asarray(conf, dtype=np.int64)
+    other = np.asarray(other, dtype=np.int64)
+    ssum, ssq = np.asarray(score_sum, dtype=np.float64), np.asarray(score_sq, dtype=np.float64)
+    n = conf.shape[0]
+    npx = conf.sum(axis=2)
+    diag = np.diagonal(conf, axis1=1, axis2=2)
+    some = npx > 0
+    den = np.where(some, npx, 1).astype(np.float64)
+    mean = ssum / den
+    std = np.sqrt(np.maximum(ssq / den - mean * mean, 0.0))     # population std: numpy's .std()
+    voxels = conf.sum(axis=(1, 2)) + other.sum(axis=1)
+
+    def ratio(num, cnt):
+        return np.where(cnt > 0, num / np.where(cnt > 0, cnt, 1).astype(np.float64), np.nan)
+    res = {'conf': conf, 'other': other, 'npx': npx,
+           'acc_class': np.where(some, diag / den, -1.0),
+           'score_mean': np.where(some, mean, -1.0),
+           'score_std': np.where(some, std, -1.0),
+           'acc_all': diag.sum(axis=1) / voxels.astype(np.float64),
+           # ana_csv.py:81-84: over label > 0, i.e. classes >= 1 plus the labels >= C (which match no prediction)
+           'acc_nonzero_label': ratio(diag[:, 1:].sum(axis=1), npx[:, 1:].sum(axis=1) + other[:, 0])}
+    if nonzero is None:
+        res['acc_nonzero_data'] = np.full(n, np.nan)
+    else:
+        nz = np.asarray(nonzero, dtype=np.int64)
+        res['acc_nonzero_data'] = ratio(nz[:, 1], nz[:, 0])
+    return res
+
+
+def ana_csv_header(num_class):
+    """The header line of example_scripts/ana_csv.py:30-37."""
+    return 'entry,acc_all,acc_nonzero' + ''.join(
+        ',npx_class%d,acc_class%d,mean_softmax_class%d,std_softmax_class%d' % (i, i, i, i) for i in range(num_class)) + '\n'
+
+
+def ana_csv_row(entry, stats, i):
+    """Event ``i`` of an ``inference_stats`` result as the reference's CSV row (example_scripts/ana_csv.py:87,113-116)."""
+    row = '%d,%g,%g' % (entry, stats['acc_all'][i], stats['acc_nonzero_label'][i])
+    for k in range(stats['npx'].shape[1]):
+        row += ',%d,%g,%g,%g' % (stats['npx'][i, k], stats['acc_class'][i, k], stats['score_mean'][i, k], stats['score_std'][i, k])
+    return row + '\n'
+
+
 class ssnet_base(object):
 
     def __init__(self, dims, num_class):
@@ -623,7 +673,17 @@ class ssnet_base(object):
         self._last_feed = fd
         self._mark_consumed(fd)
         # the label rule ends in "* (data > 1.0)" and every unlisted voxel holds 0: the host knows the exact upper bound
-        cap = int(np.count_nonzero(voxels.value > 1.0))
+        res = [self.labels_to_voxel_sets(sess, labels, int(np.count_nonzero(voxels.value > 1.0)))]
+        if with_labels:
+            res += [float(acc[0]), float(acc[1])]
+        return res
+
+    def labels_to_voxel_sets(self, sess, labels, cap):
+        """Device label volume [n, voxels] -> per-event (index int32[], class uint8[]) of its non-zeros (``ursn_labels_to_voxels``);
+        ``cap`` bounds their number over the batch."""
+        import torch
+        lib = _lib.load()
+        n, V = int(labels.shape[0]), self._label_size
         index = torch.empty(max(cap, 1), dtype=torch.int32, device=self._device)
         cls = torch.empty(max(cap, 1), dtype=torch.uint8, device=self._device)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=self._device)
@@ -634,10 +694,7 @@ class ssnet_base(object):
         off = offsets.cpu().numpy()
         assert 0 <= int(off[-1]) <= cap, 'labels_to_voxels: %d non-zero labels, at most %d expected' % (int(off[-1]), cap)
         idx, cl = index[:int(off[-1])].cpu().numpy(), cls[:int(off[-1])].cpu().numpy()
-        res = [[(idx[off[i]:off[i + 1]].copy(), cl[off[i]:off[i + 1]].copy()) for i in range(n)]]
-        if with_labels:
-            res += [float(acc[0]), float(acc[1])]
-        return res
+        return [(idx[off[i]:off[i + 1]].copy(), cl[off[i]:off[i + 1]].copy()) for i in range(n)]
 
     def inference_voxel_scores(self, sess, voxels, with_labels=True, want=('scores', 'pred', 'ana')):
         """The output side of the voxel-list boundary: class scores, argmax class and ana label (lib/ssnet_trainval.py:285-287) AT
@@ -816,6 +873,58 @@ class ssnet_base(object):
         if with_softmax:
             res.append(sm.cpu().numpy() if as_numpy else sm)
         return res
+
+    def _infer_stats(self, sess, fd, with_labels, with_softmax, as_numpy):
+        import torch
+        n, C = int(fd['input_data'].shape[0]), self._num_class
+        self._ensure_handle(n)
+        sp = tuple(int(x) for x in self._dims[:-1])
+        dev = self._device
+        conf = torch.empty((n, C, C), dtype=torch.int64, device=dev)
+        other = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        nonzero = torch.empty((n, 2), dtype=torch.int64, device=dev) if int(self._dims[-1]) == 1 else None
+        ssum = torch.empty((n, C), dtype=torch.float64, device=dev)
+        ssq = torch.empty((n, C), dtype=torch.float64, device=dev)
+        out = _lib.ursn_class_stats_out()
+        out.conf, out.other, out.score_sum, out.score_sq = conf.data_ptr(), other.data_ptr(), ssum.data_ptr(), ssq.data_ptr()
+        out.nonzero = nonzero.data_ptr() if nonzero is not None else None
+        labels = torch.empty((n,) + sp, dtype=torch.float32, device=dev) if with_labels else None
+        sm = torch.empty((n,) + sp + (C,), dtype=torch.float32, device=dev) if with_softmax else None
+        dense = with_labels or with_softmax
+        acc = (ctypes.c_float * 2)()
+        _lib.check(_lib.load().ursn_infer_stats(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']), n,
+                                                self._ptr(labels), self._ptr(sm), acc if dense else None, ctypes.byref(out),
+                                                self._stream(sess)))
+        self._last_feed = fd
+        self._mark_consumed(fd)
+        res = class_stats_from_counts(conf.cpu().numpy(), other.cpu().numpy(), ssum.cpu().numpy(), ssq.cpu().numpy(),
+                                      nonzero.cpu().numpy() if nonzero is not None else None)
+        if with_labels:
+            res['labels'] = labels.cpu().numpy() if as_numpy else labels
+        if with_softmax:
+            res['softmax'] = sm.cpu().numpy() if as_numpy else sm
+        if dense:
+            res['acc_all_batch'], res['acc_nonzero_batch'] = float(acc[0]), float(acc[1])
+        return res
+
+    def inference_stats(self, sess, input_data, input_label, with_labels=False, with_softmax=False, as_numpy=True):
+        """Per-event, per-class analysis statistics (example_scripts/ana_csv.py:67-116) from ONE forward pass, reduced on the
+        device from conv2's stored logits by ``ursn_infer_stats``: only a few hundred bytes per event come back.  Returns the dict
+        of ``class_stats_from_counts`` (``conf``, ``other``, ``npx``, ``acc_class``, ``score_mean``, ``score_std``, ``acc_all``,
+        ``acc_nonzero_label``, ``acc_nonzero_data``).  ``with_labels`` / ``with_softmax`` add the dense outputs of
+        ``inference_labels`` from the same pass (``labels``, ``softmax``) and, with either, the batch accuracies it returns
+        (``acc_all_batch``, ``acc_nonzero_batch``); without them the dense head is not launched at all."""
+        if input_label is None:
+            raise ValueError('inference_stats: input_label is required')
+        fd = {'input_data': self._feed(input_data, self._data_size, 'data'),
+              'input_label': self._feed(input_label, self._label_size, 'label')}
+        return self._infer_stats(sess, fd, with_labels, with_softmax, as_numpy)
+
+    def inference_stats_voxels(self, sess, voxels, with_labels=False, with_softmax=False, as_numpy=True):
+        """``inference_stats`` fed a VoxelBatch (with a label list), expanded on the device: no dense label crosses PCIe."""
+        self._require_single_channel('inference_stats_voxels')
+        fd = self._feed_voxels(voxels, with_label=True, with_weight=False)
+        return self._infer_stats(sess, fd, with_labels, with_softmax, as_numpy)
 
     # ------------------------------------------------------------------------------------------
     # variables (checkpoint / weight injection)

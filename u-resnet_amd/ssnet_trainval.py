@@ -33,7 +33,7 @@ import time
 import numpy as np
 
 from .config import ssnet_config
-from .ssnet import HipSession
+from .ssnet import HipSession, ana_csv_header, ana_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 
@@ -80,6 +80,7 @@ class ssnet_trainval(object):
         self._input_main = None
         self._input_test = None
         self._output = None
+        self._csv = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -139,11 +140,20 @@ class ssnet_trainval(object):
         if not cfg.MAIN_INPUT_CONFIG:
             print('Must provide larcv data filler configuration file!')
             return
+        if cfg.ANA_CSV and not cfg.TRAIN and cfg.SPARSE_SCORES:
+            raise ValueError('ANA_CSV cannot be combined with SPARSE_SCORES: the per-class statistics run over every voxel, '
+                             'SPARSE_SCORES returns scores at the listed voxels only')
         self._input_main = self._open_stream('MainIO', cfg.MAIN_INPUT_CONFIG, cfg.MINIBATCH_SIZE)
         if cfg.TEST_INPUT_CONFIG:
             self._input_test = self._open_stream('TestIO', cfg.TEST_INPUT_CONFIG, cfg.TEST_BATCH_SIZE)
         if cfg.ANA_OUTPUT_CONFIG:
             self._output = open(cfg.ANA_OUTPUT_CONFIG, 'ab')   # appended ssnet label volumes (.npy records)
+        if cfg.ANA_CSV and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_CSV) or os.path.getsize(cfg.ANA_CSV) == 0
+            self._csv = open(cfg.ANA_CSV, 'a')
+            if fresh:
+                self._csv.write(ana_csv_header(cfg.NUM_CLASS))
+                self._csv.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -382,8 +392,61 @@ class ssnet_trainval(object):
         self._advance_main()
         return result
 
+    def _ana_step_csv(self, batch_mode):
+        """ANA_CSV: ana_step's one forward pass goes through ``inference_stats`` / ``inference_stats_voxels``; the ANA_OUTPUT
+        records are those of ``ana_step`` / ``_ana_step_voxels``, one CSV row (example_scripts/ana_csv.py) is appended per entry
+        and the interactive result dict also holds ``stats``."""
+        from .synthetic_io import voxels_to_dense
+        c, io, net = self._cfg, self._input_main, self._net
+        want = dict(with_labels=bool(self._output), with_softmax=not batch_mode)
+        if c.SPARSE_IO:
+            vb = io.fetch_voxels()
+            entries = io.fetch_entries()
+            on_device = batch_mode and bool(self._output)   # nothing dense crosses PCIe: the voxel set is compacted on the device
+            stats = net.inference_stats_voxels(self._sess, vb, as_numpy=not on_device, **want)
+            if not batch_mode:
+                batch_data, batch_label, _ = voxels_to_dense(vb)
+        else:
+            batch_data = io.fetch_data(c.KEYWORD_DATA).data()
+            batch_label = io.fetch_data(c.KEYWORD_LABEL).data()
+            entries = io.fetch_entries()
+            stats = net.inference_stats(self._sess, batch_data, batch_label, **want)
+        acc_all, acc_nonzero = stats.get('acc_all_batch'), stats.get('acc_nonzero_batch')
+        if self._output:
+            labels = stats.pop('labels')
+            if c.SPARSE_IO:
+                if on_device:
+                    sets = net.labels_to_voxel_sets(self._sess, labels, int(np.count_nonzero(vb.value > 1.0)))
+                else:
+                    flat = labels.reshape(labels.shape[0], -1)
+                    sets = [(np.flatnonzero(v).astype(np.int32), v[np.flatnonzero(v)].astype(np.uint8)) for v in flat]
+                for i, (index, cls) in enumerate(sets):
+                    print('Entry', entries[i], 'Acc', acc_nonzero)
+                    np.save(self._output, index)
+                    np.save(self._output, cls)
+            else:
+                for i in range(labels.shape[0]):
+                    print('Entry', entries[i], 'Acc', acc_nonzero)
+                    np.save(self._output, labels[i])
+            self._output.flush()
+        for i in range(len(entries)):
+            self._csv.write(ana_csv_row(entries[i], stats, i))
+        self._csv.flush()
+        result = None
+        if not batch_mode:
+            softmax = stats.pop('softmax')
+            img_shape = list(softmax.shape)
+            img_shape[-1] = -1
+            result = {'entries': np.array(entries), 'input': np.array(batch_data).reshape(img_shape),
+                      'label': np.array(batch_label).reshape(img_shape), 'softmax': softmax,
+                      'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'stats': stats}
+        self._advance_main()
+        return result
+
     def ana_step(self, batch_mode=False):
         self._iteration += 1
+        if self._csv:
+            return self._ana_step_csv(batch_mode)
         if self._cfg.SPARSE_IO:
             return self._ana_step_voxels(batch_mode)
         c, io = self._cfg, self._input_main
@@ -431,7 +494,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
