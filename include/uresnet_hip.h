@@ -437,6 +437,55 @@ size_t ursn_class_stats_scratch_bytes(int32_t n, int64_t voxels, int32_t ncls);
 int ursn_infer_stats(ursn_net* net, const float* data, const float* label, int32_t n, float* labels_out, float* softmax_out,
                      float* out2, const ursn_class_stats_out* stats, void* stream);
 
+/* ---- external loss boundary (ext_loss.hip) ---------------------------------------------------------------------------
+ * Appended functions only: URSN_ABI_VERSION stays 9.
+ * The reference computes one loss, the weighted softmax cross-entropy of lib/ssnet.py:57-71, inside its graph.  These calls cut
+ * the step open at the logits so that a caller's own objective (focal / dice terms, a masked or auxiliary loss, a distillation
+ * target) can sit between the forward and the backward pass: logits out, d(loss)/d(logits) in, gradients ADDED to the flat
+ * buffer exactly like ursn_accum_step's, and optionally d(loss)/d(input).  Every call below enqueues only and never
+ * synchronises (on the bf16 plan the forward pass uploads its weight-packing table once per batch size, as in every other call);
+ * null, misaligned, out-of-domain and too-small arguments are refused with a message before any launch. */
+
+/* Dense logits from conv2's stored operands: logits_out [n, voxels, ncls] fp32, compact and channel-last,
+ *     logit[k] = fma(z[p][k], rstd[k], beta[k] - mean[k] * rstd[k])
+ * exactly as the heads and ursn_scores_at_voxels form it.  d: n, voxels, ncls, z / z_cstride / dtype, mean / rstd / beta as in
+ * ursn_scores_at_voxels (fp32 at any stride >= ncls, one 16-byte load per voxel at stride 4 | 8 with a 16-byte aligned z; bf16 bit
+ * patterns at stride 8; mean == NULL: z already holds logits); data / offsets / index are unused.  logits_out needs 4-byte
+ * alignment only.  One launch, no atomics, no scratch. */
+int ursn_logits_dense(const ursn_vscores_desc* d, float* logits_out, void* stream);
+
+/* The caller's compact fp32 dlogits [n, voxels, ncls] in the layout of a plan's d(loss)/d(logits) tensor, written as the head of
+ * that layout writes it: dtype 0, out_cstride 4 with <= 4 classes and a 16-byte aligned out: one 16-byte store per voxel, pad
+ * lanes zero; dtype 0 otherwise (out_cstride >= ncls): the ncls values, pad lanes NOT written; dtype 1 (out_cstride 8, 16-byte
+ * aligned): bf16 round-to-nearest-even, pad lanes zero.  One launch, no atomics, no scratch. */
+int ursn_dlogits_pack(const float* dlogits, int32_t n, int64_t voxels, int32_t ncls, void* out, int32_t out_cstride,
+                      int32_t dtype, void* stream);
+
+/* Input gradient of the first convolution (k3 s1 SAME, lib/uresnet.py:37-45), which no step forms:
+ *     dinput_out[n, p, c] = sum over the 3^ndim taps k and f < F of dz[n, p - (k - 1), f] * w[k, c, f]     (fp32, [n, voxels, cin])
+ * dz: conv0's stored BatchNorm-backward output, fp32 at dz_cstride >= F floats (dtype 0) or bf16 bit patterns at a stride that
+ * is a multiple of 8 (dtype 1: cin == 1, F % 8 == 0, 16-byte aligned).  w: the fp32 master weights [3^ndim, cin, F] as
+ * ursn_param lays conv0's out; with dtype 1 they are rounded to bf16 on load, the value the bf16 plan's other data gradients
+ * use.  fp32 accumulation.  One launch: the dz tile and its halo are staged once in LDS. */
+int ursn_conv0_input_grad(int32_t ndim, const int32_t* spatial, int32_t n, int32_t cin, int32_t F, const void* dz,
+                          int32_t dz_cstride, int32_t dtype, const float* w, float* dinput_out, void* stream);
+
+/* The forward pass of ursn_accum_step (every stored operand is bit for bit what a step stores), then ursn_logits_dense on conv2's
+ * operands; the head is not launched and the metrics buffer is not touched.  Needs a trainable handle.  logits_out
+ * [n, *spatial, num_class] fp32.  Both plans.  Recorded as pass 6, kernel "logits", when profiling. */
+int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, float* logits_out, void* stream);
+
+/* The backward pass of ursn_accum_step started from the caller's dlogits [n, *spatial, num_class] fp32: ursn_dlogits_pack into
+ * the handle's d(logits) tensor -- with the BatchNorm-backward partials of the logits layer where the plan's head would have
+ * carried them, in the head's partition and order, so that dlogits equal to the head's give the step's gradients bit for bit --
+ * then the unchanged backward chain; gradients are ADDED to the flat buffer.  dinput_out (nullable) [n, *spatial, cin] fp32:
+ * ursn_conv0_input_grad after conv0's BatchNorm backward has stored its dz.
+ * Legal only directly after ursn_forward_logits on the same handle with the same n and data pointer: any run call in between
+ * (accum_step, eval, every infer, another forward_logits), ursn_apply_adam, or a backward_logits that already consumed the
+ * forward makes the call fail with a message naming the reason, before anything is launched.
+ * Recorded as pass 6 "dlogits" and pass 1 "dinput" (layer conv0) when profiling. */
+int ursn_backward_logits(ursn_net* net, const float* data, const float* dlogits, int32_t n, float* dinput_out, void* stream);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

@@ -132,6 +132,12 @@ _SIGS = {
     "ursn_class_stats": (C.c_int, [C.POINTER(ursn_vscores_desc), _P, C.POINTER(ursn_class_stats_out), _P, C.c_size_t, _P]),
     "ursn_class_stats_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
     "ursn_infer_stats": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.POINTER(C.c_float), C.POINTER(ursn_class_stats_out), _P]),
+    "ursn_logits_dense": (C.c_int, [C.POINTER(ursn_vscores_desc), _P, _P]),
+    "ursn_dlogits_pack": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    "ursn_conv0_input_grad": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                        _P, _P, _P]),
+    "ursn_forward_logits": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    "ursn_backward_logits": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -12,6 +12,7 @@
 
 #include "ursn_common.h"
 #include "net_bf16.h"
+#include "ext_loss.h"
 
 int conv_dispatch(const ursn_conv_desc& d, ConvPass pass, const float* in, const float* w, float* out, int accumulate,
                   hipStream_t s);
@@ -85,6 +86,10 @@ struct ursn_net {
   const float* vdz_g = nullptr;
   int64_t adam_t = 0;
   int last_n = 0;
+  // external loss boundary: the forward of ursn_forward_logits that ursn_backward_logits may still continue
+  // (0 none ran, 1 pending, 2 consumed by a backward, 3 overwritten by another run call, 4 parameters changed by apply_adam)
+  int pend_state = 0, pend_n = 0;
+  const float* pend_data = nullptr;
   // optional per-launch timing with HIP events on the launch stream (bench.py roofline leg)
   bool profile = false;
   struct ProfRec { int layer; int pass; const char* kernel; double flops; double bytes; hipEvent_t e0, e1; long l0; int launches; };
@@ -889,6 +894,7 @@ int read_metrics(ursn_net* n, float* out, int cnt, hipStream_t s) {
 
 int check_call(ursn_net* n, const float* data, int N) {
   URSN_REQUIRE(n, "null handle");
+  if (n->pend_state == 1) n->pend_state = 3;   // every run call overwrites the activations a pending forward_logits stored
   URSN_REQUIRE(data, "input_data is null");
   URSN_REQUIRE(N >= 1 && N <= n->cfg.max_batch, "batch %d outside [1,%d]", N, n->cfg.max_batch);
   return 0;
@@ -1147,6 +1153,7 @@ extern "C" int ursn_apply_adam(ursn_net* net, float lr, void* stream) {
   URSN_REQUIRE(net && net->grads, "apply_adam: net is not trainable");
   const double b1 = 0.9, b2 = 0.999;
   if (lr <= 0.f) lr = 1e-3f;  // tf.train.AdamOptimizer() default (lib/ssnet.py:72-73)
+  if (net->pend_state == 1) net->pend_state = 4;
   net->adam_t += 1;
   double lr_t = (double)lr * sqrt(1.0 - pow(b2, (double)net->adam_t)) / (1.0 - pow(b1, (double)net->adam_t));
   return launch_adam(net->params, net->grads, net->adam_m, net->adam_v, net->sizes.n_params, (float)lr_t, (float)b1,
@@ -1274,6 +1281,78 @@ extern "C" int ursn_infer_stats(ursn_net* net, const float* data, const float* l
   }
   if (out2) URSN_TRY(read_metrics(net, out2, 2, s));
   else URSN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- external loss boundary (ext_loss.hip) ------------------------------------------------------------------------------------
+// The step of ursn_accum_step cut open at the logits: forward() as a step runs it, then logits_dense instead of the head.
+extern "C" int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, float* logits_out, void* stream) {
+  URSN_TRY(check_call(net, data, n));
+  URSN_REQUIRE(net->cfg.trainable && net->grads, "forward_logits: net constructed with trainable=False");
+  URSN_REQUIRE(logits_out, "forward_logits: logits_out is null");
+  URSN_REQUIRE(((uintptr_t)logits_out & 3) == 0, "forward_logits: logits_out must be 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  net->last_n = n;
+  if (net->bf) {
+    URSN_TRY(bnet_forward_logits(net->bf, data, n, logits_out, s));
+  } else {
+    URSN_TRY(forward(net, data, n, s));
+    const Layer& L = net->layers[net->conv2];
+    ursn_vscores_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = n; d.voxels = net->lvox[0]; d.ncls = net->cfg.num_class;
+    d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
+    d.mean = L.mean; d.rstd = L.rstd; d.beta = net->params + L.b_off;
+    ProfScope ps(net, s, net->conv2, 6, 0.0, (double)n * net->lvox[0] * 4.0 * (L.zcs + d.ncls));
+    URSN_TRY(launch_logits_dense(&d, logits_out, s));
+    ps.done("logits");
+  }
+  net->pend_state = 1; net->pend_n = n; net->pend_data = data;
+  return 0;
+}
+
+// ... and continued from the caller's d(loss)/d(logits): dlogits_pack fills n->dlog and, where the head would have carried the
+// logits layer's BatchNorm-backward sums, the same partials; then the unchanged backward().  Gradients are ADDED like a step's.
+extern "C" int ursn_backward_logits(ursn_net* net, const float* data, const float* dlogits, int32_t n, float* dinput_out,
+                                    void* stream) {
+  URSN_REQUIRE(net, "backward_logits: null handle");
+  URSN_REQUIRE(net->cfg.trainable && net->grads, "backward_logits: net constructed with trainable=False");
+  URSN_REQUIRE(data && dlogits, "backward_logits: null data / dlogits");
+  URSN_REQUIRE((((uintptr_t)dlogits | (uintptr_t)dinput_out) & 3) == 0, "backward_logits: dlogits / dinput_out must be 4-byte aligned");
+  static const char* const why[5] = {
+      "no ursn_forward_logits has run on this handle", "",
+      "the pending ursn_forward_logits was already consumed by an ursn_backward_logits",
+      "another run call (accum_step, eval, infer*, forward_logits) overwrote the activations of the pending ursn_forward_logits",
+      "ursn_apply_adam changed the parameters after the pending ursn_forward_logits"};
+  URSN_REQUIRE(net->pend_state == 1, "backward_logits: %s", why[net->pend_state >= 0 && net->pend_state < 5 ? net->pend_state : 0]);
+  URSN_REQUIRE(n == net->pend_n, "backward_logits: batch %d, but the pending ursn_forward_logits ran batch %d", (int)n, net->pend_n);
+  URSN_REQUIRE(data == net->pend_data, "backward_logits: data is not the tensor the pending ursn_forward_logits read");
+  hipStream_t s = (hipStream_t)stream;
+  net->pend_state = 2;
+  if (net->bf) return bnet_backward_logits(net->bf, data, dlogits, n, dinput_out, s);
+  const Layer& L = net->layers[net->conv2];
+  {
+    // the handle state head() leaves behind: with the 4-padded logits its kernel carries the sums of conv2's BatchNorm backward
+    static const bool fuse = ursn_env_on("URSN_HEAD_BN_BWD");
+    double* bs = nullptr;
+    int blocks = 0;
+    net->bs_layer = -1;
+    if (fuse && net->bs_scratch && L.zcs == 4 && net->cfg.num_class <= 4 && head_blocks(n, net->lvox[0]) <= 16384) {
+      bs = net->bs_scratch; blocks = head_blocks(n, net->lvox[0]);
+      net->bs_layer = net->conv2; net->bs_blocks = blocks; net->bs_C = 4;
+    }
+    ProfScope ps(net, s, net->conv2, 6, 0.0, (double)n * net->lvox[0] * 4.0 * (net->cfg.num_class + L.zcs + (bs ? L.zcs : 0)));
+    URSN_TRY(launch_dlogits_pack(dlogits, n, net->lvox[0], net->cfg.num_class, net->dlog, L.zcs, 0, L.z, L.mean, L.rstd, bs, blocks, s));
+    ps.done("dlogits");
+  }
+  URSN_TRY(backward(net, data, n, s));
+  if (dinput_out) {   // conv0's BatchNorm backward has stored its dz; the weight gradient on the second stream only reads it
+    const Layer& L0 = net->layers[net->conv0];
+    ProfScope ps(net, s, net->conv0, 1, 2.0 * layer_macs(net, L0, n), (double)n * net->lvox[0] * 4.0 * (L0.cout + L0.cin) + 4.0 * L0.w_n);
+    URSN_TRY(launch_conv0_input_grad(net->cfg.ndim, net->cfg.spatial, n, L0.cin, L0.cout, L0.dz, L0.zcs, 0, net->params + L0.w_off,
+                                     dinput_out, s));
+    ps.done("dinput");
+  }
   return 0;
 }
 

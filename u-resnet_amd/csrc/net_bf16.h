@@ -20,6 +20,9 @@ int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N
 // ursn_infer_stats: forward, the dense head only with dense_head, the class statistics (ana_stats.hip) on conv2's z / mean / rstd
 int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N, bool dense_head, float* labels_out,
                      float* softmax_out, const ursn_class_stats_out* stats, hipStream_t s);
+// external loss boundary (ext_loss.hip): forward + logits_dense without the head; dlogits_pack + backward (+ conv0_input_grad)
+int bnet_forward_logits(ursn_bnet* n, const float* data, int N, float* logits_out, hipStream_t s);
+int bnet_backward_logits(ursn_bnet* n, const float* data, const float* dlogits, int N, float* dinput_out, hipStream_t s);
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride);
 // per-launch HIP-event records (as ursn_profile_enable / ursn_profile_read of the fp32 plan) and the weight-gradient stream switch
 int bnet_profile_enable(ursn_bnet* n, int on);

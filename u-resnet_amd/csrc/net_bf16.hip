@@ -20,6 +20,7 @@
 #include "bf16_common.h"
 #include "bf16_pack.h"
 #include "net_bf16.h"
+#include "ext_loss.h"
 
 namespace {
 
@@ -1082,6 +1083,49 @@ int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N,
   d.data = data;
   BProf ps(n, s, n->conv2, 6, 0.0, (double)N * n->lvox[0] * (16.0 + 4.0 + 4.0), "cstats");
   return launch_cstats(&d, label, stats, n->cs_scratch, n->cs_scratch_bytes, s);
+}
+
+// ursn_forward_logits: the forward of a step, then conv2's z / mean / rstd and the padded beta as dense fp32 logits; no head
+int bnet_forward_logits(ursn_bnet* n, const float* data, int N, float* logits_out, hipStream_t s) {
+  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  URSN_TRY(forward(n, data, N, s));
+  const BLayer& L = n->layers[n->conv2];
+  ursn_vscores_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
+  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
+  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  BProf ps(n, s, n->conv2, 6, 0.0, (double)N * n->lvox[0] * (16.0 + 4.0 * d.ncls), "logits");
+  return launch_logits_dense(&d, logits_out, s);
+}
+
+// ursn_backward_logits: the caller's d-logits rounded into n->dlog with the partials bhead_kernel would have carried, then the
+// unchanged backward().  The weight packs of the data gradients are those the pending forward's replay filled (same parameters).
+int bnet_backward_logits(ursn_bnet* n, const float* data, const float* dlogits, int N, float* dinput_out, hipStream_t s) {
+  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  static const bool prepack = ursn_env_on("URSN_BF16_PREPACK");
+  if (prepack && n->pack.d_jobs && n->pack_N == N) bpack_set_ctx(&n->pack);
+  n->a_data.in_f32 = n->scalar_in ? data : nullptr;
+  const BLayer& L = n->layers[n->conv2];
+  {
+    static const bool fuse = ursn_env_on("URSN_BF16_HEAD_BN_BWD");
+    double* bs = nullptr;
+    int blocks = 0;
+    n->bs_layer = -1;
+    if (fuse && n->bs_scratch && L.kout == 8 && bhead_blocks(N, n->lvox[0]) <= 16384) {
+      bs = n->bs_scratch; blocks = bhead_blocks(N, n->lvox[0]);
+      n->bs_layer = n->conv2; n->bs_blocks = blocks;
+    }
+    BProf ps(n, s, n->conv2, 6, 0.0, (double)N * n->lvox[0] * (4.0 * n->cfg.num_class + 16.0 + (bs ? 16.0 : 0.0)), "dlogits");
+    URSN_TRY(launch_dlogits_pack(dlogits, N, n->lvox[0], n->cfg.num_class, n->dlog, 8, 1, L.z, L.mean, L.rstd, bs, blocks, s));
+  }
+  URSN_TRY(backward(n, N, s));
+  if (dinput_out) {
+    const BLayer& L0 = n->layers[n->conv0];
+    BProf ps(n, s, n->conv0, 1, blayer_flops(n, L0, N), (double)N * n->lvox[0] * (2.0 * L0.kout + 4.0) + 4.0 * L0.w_n, "dinput");
+    URSN_TRY(launch_conv0_input_grad(n->cfg.ndim, n->cfg.spatial, N, 1, L0.cout, L0.dz, L0.kout, 1, n->params + L0.w_off, dinput_out, s));
+  }
+  return 0;
 }
 
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride) {

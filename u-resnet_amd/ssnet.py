@@ -794,6 +794,67 @@ class ssnet_base(object):
             return None, doc
         return [None, float(out[0]), float(out[1]), float(out[2])], doc
 
+    # ------------------------------------------------------------------------------------------
+    # external losses (not in the reference, whose one loss is part of the graph, lib/ssnet.py:57-71): the step cut open at
+    # the logits -- logits out, the caller's d(loss)/d(logits) in, gradients ADDED to the flat buffer like accum_gradients'
+    # ------------------------------------------------------------------------------------------
+    def forward_logits(self, sess, input_data, as_numpy=False):
+        """The forward pass of ``accum_gradients`` up to the logits: ``[N, *spatial, num_class]`` fp32, a device tensor by
+        default.  The head is not launched (no loss, no accuracies).  ``backward_logits`` may continue this forward as long as
+        no other run call comes in between."""
+        import torch
+        if not self._trainable:
+            raise RuntimeError('forward_logits: constructed with trainable=False')
+        fd = {'input_data': self._feed(input_data, self._data_size, 'data')}
+        n = int(fd['input_data'].shape[0])
+        self._ensure_handle(n)
+        out = torch.empty((n,) + tuple(int(d) for d in self._dims[:-1]) + (self._num_class,), dtype=torch.float32,
+                          device=self._device)
+        _lib.check(_lib.load().ursn_forward_logits(self._handle, self._ptr(fd['input_data']), n, self._ptr(out),
+                                                   self._stream(sess)))
+        self._last_feed = fd  # keep the device input alive: backward_logits reads it again (conv0's weight gradient)
+        self._mark_consumed(fd)
+        return out.cpu().numpy() if as_numpy else out
+
+    def backward_logits(self, sess, dlogits, want_input_grad=False):
+        """Backward pass from ``dlogits`` (device tensor or host array, ``[N, *spatial, num_class]``) of the forward the last
+        ``forward_logits`` ran; gradients are added to the flat buffer exactly like a step's (``zero_gradients`` /
+        ``apply_gradients`` work unchanged).  Returns ``None`` or, with ``want_input_grad``, d(loss)/d(input) ``[N, *dims]`` fp32
+        on the device.  Raises when no ``forward_logits`` is pending (another run call came in between, the batch differs)."""
+        import torch
+        if not self._trainable:
+            raise RuntimeError('backward_logits: constructed with trainable=False')
+        if self._handle is None or getattr(self, '_last_feed', None) is None:
+            raise RuntimeError('backward_logits: no forward_logits has run')
+        fd = self._last_feed
+        g = dlogits if isinstance(dlogits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(dlogits, dtype=np.float32))
+        g = g.detach().to(device=self._device, dtype=torch.float32).contiguous()
+        n = int(fd['input_data'].shape[0])
+        want = (n,) + tuple(int(d) for d in self._dims[:-1]) + (self._num_class,)
+        if tuple(g.shape) != want and tuple(g.shape) != (n, self._label_size * self._num_class):
+            raise ValueError('backward_logits: dlogits has shape %s, the pending forward_logits produced %s'
+                             % (tuple(g.shape), want))
+        din = torch.empty((n,) + tuple(int(d) for d in self._dims), dtype=torch.float32, device=self._device) \
+            if want_input_grad else None
+        _lib.check(_lib.load().ursn_backward_logits(self._handle, self._ptr(fd['input_data']), self._ptr(g), n, self._ptr(din),
+                                                    self._stream(sess)))
+        g.record_stream(torch.cuda.current_stream(self._device))
+        self._mark_consumed(fd)
+        return din
+
+    def accum_gradients_custom(self, sess, input_data, loss_fn, fetch=True):
+        """``accum_gradients`` with the caller's objective: ``loss = loss_fn(logits)`` on the logits as a torch autograd leaf
+        (``[N, *spatial, num_class]``, device), ``loss.backward()``, then ``backward_logits(logits.grad)``.  Returns
+        ``([None, loss], ['', 'loss'])`` (``None`` results with ``fetch=False``: nothing is read back)."""
+        logits = self.forward_logits(sess, input_data).requires_grad_(True)
+        loss = loss_fn(logits)
+        loss.backward()
+        self.backward_logits(sess, logits.grad)
+        doc = ['', 'loss']
+        if not fetch:
+            return None, doc
+        return [None, float(loss.detach().item())], doc
+
     def last_feed(self):
         """Device-resident tensors of the most recent accum_gradients / inference_labels call (valid until two more
         batches have been fed): lets a caller re-run them (summary) without another host copy."""
