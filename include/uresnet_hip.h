@@ -486,6 +486,60 @@ int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, float* logi
  * Recorded as pass 6 "dlogits" and pass 1 "dinput" (layer conv0) when profiling. */
 int ursn_backward_logits(ursn_net* net, const float* data, const float* dlogits, int32_t n, float* dinput_out, void* stream);
 
+/* ---- cube-symmetry augmentation and test-time averaging (symmetry.hip) --------------------------------------------------
+ * Appended functions and one struct only: URSN_ABI_VERSION stays 9.
+ * What users of a 3-D segmentation trainer do on the host before the feed -- flip and transpose the (data, label, weight)
+ * volumes -- and, on the analysis side, map the score volumes of several symmetric views back before averaging them.  An
+ * operation is a small integer code; for one event x of shape [*spatial, C] it means
+ *     out = np.flip(np.transpose(x, P[code >> ndim] + (ndim,)), axis=[a for a in range(ndim) if (code >> a) & 1])
+ * with P the axis permutations in lexicographic order (3-D: (0,1,2),(0,2,1),(1,0,2),(1,2,0),(2,0,1),(2,1,0); 2-D: (0,1),(1,0)):
+ * 48 codes in 3-D, 8 in 2-D, code 0 the identity, bit a flips OUTPUT axis a.  Equivalently input voxel i lands at output voxel o
+ * with o[a] = f_a(i[P[a]]), f_a(t) = spatial[a] - 1 - t if bit a is set, else t.  A code is valid for a shape iff
+ * spatial[P[a]] == spatial[a] for every a (the output then has the input's shape); any other code is refused.
+ * The passes are pure data movement: output bits equal input bits (NaN payloads, -0.0).  Every call below enqueues only and
+ * never synchronises, uses no atomics and no scratch, and its results depend only on its arguments; null, misaligned,
+ * overlapping, out-of-domain or invalid-code arguments are refused with a message before anything is launched.  The codes are a
+ * HOST array, validated on the host, and travel to the kernel as launch arguments (one byte per event: no H2D copy), which is
+ * why these calls take n <= 1024. */
+typedef struct ursn_sym_desc {
+  int32_t ndim, spatial[3], n, channels;  /* ndim 2 | 3 (spatial[2] unused in 2-D); channels 1..8, channel-last;
+                                           * prod(spatial) * channels < 2^31 */
+  const int32_t* ops;                     /* HOST array, one code per event */
+} ursn_sym_desc;
+
+/* Host helpers, no device access: the number of codes (0 for ndim outside {2, 3}); whether `code` is valid for the shape (0 | 1);
+ * the inverse code; the code of "b after a" (apply a, then b).  inverse / compose return -1 for a code outside [0, count). */
+int ursn_sym_count(int32_t ndim);
+int ursn_sym_valid(int32_t ndim, const int32_t* spatial, int32_t code);
+int ursn_sym_inverse(int32_t ndim, int32_t code);
+int ursn_sym_compose(int32_t ndim, int32_t a, int32_t b);
+
+/* Up to three tensors [n, *spatial, channels] fp32 (the data / label / weight triple) permuted in ONE launch:
+ * dst_k[e] = op[e](src_k[e]).  Later pairs may be NULL (a pair is either both set or both NULL); no dst may overlap any src or
+ * another dst.  Pointers need 4-byte alignment only.  Events whose op keeps the last axis last copy whole rows (reversed when
+ * flipped, 16-byte accesses where both sides are 16-byte aligned); events whose op moves the last axis transpose 32 x 32 tiles
+ * through padded LDS, so that global reads and writes are both contiguous along the fastest axis of their tensor. */
+int ursn_sym_apply(const ursn_sym_desc* d, const float* src0, float* dst0, const float* src1, float* dst1, const float* src2,
+                   float* dst2, void* stream);
+
+/* dst = ((first ? 0 : dst) + op(src)) * scale, one fp32 add then one fp32 multiply, same access pattern as ursn_sym_apply: the
+ * back-mapping step of test-time averaging (the caller passes the INVERSE codes of the views).  first != 0: dst is not read. */
+int ursn_sym_accumulate(const ursn_sym_desc* d, const float* src, float* dst, int32_t first, float scale, void* stream);
+
+/* ursn_voxels_to_dense with the scatter writing list entry i at its image o under ops[event] (a bijection of the event's voxels, so
+ * no two entries share an address; an index outside [0, voxels) is skipped).  The fill pass is ursn_voxels_to_dense's.
+ * prod(spatial) must equal b->voxels; ops is a HOST array of b->n <= 1024 codes. */
+int ursn_voxels_to_dense_sym(const ursn_voxel_batch* b, int32_t ndim, const int32_t* spatial, const int32_t* ops, float* data,
+                             float* label, float* weight, void* stream);
+
+/* The gather side: index_out[m] = image of index[m] under ops[event] for the entries [offsets[e], offsets[e+1]) of event e
+ * (offsets [n+1], index / index_out [M]: device pointers; index_out may not overlap index).  An index outside [0, prod(spatial))
+ * is copied unchanged.  The list that comes out is NOT sorted: it is in the order of `index`, entry m still belongs to the voxel
+ * entry m came in as.  ursn_scores_at_voxels and ursn_infer_voxels need distinct indices per event only, not sorted ones, so
+ * scores gathered on a transformed volume at index_out line up with the original list. */
+int ursn_voxel_index_sym(int32_t ndim, const int32_t* spatial, int32_t n, const int32_t* ops, const int64_t* offsets,
+                         const int32_t* index, int32_t* index_out, void* stream);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

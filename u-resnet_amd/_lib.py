@@ -71,6 +71,11 @@ class ursn_class_stats_out(C.Structure):
                 ("score_sq", C.c_void_p)]
 
 
+class ursn_sym_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("channels", C.c_int32),
+                ("ops", C.POINTER(C.c_int32))]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -138,6 +143,15 @@ _SIGS = {
                                         _P, _P, _P]),
     "ursn_forward_logits": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "ursn_backward_logits": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    "ursn_sym_count": (C.c_int, [C.c_int32]),
+    "ursn_sym_valid": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "ursn_sym_inverse": (C.c_int, [C.c_int32, C.c_int32]),
+    "ursn_sym_compose": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "ursn_sym_apply": (C.c_int, [C.POINTER(ursn_sym_desc), _P, _P, _P, _P, _P, _P, _P]),
+    "ursn_sym_accumulate": (C.c_int, [C.POINTER(ursn_sym_desc), _P, _P, C.c_int32, C.c_float, _P]),
+    "ursn_voxels_to_dense_sym": (C.c_int, [C.POINTER(ursn_voxel_batch), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           _P, _P, _P, _P]),
+    "ursn_voxel_index_sym": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

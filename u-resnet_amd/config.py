@@ -64,6 +64,17 @@ class ssnet_config(object):
     # accuracies, per-class pixel count / accuracy / score mean / score std, reduced on the device); '' = off.  Ignored with
     # TRAIN; refused together with SPARSE_SCORES
     ANA_CSV = ''
+    # not in the reference (its users flip / transpose the volumes on the host before the feed): '' | 'flip' | 'cube' = every
+    # training minibatch is fed through one random symmetry operation per event (symmetry.py: 'flip' the axis flips, 'cube' every
+    # flip / axis permutation the image shape admits), applied on the device to data, label and weight alike
+    # (ursn_sym_apply, with SPARSE_IO ursn_voxels_to_dense_sym).  The operations are a function of (AUGMENT_SEED, iteration,
+    # minibatch, rank) alone, so a resumed run repeats them.  '' = off
+    AUGMENT = ''
+    AUGMENT_SEED = 0
+    # not in the reference: a non-empty list of symmetry codes = ana_step averages the softmax over these views of every event
+    # (ssnet_base.inference_tta, with SPARSE_IO inference_voxel_scores_tta); [0] is the plain pass, [] = off.  Ignored with
+    # TRAIN; refused together with ANA_CSV
+    ANA_TTA = []
 
     def __init__(self):
         pass
@@ -104,6 +115,12 @@ class ssnet_config(object):
                 print('Incompatible type: %s' % line)
                 raise TypeError(line)
             if key == 'PRECISION' and value not in ('fp32', 'bf16'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'AUGMENT' and value not in ('', 'flip', 'cube'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'ANA_TTA' and not all(type(c) is int and 0 <= c < 48 for c in value):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             setattr(self, key, value)

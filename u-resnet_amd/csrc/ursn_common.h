@@ -311,6 +311,8 @@ int launch_head(const HeadArgs& a, hipStream_t s);
 // beyond m_total are never written, 0 launches nothing).  Validates like the C entry point.
 int launch_vscores(const ursn_vscores_desc* d, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, int64_t m_total,
                    hipStream_t s);
+// ursn_voxels_to_dense's argument checks and fill pass (voxel_io.hip), shared with ursn_voxels_to_dense_sym (symmetry.hip)
+int launch_voxel_fill(const ursn_voxel_batch* b, float* data, float* label, float* weight, hipStream_t s);
 // Per-event class statistics (ana_stats.hip): ursn_class_stats on a stream.  Validates like the C entry point.
 int launch_cstats(const ursn_vscores_desc* d, const float* label, const ursn_class_stats_out* out, void* scratch,
                   size_t scratch_bytes, hipStream_t s);

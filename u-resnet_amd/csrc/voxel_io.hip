@@ -86,7 +86,8 @@ static int check_dims(const char* who, int32_t n, int64_t voxels) {
   return 0;
 }
 
-extern "C" int ursn_voxels_to_dense(const ursn_voxel_batch* b, float* data, float* label, float* weight, void* stream) {
+// ursn_voxels_to_dense's argument checks and its fill pass; ursn_voxels_to_dense_sym (symmetry.hip) shares them
+int launch_voxel_fill(const ursn_voxel_batch* b, float* data, float* label, float* weight, hipStream_t s) {
   URSN_REQUIRE(b && data, "voxels_to_dense: null batch or data output");
   URSN_TRY(check_dims("voxels_to_dense", b->n, b->voxels));
   URSN_REQUIRE(b->offsets && b->index && b->value, "voxels_to_dense: null offsets / index / value");
@@ -94,7 +95,6 @@ extern "C" int ursn_voxels_to_dense(const ursn_voxel_batch* b, float* data, floa
   URSN_REQUIRE((weight != nullptr) == (b->weight != nullptr), "voxels_to_dense: weight list and weight output must come together");
   URSN_REQUIRE(!weight || b->bg_weight, "voxels_to_dense: null bg_weight with a weight output");
   URSN_REQUIRE((((uintptr_t)data | (uintptr_t)label | (uintptr_t)weight) & 3) == 0, "voxels_to_dense: outputs must be 4-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
   VoxFillArgs f;
   f.out[0] = data, f.out[1] = label, f.out[2] = weight;
   f.bg = b->bg_weight, f.n = b->n, f.V = b->voxels;
@@ -104,6 +104,12 @@ extern "C" int ursn_voxels_to_dense(const ursn_voxel_batch* b, float* data, floa
   ursn_note_kernel("voxel_fill");
   hipLaunchKernelGGL(voxel_fill_kernel, dim3((unsigned)fx, (unsigned)b->n, 3), dim3(256), 0, s, f);
   URSN_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ursn_voxels_to_dense(const ursn_voxel_batch* b, float* data, float* label, float* weight, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  URSN_TRY(launch_voxel_fill(b, data, label, weight, s));
   // the list length lives on the device (offsets[n]): a grid sized for the usual occupancy, grid-stride for a denser event
   int64_t sx = cdiv64(b->voxels, 256 * 8);
   sx = sx < 1 ? 1 : sx > 1024 ? 1024 : sx;

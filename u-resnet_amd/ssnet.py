@@ -523,6 +523,142 @@ class ssnet_base(object):
         fd['input_weight'] = out
 
     # ------------------------------------------------------------------------------------------
+    # cube-symmetry augmentation and test-time averaging on the device (not in the reference, whose users flip and transpose
+    # the volumes with numpy before the feed; codes and their numpy definition: symmetry.py)
+    # ------------------------------------------------------------------------------------------
+    def _sym_spatial(self):
+        return (ctypes.c_int32 * 3)(*([int(d) for d in self._dims[:-1]] + [1])[:3])
+
+    @staticmethod
+    def _sym_ops(codes, n):
+        """One code per event as the HOST int32 array the library reads; it validates the codes against the shape itself."""
+        codes = [int(c) for c in codes]
+        if len(codes) != n:
+            raise ValueError('symmetry: %d codes for a batch of %d events' % (len(codes), n))
+        return (ctypes.c_int32 * n)(*codes)
+
+    def _sym_desc(self, ops, n, channels):
+        d = _lib.ursn_sym_desc()
+        d.ndim = len(self._dims) - 1
+        for i in range(d.ndim):
+            d.spatial[i] = int(self._dims[i])
+        d.n, d.channels = n, channels
+        d.ops = ctypes.cast(ops, ctypes.POINTER(ctypes.c_int32))
+        return d
+
+    def _apply_symmetry(self, fd, symmetry, sess):
+        """``fd`` as ``_feed`` left it -> the same roles with event i under operation ``symmetry[i]``, written by ``ursn_sym_apply``
+        on the compute stream (which ``_feed`` has made wait for the copies) into a second set of feed slots, two buffers per
+        role used alternately and registered like the voxel expansion's, so ``last_feed``, ``_mark_consumed`` and the in-place
+        weight normalisation treat them like fed tensors.  With one input channel the whole triple is ONE launch."""
+        import torch
+        self._copy_stream()                         # the slot table lives with the copy stream
+        n = int(fd['input_data'].shape[0])
+        ops = self._sym_ops(symmetry, n)
+        out = {}
+        for key, t in fd.items():
+            ds = self._feed_slots.setdefault('sym_' + key[len('input_'):], ssnet_base._FeedSlot())
+            k = ds.turn
+            ds.turn ^= 1
+            if ds.dev[k] is None or ds.dev[k].shape[0] < n:
+                ds.dev[k] = torch.empty((n, int(t.shape[1])), dtype=torch.float32, device=self._device)
+                ds.consumed[k] = None
+            out[key] = ds.dev[k][:n]
+        lib, cin = _lib.load(), int(self._dims[-1])
+        rest = [k for k in ('input_label', 'input_weight') if k in fd]
+        calls = [(cin, ['input_data'])] + ([(1, rest)] if rest else [])
+        if cin == 1:
+            calls = [(1, ['input_data'] + rest)]
+        for channels, keys in calls:
+            d = self._sym_desc(ops, n, channels)
+            pairs = []
+            for k in keys:
+                pairs += [self._ptr(fd[k]), self._ptr(out[k])]
+            pairs += [None] * (6 - len(pairs))
+            _lib.check(lib.ursn_sym_apply(ctypes.byref(d), *(pairs + [self._stream(sess)])))
+        self._mark_consumed(fd)                     # the copies' buffers are free once the permutation has read them
+        return out
+
+    def inference_tta(self, sess, input_data, codes, as_numpy=True):
+        """Test-time averaging of ``inference`` over symmetric views: for each code of ``codes`` the data is permuted on the
+        device (``ursn_sym_apply``), the forward pass and softmax run, and ``ursn_sym_accumulate`` maps the score volume back with
+        the inverse code into one result buffer.  Returns ``mean_k inv_k(softmax_k)`` [N, *spatial, num_class], formed as an fp32
+        left-to-right sum in list order and then multiplied by ``np.float32(1 / K)``; only the result crosses PCIe."""
+        import torch
+        from . import symmetry as S
+        codes = [int(c) for c in codes]
+        if not codes:
+            raise ValueError('inference_tta: no codes')
+        nd, K, C = len(self._dims) - 1, len(codes), self._num_class
+        fd = {'input_data': self._feed(input_data, self._data_size, 'data')}
+        n = int(fd['input_data'].shape[0])
+        self._ensure_handle(n)
+        lib, stream = _lib.load(), self._stream(sess)
+        view = torch.empty((n, self._data_size), dtype=torch.float32, device=self._device)
+        sm = torch.empty((n,) + tuple(int(d) for d in self._dims[:-1]) + (C,), dtype=torch.float32, device=self._device)
+        res = torch.empty_like(sm)
+        out = (ctypes.c_float * 2)()
+        for k, code in enumerate(codes):
+            ops = self._sym_ops([code] * n, n)
+            d = self._sym_desc(ops, n, int(self._dims[-1]))
+            _lib.check(lib.ursn_sym_apply(ctypes.byref(d), self._ptr(fd['input_data']), self._ptr(view), None, None, None, None,
+                                          stream))
+            _lib.check(lib.ursn_infer(self._handle, self._ptr(view), None, n, self._ptr(sm), out, stream))
+            back = self._sym_ops([S.inverse(nd, code)] * n, n)
+            d = self._sym_desc(back, n, C)
+            _lib.check(lib.ursn_sym_accumulate(ctypes.byref(d), self._ptr(sm), self._ptr(res), int(k == 0),
+                                               float(np.float32(1.0 / K)) if k == K - 1 else 1.0, stream))
+        self._mark_consumed(fd)
+        return res.cpu().numpy() if as_numpy else res
+
+    def inference_voxel_scores_tta(self, sess, voxels, codes):
+        """``inference_voxel_scores`` averaged over symmetric views.  Each view is expanded from the list by
+        ``ursn_voxels_to_dense_sym``; ``ursn_voxel_index_sym`` gives the (unsorted) positions of the event's own voxels inside the
+        view and ``ursn_infer_voxels`` gathers the scores there, so entry m of every view belongs to the voxel entry m came in as
+        and no volume has to be mapped back.  The scores [M, num_class] are averaged on the device (fp32 left-to-right sum in list
+        order, then times ``np.float32(1 / K)``); ``pred`` is the lowest-index argmax and ``ana`` the reference's rule
+        (lib/ssnet_trainval.py:285-287) on the averaged scores.  Nothing dense crosses PCIe.  Returns a dict of per-event lists
+        ``index`` / ``scores`` / ``pred`` / ``ana`` like ``inference_voxel_scores``."""
+        import torch
+        self._require_single_channel('inference_voxel_scores_tta')
+        codes = [int(c) for c in codes]
+        if not codes:
+            raise ValueError('inference_voxel_scores_tta: no codes')
+        if self._num_class < 3:
+            raise ValueError('inference_voxel_scores_tta: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
+        lib, nd, K, C = _lib.load(), len(self._dims) - 1, len(codes), self._num_class
+        n, off = voxels.n, voxels.offsets
+        M = int(off[-1])
+        remapped = torch.empty(max(M, 1), dtype=torch.int32, device=self._device)
+        total = None
+        for code in codes:
+            fd = self._feed_voxels(voxels, with_label=False, with_weight=False, symmetry=[code] * n)
+            self._ensure_handle(n)
+            slot, turn, d_offsets, d_index = self._fed_list
+            _lib.check(lib.ursn_voxel_index_sym(nd, self._sym_spatial(), n, self._sym_ops([code] * n, n), ctypes.c_void_p(d_offsets),
+                                                ctypes.c_void_p(d_index), self._ptr(remapped), self._stream(sess)))
+            scores = torch.empty((max(M, 1), C), dtype=torch.float32, device=self._device)
+            _lib.check(lib.ursn_infer_voxels(self._handle, self._ptr(fd['input_data']), None, n, ctypes.c_void_p(d_offsets),
+                                             self._ptr(remapped), M, self._ptr(scores), None, None, None, self._stream(sess)))
+            self._last_feed = fd
+            self._mark_consumed(fd)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self._device))
+            slot.consumed[turn] = done             # offsets / index have been read: the list buffer is free again
+            total = scores if total is None else total + scores
+        avg = (total * float(np.float32(1.0 / K)))[:M]
+        classes = torch.arange(C, device=self._device)
+        pred = torch.where(avg == avg.max(dim=1, keepdim=True).values, classes, C).min(dim=1).values.to(torch.uint8)
+        shower, track = avg[:, 1], avg[:, 2]
+        rule = (shower > track).to(torch.uint8) + (track >= shower).to(torch.uint8) * 2
+        ana = rule * (torch.from_numpy(voxels.value[:M]).to(self._device) > 1.0).to(torch.uint8)
+        res = {'index': [voxels.index[off[i]:off[i + 1]].copy() for i in range(n)]}
+        for name, t in (('scores', avg), ('pred', pred), ('ana', ana)):
+            host = t.cpu().numpy()
+            res[name] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
+        return res
+
+    # ------------------------------------------------------------------------------------------
     # voxel-list feed (not in the reference: larcv fills dense arrays; see VoxelBatch)
     # ------------------------------------------------------------------------------------------
     def _require_single_channel(self, what):
@@ -530,14 +666,16 @@ class ssnet_base(object):
             raise ValueError('%s: voxel lists carry one value per voxel, so dims[-1] must be 1 (dims = %s)'
                              % (what, [int(d) for d in self._dims]))
 
-    def _feed_voxels(self, vb, with_label=True, with_weight=None):
+    def _feed_voxels(self, vb, with_label=True, with_weight=None, symmetry=None):
         """VoxelBatch -> the dense device tensors of ``feed_dict``, without the dense arrays ever crossing PCIe.
 
         Every array of the batch is packed into ONE page-locked staging buffer and travels in ONE copy on the copy stream,
         under the discipline of ``_feed``: two device buffers used alternately, a buffer overwritten only after the launch
         that last read it (``consumed``), the call returning once the copy is done (``copied``) and never waiting for compute.
         ``ursn_voxels_to_dense`` then expands the list on the compute stream into per-role device tensors (two sets,
-        alternating, registered as feed slots so ``last_feed`` / ``_mark_consumed`` treat them like fed tensors)."""
+        alternating, registered as feed slots so ``last_feed`` / ``_mark_consumed`` treat them like fed tensors).  With
+        ``symmetry`` (one code per event, symmetry.py) ``ursn_voxels_to_dense_sym`` expands instead: every list entry is written at
+        its image under the event's operation."""
         import torch
         self._require_single_channel('_feed_voxels')
         vb.validate()
@@ -608,8 +746,15 @@ class ssnet_base(object):
         b.label = base + at['label'] if with_label else None
         b.weight = base + at['weight'] if with_weight else None
         b.bg_weight = base + at['bg_weight'] if with_weight else None
-        _lib.check(_lib.load().ursn_voxels_to_dense(ctypes.byref(b), self._ptr(fd['input_data']), self._ptr(fd.get('input_label')),
-                                                    self._ptr(fd.get('input_weight')), self._stream(None)))
+        if symmetry is None:
+            _lib.check(_lib.load().ursn_voxels_to_dense(ctypes.byref(b), self._ptr(fd['input_data']),
+                                                        self._ptr(fd.get('input_label')), self._ptr(fd.get('input_weight')),
+                                                        self._stream(None)))
+        else:
+            _lib.check(_lib.load().ursn_voxels_to_dense_sym(ctypes.byref(b), len(self._dims) - 1, self._sym_spatial(),
+                                                            self._sym_ops(symmetry, n), self._ptr(fd['input_data']),
+                                                            self._ptr(fd.get('input_label')), self._ptr(fd.get('input_weight')),
+                                                            self._stream(None)))
         done = torch.cuda.Event()
         done.record(cur)
         slot.consumed[i] = done                    # the list buffer is free once the expansion has read it
@@ -617,14 +762,16 @@ class ssnet_base(object):
         self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
         return fd
 
-    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False):
+    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None):
         """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure.  ``normalize_weight``: the expanded dense
         weight tensor is normalised per event on the device (``_normalize_fed_weight``), the same definition of the sum as the
-        dense feed's; ``voxels.weight`` / ``bg_weight`` are not written and ``VoxelBatch.normalize_weights`` is not needed."""
+        dense feed's; ``voxels.weight`` / ``bg_weight`` are not written and ``VoxelBatch.normalize_weights`` is not needed.
+        ``symmetry``: as in ``accum_gradients``; the operation is index arithmetic inside the expansion's scatter and the list
+        is neither rewritten nor re-sorted."""
         if not self._trainable:
             raise RuntimeError('accum_gradients_voxels: constructed with trainable=False')
         self._require_single_channel('accum_gradients_voxels')
-        fd = self._feed_voxels(voxels)
+        fd = self._feed_voxels(voxels, symmetry=symmetry)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
@@ -772,13 +919,19 @@ class ssnet_base(object):
         _lib.check(_lib.load().ursn_zero_grad(self._handle, self._stream(sess)))
         return [None]
 
-    def accum_gradients(self, sess, input_data, input_label, input_weight=None, fetch=True, normalize_weight=False):
+    def accum_gradients(self, sess, input_data, input_label, input_weight=None, fetch=True, normalize_weight=False,
+                        symmetry=None):
         """``normalize_weight`` (not in the reference, whose driver normalises on the host, lib/ssnet_trainval.py:173): the fed
         weights are divided by their per-event sums on the device before the step (``_normalize_fed_weight``); ``input_weight``
-        itself, host array or device tensor, is left as it is."""
+        itself, host array or device tensor, is left as it is.  ``symmetry`` (not in the reference, whose users flip and
+        transpose on the host): a sequence of one code per event (symmetry.py); the step then sees data, label and weight of event
+        i under operation ``symmetry[i]``, permuted on the device (``_apply_symmetry``) before the weight normalisation.  None:
+        the call is made exactly as without the keyword."""
         if not self._trainable:
             raise RuntimeError('accum_gradients: constructed with trainable=False')
         fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
+        if symmetry is not None:
+            fd = self._apply_symmetry(fd, symmetry, sess)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])

@@ -32,6 +32,7 @@ import time
 
 import numpy as np
 
+from . import symmetry
 from .config import ssnet_config
 from .ssnet import HipSession, ana_csv_header, ana_csv_row
 from .synthetic_io import synthetic_threadio
@@ -143,6 +144,9 @@ class ssnet_trainval(object):
         if cfg.ANA_CSV and not cfg.TRAIN and cfg.SPARSE_SCORES:
             raise ValueError('ANA_CSV cannot be combined with SPARSE_SCORES: the per-class statistics run over every voxel, '
                              'SPARSE_SCORES returns scores at the listed voxels only')
+        if cfg.ANA_TTA and not cfg.TRAIN and cfg.ANA_CSV:
+            raise ValueError('ANA_TTA cannot be combined with ANA_CSV: the per-class statistics are reduced on the device from the '
+                             'logits of ONE forward pass, a test-time average only exists as scores after several passes')
         self._input_main = self._open_stream('MainIO', cfg.MAIN_INPUT_CONFIG, cfg.MINIBATCH_SIZE)
         if cfg.TEST_INPUT_CONFIG:
             self._input_test = self._open_stream('TestIO', cfg.TEST_INPUT_CONFIG, cfg.TEST_BATCH_SIZE)
@@ -163,6 +167,9 @@ class ssnet_trainval(object):
         self._net.construct(trainable=cfg.TRAIN, use_weight=cfg.USE_WEIGHTS, seed=cfg.TF_RANDOM_SEED,
                             precision=cfg.PRECISION, **extra)
         self._sess = HipSession()
+        bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
+        if bad and not cfg.TRAIN:
+            raise ValueError('ANA_TTA: codes %s are not symmetry operations of the image shape %s' % (bad, list(dims[:-1])))
 
         self._saved = collections.deque()
         if _is_rank0():
@@ -233,6 +240,17 @@ class ssnet_trainval(object):
         DEVICE_WEIGHT_NORM False: those calls are then made exactly as before."""
         return {'normalize_weight': True} if self._cfg.DEVICE_WEIGHT_NORM and self._cfg.USE_WEIGHTS else {}
 
+    def _sym_kw(self, minibatch, n):
+        """Keyword of the accumulate calls.  Empty with the default AUGMENT '': those calls are then made exactly as before.  Else
+        one symmetry code per event, a function of (AUGMENT_SEED, iteration, minibatch, rank) alone: a resumed run repeats the
+        operations, every rank draws its own."""
+        c = self._cfg
+        if not c.AUGMENT:
+            return {}
+        d = _dist()
+        codes = symmetry.group(c.AUGMENT, [int(x) for x in self._net._dims[:-1]])
+        return {'symmetry': symmetry.draw(c.AUGMENT_SEED, self._iteration, minibatch, d.get_rank() if d is not None else 0, n, codes)}
+
     def _run_minibatches(self, want_metrics):
         """zero -> NUM_MINIBATCHES x accumulate -> apply.  Returns the per-minibatch metrics [M, 3] when asked for
         (each read is a stream synchronisation), else None; in both cases ``self._last_minibatch`` holds the
@@ -241,13 +259,14 @@ class ssnet_trainval(object):
         rows = []
         norm = self._norm_kw()
         net.zero_gradients(self._sess)
-        for _ in range(c.NUM_MINIBATCHES):
+        for minibatch in range(c.NUM_MINIBATCHES):
             if c.SPARSE_IO:
-                res, doc = net.accum_gradients_voxels(self._sess, self._pull_voxels(self._input_main), fetch=want_metrics, **norm)
+                vb = self._pull_voxels(self._input_main)
+                res, doc = net.accum_gradients_voxels(self._sess, vb, fetch=want_metrics, **norm, **self._sym_kw(minibatch, vb.n))
             else:
                 data, label, weight = self._pull(self._input_main, c.KEYWORD_DATA, c.KEYWORD_LABEL, c.KEYWORD_WEIGHT)
                 res, doc = net.accum_gradients(sess=self._sess, input_data=data, input_label=label, input_weight=weight,
-                                               fetch=want_metrics, **norm)
+                                               fetch=want_metrics, **norm, **self._sym_kw(minibatch, len(data)))
             # the copy has completed, the kernels are queued: the IO may refill this buffer while they run
             self._descr_metrics = doc[1:]
             if want_metrics:
@@ -443,10 +462,71 @@ class ssnet_trainval(object):
         self._advance_main()
         return result
 
+    def _ana_step_tta(self, batch_mode):
+        """ANA_TTA: the scores are the mean over the listed symmetric views of every event, mapped back on the device
+        (``inference_tta``; with SPARSE_IO ``inference_voxel_scores_tta``, which gathers every view at the event's own voxels).
+        Labels, records and accuracies are formed from the averaged scores by the rules of ``ana_step`` /
+        ``_ana_step_voxel_scores``.  With SPARSE_IO only the listed voxels have scores: ``acc_nonzero`` (over data > 0, which
+        all lie in the list) is exact, ``acc_all`` is None."""
+        c, io, net = self._cfg, self._input_main, self._net
+        codes = list(c.ANA_TTA)
+        if c.SPARSE_IO:
+            vb = io.fetch_voxels()
+            entries = io.fetch_entries()
+            r = net.inference_voxel_scores_tta(self._sess, vb, codes)
+            lit = vb.value > 0
+            hit = np.concatenate(r['pred']).astype(np.float32) == vb.label
+            acc_all, acc_nonzero = None, float(hit[lit].sum()) / max(int(lit.sum()), 1)
+            if self._output:
+                for i in range(vb.n):
+                    keep = r['ana'][i] != 0
+                    print('Entry', entries[i], 'Acc', acc_nonzero)
+                    np.save(self._output, r['index'][i][keep])
+                    np.save(self._output, r['ana'][i][keep])
+                    np.save(self._output, r['scores'][i][keep])
+                self._output.flush()
+            result = None
+            if not batch_mode:
+                off = vb.offsets
+                events = [{'index': r['index'][i], 'value': vb.value[off[i]:off[i + 1]].copy(),
+                           'label': vb.label[off[i]:off[i + 1]].copy(), 'scores': r['scores'][i], 'pred': r['pred'][i]}
+                          for i in range(vb.n)]
+                result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
+            self._advance_main()
+            return result
+        batch_data = io.fetch_data(c.KEYWORD_DATA).data()
+        batch_label = io.fetch_data(c.KEYWORD_LABEL).data()
+        entries = io.fetch_entries()
+        softmax = net.inference_tta(self._sess, batch_data, codes)
+        hit = softmax.argmax(axis=-1) == np.asarray(batch_label).reshape(softmax.shape[:-1])
+        acc_all, acc_nonzero = float(hit.mean()), None
+        if softmax.size == np.asarray(batch_data).size * softmax.shape[-1]:   # one input channel: data > 0 names voxels
+            lit = np.asarray(batch_data).reshape(softmax.shape[:-1]) > 0
+            acc_nonzero = float(hit[lit].sum()) / max(int(lit.sum()), 1)
+        if self._output:
+            # lib/ssnet_trainval.py:285-287 on the averaged scores
+            shower, track = softmax[..., 1], softmax[..., 2]
+            labels = ((shower > track) * 1.0 + (track >= shower) * 2.0) * (np.asarray(batch_data).reshape(shower.shape) > 1.0)
+            for i in range(labels.shape[0]):
+                print('Entry', entries[i], 'Acc', acc_nonzero)
+                np.save(self._output, labels[i].astype(np.float32))
+            self._output.flush()
+        result = None
+        if not batch_mode:
+            img_shape = list(softmax.shape)
+            img_shape[-1] = -1
+            result = {'entries': np.array(entries), 'input': np.array(batch_data).reshape(img_shape),
+                      'label': np.array(batch_label).reshape(img_shape), 'softmax': softmax,
+                      'acc_all': acc_all, 'acc_nonzero': acc_nonzero}
+        self._advance_main()
+        return result
+
     def ana_step(self, batch_mode=False):
         self._iteration += 1
         if self._csv:
             return self._ana_step_csv(batch_mode)
+        if self._cfg.ANA_TTA:
+            return self._ana_step_tta(batch_mode)
         if self._cfg.SPARSE_IO:
             return self._ana_step_voxels(batch_mode)
         c, io = self._cfg, self._input_main
