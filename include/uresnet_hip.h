@@ -154,7 +154,8 @@ int ursn_tensor(const ursn_net* net, const char* name, float** ptr, int64_t* vox
 /* Per-launch timing with HIP events recorded on the launch stream (bench.py roofline leg; the
  * reference has no counterpart: lib/ssnet_trainval.py:48-49 only reports peak bytes).
  * pass: 0 conv fwd, 1 conv dgrad, 2 conv wgrad, 3 bn stats, 4 bn apply, 5 bn backward, 6 head (the dense head records
- * kernel "head" / "bhead", the gather head of ursn_infer_voxels "vscores", the statistics of ursn_infer_stats "cstats"). */
+ * kernel "head" / "bhead", the gather head of ursn_infer_voxels "vscores", the statistics of ursn_infer_stats "cstats"),
+ * 7 BatchNorm moving statistics ("bn_moving_update", "bn_frozen_load": one launch for all layers). */
 typedef struct ursn_prof_rec {
   char kernel[48];
   char layer[96];
@@ -539,6 +540,47 @@ int ursn_voxels_to_dense_sym(const ursn_voxel_batch* b, int32_t ndim, const int3
  * scores gathered on a transformed volume at index_out line up with the original list. */
 int ursn_voxel_index_sym(int32_t ndim, const int32_t* spatial, int32_t n, const int32_t* ops, const int64_t* offsets,
                          const int32_t* index, int32_t* index_out, void* stream);
+
+/* ---- BatchNorm moving statistics (bn_moving.hip) -------------------------------------------------------------------------
+ * Appended functions only: URSN_ABI_VERSION stays 9.
+ * The part of slim.batch_norm the reference leaves dead (is_training is never False and UPDATE_OPS never run): per BatchNorm layer
+ * moving_mean[C] (initial 0) and moving_variance[C] (initial 1) in fp32, maintained by assign_moving_average without zero-debias,
+ *     m <- m - momentum * (m - x),    momentum = 1 - decay (slim default decay 0.999),
+ * x = the layer's batch mean, respectively its BIASED batch variance v = max(1 / (rstd * rstd) - eps, 0) recovered in fp64 from the
+ * fp32 rstd the forward stores.  The whole update is fp64 with every operation rounded on its own (no FMA contraction) and rounded
+ * to fp32 once: np.float32(m - mu * (m - x)) on float64 operands gives the same bits.
+ * The moving buffer is caller-owned like `params`: 2 * sum(cout) floats, layer by layer in ursn_query_layer order, each layer
+ * [moving_mean[cout] | moving_variance[cout]], unpadded.  It is not part of the workspace. */
+
+/* Floats of the moving buffer of a configuration (2 * sum of cout over ursn_query_layer); no device access. */
+int ursn_bn_moving_size(const ursn_config* cfg, int64_t* out);
+
+/* Attaches the caller's buffer (NULL detaches; detaching while frozen is refused).  Nothing is launched, the buffer is not read. */
+int ursn_bn_attach(ursn_net* net, float* moving);
+
+/* Folds the batch statistics of the handle's LAST forward (any run call, both plans) into the attached buffer: ONE launch for all
+ * layers on `stream`, enqueued only.  The forward joins its side stream before it returns, so a launch on the stream the run call
+ * used is ordered after every writer of a layer's mean / rstd and before the next forward overwrites them.  Refused when no buffer
+ * is attached, no forward has run, the last forward was frozen, or momentum lies outside [0, 1]. */
+int ursn_bn_update(ursn_net* net, double momentum, void* stream);
+
+/* The same kernel on flat contiguous vectors of `count` channels (mean / rstd in, moving_mean / moving_variance updated in place),
+ * for tests and callers without a handle.  Null or misaligned pointers, count outside [1, 2^31), momentum outside [0, 1] and
+ * eps <= 0 are refused before any device access.  One launch, enqueued only. */
+int ursn_bn_moving_update(const float* mean, const float* rstd, float* moving_mean, float* moving_variance, int64_t count,
+                          double momentum, float eps, void* stream);
+
+/* on != 0: every forward-only entry (ursn_infer, ursn_infer_labels, ursn_infer_voxels, ursn_infer_stats, ursn_eval) normalises
+ * every layer with the moving statistics, y = (z - moving_mean) * (1 / sqrt(moving_variance + eps)) + beta with the reciprocal
+ * root formed like the kernels' own finalise forms rstd (fp64, rounded to fp32): ONE launch at the start of the call writes every
+ * layer's mean / rstd vectors (pad lanes 0) from the buffer, and the conv kernels' statistics finalise is pointed at a scratch pair
+ * nobody reads, so every consumer (BatchNorm passes, normalise-on-load, the heads, ursn_tensor's :mean / :rstd) sees the moving
+ * values.  The statistics reductions inside the conv kernels still run.  While frozen, ursn_accum_step, ursn_forward_logits and
+ * ursn_backward_logits are refused (frozen mode is forward-only).  Needs an attached buffer.  With nothing attached and frozen off
+ * no call launches anything new or passes a different pointer.
+ * When profiling, the load and ursn_bn_update's launch are recorded under a pass id of their own, 7, as kernels "bn_frozen_load" and
+ * "bn_moving_update" (all layers in one launch: the record carries the first layer's name). */
+int ursn_bn_set_frozen(ursn_net* net, int32_t on);
 
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);

@@ -152,6 +152,11 @@ _SIGS = {
     "ursn_voxels_to_dense_sym": (C.c_int, [C.POINTER(ursn_voxel_batch), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                            _P, _P, _P, _P]),
     "ursn_voxel_index_sym": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "ursn_bn_moving_size": (C.c_int, [C.POINTER(ursn_config), C.POINTER(C.c_int64)]),
+    "ursn_bn_attach": (C.c_int, [_P, _P]),
+    "ursn_bn_update": (C.c_int, [_P, C.c_double, _P]),
+    "ursn_bn_moving_update": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_double, C.c_float, _P]),
+    "ursn_bn_set_frozen": (C.c_int, [_P, C.c_int32]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

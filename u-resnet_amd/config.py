@@ -75,6 +75,15 @@ class ssnet_config(object):
     # (ssnet_base.inference_tta, with SPARSE_IO inference_voxel_scores_tta); [0] is the plain pass, [] = off.  Ignored with
     # TRAIN; refused together with ANA_CSV
     ANA_TTA = []
+    # not in the reference, where slim.batch_norm's moving_mean / moving_variance exist but are never updated nor read
+    # (is_training stays True, UPDATE_OPS never run).  BN_MOVING True = every training minibatch folds its batch statistics into
+    # the moving statistics with momentum 1 - BN_DECAY (slim's assign_moving_average), checkpoints carry them under the TF names
+    # UResNet/<scope>/BatchNorm/moving_mean | moving_variance and a restore loads them when the file has them (else 0 / 1).
+    # ANA_BN 'batch' | 'moving' = which statistics the ana driver's forward passes normalise with, in all its output modes;
+    # 'moving' makes an event's result independent of the events that share its batch.  Defaults: off, as the reference behaves
+    BN_MOVING = False
+    BN_DECAY = 0.999
+    ANA_BN = 'batch'
 
     def __init__(self):
         pass
@@ -118,6 +127,12 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'AUGMENT' and value not in ('', 'flip', 'cube'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'ANA_BN' and value not in ('batch', 'moving'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'BN_DECAY' and not 0.0 <= value <= 1.0:
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'ANA_TTA' and not all(type(c) is int and 0 <= c < 48 for c in value):

@@ -13,6 +13,7 @@
 #include "ursn_common.h"
 #include "net_bf16.h"
 #include "ext_loss.h"
+#include "bn_moving.h"
 
 int conv_dispatch(const ursn_conv_desc& d, ConvPass pass, const float* in, const float* w, float* out, int accumulate,
                   hipStream_t s);
@@ -115,6 +116,7 @@ struct ursn_net {
   std::vector<std::pair<std::string, std::string>> cat_names;   // per decoder step: producers of [first | second] channel halves
   std::map<std::string, Act> named;       // debug lookup: activations
   std::map<std::string, int> named_z;     // layer name -> layer index
+  BnmState bnm;                           // BatchNorm moving statistics (bn_moving.hip); the bf16 plan keeps its own
 };
 
 namespace {
@@ -380,6 +382,10 @@ int plan(ursn_net* n, Arena& A) {
   n->bs_scratch = tr ? (double*)A.take((size_t)16384 * 3 * 8 * sizeof(double)) : nullptr;
   n->cs_scratch_bytes = ursn_class_stats_scratch_bytes(c.max_batch, n->lvox[0], c.num_class);
   n->cs_scratch = A.take(n->cs_scratch_bytes);
+  // BatchNorm moving statistics: the layer table and the frozen-mode scratch pairs come last, so no earlier piece moves
+  n->bnm.host.clear();
+  for (const Layer& L : n->layers) n->bnm.host.push_back(BnmEntry{L.mean, L.rstd, L.cout, L.zcs, 0});
+  bnm_plan(n->bnm, A);
 
   n->sizes.n_params = poff;
   n->sizes.n_layers = (int64_t)n->layers.size();
@@ -433,6 +439,11 @@ int conv_stats(ursn_net* n, int li, const Act& in, int N, hipStream_t s, const A
                void* red_scratch = nullptr) {
   if (!red_scratch) red_scratch = n->red_scratch;
   Layer& L = n->layers[li];
+  // where this launch's statistics finalise writes: the layer's vectors, or (frozen on the moving statistics) a scratch pair of
+  // the stream it runs on that nobody reads -- the consumers then find what the frozen load wrote into L.mean / L.rstd
+  const int slot = red_scratch == n->red_scratch2 ? 1 : 0;
+  float* const sm = bnm_mean(n->bnm, n->layers[li].mean, slot);
+  float* const sr = bnm_rstd(n->bnm, n->layers[li].rstd, slot);
   ursn_conv_desc d = L.desc;
   d.n = N;
   d.in_cstride = in.cs;
@@ -445,49 +456,49 @@ int conv_stats(ursn_net* n, int li, const Act& in, int N, hipStream_t s, const A
   if (pointwise_conv_supported(d, PASS_FWD, 0)) {  // 1x1 shortcut + BN-statistics partials in one pass
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
     URSN_TRY(launch_pointwise_conv(d, PASS_FWD, in.p, n->params + L.w_off, L.z, 0, (double*)red_scratch,
-                                   n->cfg.bn_eps, L.mean, L.rstd, s));
+                                   n->cfg.bn_eps, sm, sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
   if (n->dc_scratch && red_scratch == n->red_scratch && deep_conv_supported(d, PASS_FWD)) {  // deepest levels: weight-streaming kernel + moments
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
     URSN_TRY(launch_deep_conv(d, PASS_FWD, in.p, n->params + L.w_off, L.z, 0, n->dc_scratch, (double*)red_scratch, n->cfg.bn_eps,
-                              L.mean, L.rstd, s));
+                              sm, sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
   if (igemm_conv_supported(d, PASS_FWD)) {  // LDS-staged implicit GEMM + BN-statistics partials in one pass
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
     URSN_TRY(launch_igemm_conv(d, PASS_FWD, in.p, n->params + L.w_off, L.z, 0, (double*)red_scratch,
-                               n->cfg.bn_eps, L.mean, L.rstd, s));
+                               n->cfg.bn_eps, sm, sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
   if (stride2_conv_supported(d, PASS_FWD)) {  // LDS-staged stride-2 conv + BN-statistics partials in one pass
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
     URSN_TRY(launch_stride2_conv(d, PASS_FWD, in.p, n->params + L.w_off, L.z, 0, (double*)red_scratch,
-                                 n->cfg.bn_eps, L.mean, L.rstd, s));
+                                 n->cfg.bn_eps, sm, sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
   if (prefer_lds_scatter(d, PASS_FWD)) {  // LDS-staged transposed conv + BN-statistics partials in one pass
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
     URSN_TRY(launch_lds_scatter(d, PASS_FWD, in.p, n->params + L.w_off, L.z, 0, (double*)red_scratch,
-                                n->cfg.bn_eps, L.mean, L.rstd, s));
+                                n->cfg.bn_eps, sm, sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
   if (tiled_deconv_supported(d, PASS_FWD)) {  // transposed conv + BN-statistics partials in one pass
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
     URSN_TRY(launch_tiled_deconv(d, PASS_FWD, in.p, n->params + L.w_off, L.z, 0, (double*)red_scratch,
-                                 n->cfg.bn_eps, L.mean, L.rstd, s));
+                                 n->cfg.bn_eps, sm, sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
   if (tiled_conv_supported(d, PASS_FWD)) {  // conv + BN-statistics partials in one pass
     ProfScope ps(n, s, li, 0, 2.0 * layer_macs(n, L, N), layer_bytes(n, L, N));
-    URSN_TRY(launch_tiled_conv_bn(d, in.p, n->params + L.w_off, L.z, (double*)red_scratch, n->cfg.bn_eps, L.mean,
-                                  L.rstd, s));
+    URSN_TRY(launch_tiled_conv_bn(d, in.p, n->params + L.w_off, L.z, (double*)red_scratch, n->cfg.bn_eps, sm,
+                                  sr, s));
     ps.done(ursn_last_kernel_name());
     return 0;
   }
@@ -498,7 +509,7 @@ int conv_stats(ursn_net* n, int li, const Act& in, int N, hipStream_t s, const A
   }
   {
     ProfScope ps(n, s, li, 3, 0.0, 4.0 * N * n->lvox[L.lout] * L.cout);
-    URSN_TRY(launch_bn_stats(L.z, L.zcs, (int64_t)N * n->lvox[L.lout], L.cout, n->cfg.bn_eps, L.mean, L.rstd,
+    URSN_TRY(launch_bn_stats(L.z, L.zcs, (int64_t)N * n->lvox[L.lout], L.cout, n->cfg.bn_eps, sm, sr,
                              red_scratch, s));
     ps.done("bn_stats");
   }
@@ -570,6 +581,12 @@ int unit_fwd(ursn_net* n, Unit& u, int N, hipStream_t s) {
 int forward(ursn_net* n, const float* data, int N, hipStream_t s) {
   const int ns = n->cfg.num_strides;
   n->fwd_used = 0;
+  n->bnm.last_fwd = n->bnm.frozen ? 2 : 1;
+  if (n->bnm.frozen) {   // every layer's mean / rstd from the moving buffer, ONE launch; conv_stats keeps the finalises off them
+    ProfScope ps(n, s, n->conv0, 7, 0.0, 4.0 * (double)n->bnm.total);
+    URSN_TRY(bnm_launch_load(n->bnm, s));
+    ps.done("bn_frozen_load");
+  }
   Act din = n->a_data;
   din.p = const_cast<float*>(data);
   URSN_TRY(conv_stats(n, n->conv0, din, N, s));
@@ -892,8 +909,14 @@ int read_metrics(ursn_net* n, float* out, int cnt, hipStream_t s) {
   return 0;
 }
 
-int check_call(ursn_net* n, const float* data, int N) {
+BnmState& bnm_of(ursn_net* n) { return n->bf ? *bnet_bnm(n->bf) : n->bnm; }
+
+// training_entry: the name of a call that runs (or continues into) a backward pass; refused while frozen
+int check_call(ursn_net* n, const float* data, int N, const char* training_entry = nullptr) {
   URSN_REQUIRE(n, "null handle");
+  URSN_REQUIRE(!(training_entry && bnm_of(n).frozen),
+               "%s: refused while BatchNorm is frozen on its moving statistics (ursn_bn_set_frozen): frozen mode is forward-only",
+               training_entry);
   if (n->pend_state == 1) n->pend_state = 3;   // every run call overwrites the activations a pending forward_logits stored
   URSN_REQUIRE(data, "input_data is null");
   URSN_REQUIRE(N >= 1 && N <= n->cfg.max_batch, "batch %d outside [1,%d]", N, n->cfg.max_batch);
@@ -975,6 +998,8 @@ extern "C" int ursn_create(const ursn_config* cfg, float* params, float* grads, 
   }
   if (rc) { delete n; return rc; }
   n->params = params; n->grads = grads; n->adam_m = adam_m; n->adam_v = adam_v;
+  n->bnm.eps = n->cfg.bn_eps;
+  if (bnm_upload(n->bnm)) { delete n; return 1; }
   {
     if (ursn_env_on("URSN_WGRAD_STREAM")) {   // also for inference-only nets: the forward pass runs the shortcut convs on it
       int prio_lo = 0, prio_hi = 0;   // lowest priority: the dgrad / BN chain on the caller's stream is the critical path
@@ -1060,12 +1085,13 @@ extern "C" int ursn_zero_grad(ursn_net* net, void* stream) {
 
 extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* label, const float* weight, int32_t n,
                                float* out3, void* stream) {
-  URSN_TRY(check_call(net, data, n));
+  URSN_TRY(check_call(net, data, n, "accum_step"));
   URSN_REQUIRE(net->cfg.trainable && net->grads, "accum_step: net constructed with trainable=False");
   URSN_REQUIRE(label, "accum_step: input_label is null");
   URSN_REQUIRE(!net->cfg.use_weight || weight, "Network configured to use loss pixel-weighting. Cannot run w/ input_weight=None");
   hipStream_t s = (hipStream_t)stream;
   net->last_n = n;
+  bnm_of(net).last_fwd = 1;   // never frozen; set here too: a hipGraph replay below does not pass through forward()
   if (net->bf) {
     URSN_TRY(bnet_step(net->bf, data, label, weight, n, 0, nullptr, nullptr, s));
     if (out3) URSN_TRY(read_metrics(net, out3, 3, s));
@@ -1287,12 +1313,13 @@ extern "C" int ursn_infer_stats(ursn_net* net, const float* data, const float* l
 // ---- external loss boundary (ext_loss.hip) ------------------------------------------------------------------------------------
 // The step of ursn_accum_step cut open at the logits: forward() as a step runs it, then logits_dense instead of the head.
 extern "C" int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, float* logits_out, void* stream) {
-  URSN_TRY(check_call(net, data, n));
+  URSN_TRY(check_call(net, data, n, "forward_logits"));
   URSN_REQUIRE(net->cfg.trainable && net->grads, "forward_logits: net constructed with trainable=False");
   URSN_REQUIRE(logits_out, "forward_logits: logits_out is null");
   URSN_REQUIRE(((uintptr_t)logits_out & 3) == 0, "forward_logits: logits_out must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   net->last_n = n;
+  bnm_of(net).last_fwd = 1;   // never frozen
   if (net->bf) {
     URSN_TRY(bnet_forward_logits(net->bf, data, n, logits_out, s));
   } else {
@@ -1316,6 +1343,8 @@ extern "C" int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, 
 extern "C" int ursn_backward_logits(ursn_net* net, const float* data, const float* dlogits, int32_t n, float* dinput_out,
                                     void* stream) {
   URSN_REQUIRE(net, "backward_logits: null handle");
+  URSN_REQUIRE(!bnm_of(net).frozen, "backward_logits: refused while BatchNorm is frozen on its moving statistics (ursn_bn_set_frozen): "
+                                    "frozen mode is forward-only");
   URSN_REQUIRE(net->cfg.trainable && net->grads, "backward_logits: net constructed with trainable=False");
   URSN_REQUIRE(data && dlogits, "backward_logits: null data / dlogits");
   URSN_REQUIRE((((uintptr_t)dlogits | (uintptr_t)dinput_out) & 3) == 0, "backward_logits: dlogits / dinput_out must be 4-byte aligned");
@@ -1353,6 +1382,52 @@ extern "C" int ursn_backward_logits(ursn_net* net, const float* data, const floa
                                      dinput_out, s));
     ps.done("dinput");
   }
+  return 0;
+}
+
+// ---- BatchNorm moving statistics (bn_moving.hip) ----------------------------------------------------------------------------
+extern "C" int ursn_bn_moving_size(const ursn_config* cfg, int64_t* out) {
+  URSN_REQUIRE(cfg && out, "bn_moving_size: null argument");
+  ursn_sizes sz;
+  URSN_TRY(ursn_query(cfg, &sz));   // the chosen plan's own checks of the configuration
+  ursn_net tmp;
+  tmp.cfg = *cfg;
+  tmp.cfg.act_dtype = 0;            // same layers and widths in both precisions
+  Arena A;
+  URSN_TRY(plan(&tmp, A));
+  *out = tmp.bnm.total;
+  return 0;
+}
+
+extern "C" int ursn_bn_attach(ursn_net* net, float* moving) {
+  URSN_REQUIRE(net, "bn_attach: null handle");
+  BnmState& st = bnm_of(net);
+  URSN_REQUIRE(moving || !st.frozen, "bn_attach: cannot detach the moving buffer while BatchNorm is frozen on it");
+  URSN_REQUIRE(((uintptr_t)moving & 3) == 0, "bn_attach: the moving buffer must be 4-byte aligned");
+  st.moving = moving;
+  return 0;
+}
+
+extern "C" int ursn_bn_update(ursn_net* net, double momentum, void* stream) {
+  URSN_REQUIRE(net, "bn_update: null handle");
+  BnmState& st = bnm_of(net);
+  URSN_REQUIRE(st.moving, "bn_update: no moving buffer is attached (ursn_bn_attach)");
+  URSN_REQUIRE(momentum >= 0.0 && momentum <= 1.0, "bn_update: momentum = %g outside [0, 1]", momentum);
+  URSN_REQUIRE(st.last_fwd != 0, "bn_update: no forward has run on this handle");
+  URSN_REQUIRE(st.last_fwd == 1, "bn_update: the last forward was frozen: its mean / rstd are the moving statistics, not a batch's");
+  hipStream_t s = (hipStream_t)stream;
+  if (net->bf) return bnet_bn_update(net->bf, momentum, s);
+  ProfScope ps(net, s, net->conv0, 7, 0.0, 4.0 * (3.0 * (double)st.total));   // mean, rstd in; the buffer in and out
+  URSN_TRY(bnm_launch_update(st, momentum, s));
+  ps.done("bn_moving_update");
+  return 0;
+}
+
+extern "C" int ursn_bn_set_frozen(ursn_net* net, int32_t on) {
+  URSN_REQUIRE(net, "bn_set_frozen: null handle");
+  BnmState& st = bnm_of(net);
+  URSN_REQUIRE(!on || st.moving, "bn_set_frozen: no moving buffer is attached (ursn_bn_attach)");
+  st.frozen = on != 0;
   return 0;
 }
 

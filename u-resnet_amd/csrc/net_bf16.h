@@ -9,6 +9,9 @@ int bnet_create(const ursn_config* cfg, float* params, float* grads, void* works
 void bnet_destroy(ursn_bnet* n);
 const ursn_sizes* bnet_sizes(const ursn_bnet* n);
 float* bnet_metrics(ursn_bnet* n);
+struct BnmState;
+BnmState* bnet_bnm(ursn_bnet* n);   // BatchNorm moving statistics of the plan (bn_moving.h)
+int bnet_bn_update(ursn_bnet* n, double momentum, hipStream_t s);   // ursn_bn_update's launch, recorded when profiling
 int bnet_param(const ursn_bnet* n, int64_t index, ursn_param_info* out);
 // mode 0: forward + loss + backward (gradients accumulate); 1: forward + loss; 2: forward + softmax / ana labels
 int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, int mode, float* softmax_out,

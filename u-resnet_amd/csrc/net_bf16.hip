@@ -21,6 +21,7 @@
 #include "bf16_pack.h"
 #include "net_bf16.h"
 #include "ext_loss.h"
+#include "bn_moving.h"
 
 namespace {
 
@@ -107,6 +108,7 @@ struct ursn_bnet {
   std::vector<hipEvent_t> evs;
   size_t ev_used = 0;
   std::map<std::string, BAct> named;   // debug lookup (ursn_tensor): materialised activations and their gradient tensors
+  BnmState bnm;                        // BatchNorm moving statistics (bn_moving.hip)
 };
 
 namespace {
@@ -388,6 +390,10 @@ int plan(ursn_bnet* n, Arena& A) {
   n->bs_scratch = tr ? (double*)A.take((size_t)16384 * 24 * sizeof(double)) : nullptr;
   n->cs_scratch_bytes = ursn_class_stats_scratch_bytes(c.max_batch, n->lvox[0], c.num_class);
   n->cs_scratch = A.take(n->cs_scratch_bytes);
+  // BatchNorm moving statistics: the layer table and the frozen-mode scratch pairs come last, so no earlier piece moves
+  n->bnm.host.clear();
+  for (const BLayer& L : n->layers) n->bnm.host.push_back(BnmEntry{L.mean, L.rstd, L.cout, L.kout, 0});
+  bnm_plan(n->bnm, A);
 
   n->sizes.n_params = poff;
   n->sizes.n_layers = (int64_t)n->layers.size();
@@ -454,6 +460,11 @@ const float* beta_of(ursn_bnet* n, const BLayer& L);
 int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, double* stats = nullptr) {
   if (!stats) stats = n->stats;
   BLayer& L = n->layers[li];
+  // where this layer's statistics finalise writes: the layer's vectors, or (frozen on the moving statistics) a scratch pair of
+  // the stream it runs on that nobody reads -- the consumers then find what the frozen load wrote into L.mean / L.rstd
+  const int slot = stats == n->stats2 ? 1 : 0;
+  float* const sm = bnm_mean(n->bnm, L.mean, slot);
+  float* const sr = bnm_rstd(n->bnm, L.rstd, slot);
   GatherGeom g[8];
   const int cnt = layer_geoms(n, L, PASS_FWD, N, in.cs, L.kout, g);
   int Kw, Nw;
@@ -464,24 +475,24 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
     total = bdeconv_grid_blocks(g, cnt);
     URSN_TRY(pack_fits(L, 0, bdeconv_pack_elems()));
     URSN_TRY(launch_bdeconv(g, cnt, in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, s));
-    return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+    return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
   }
   if (bsconv_ok(g, cnt)) {   // transposed convs of the deeper levels: the eight parity classes in one launch
     URSN_TRY(pack_fits(L, 0, bsconv_pack_elems(g, cnt)));
     URSN_TRY(launch_bsconv(g, cnt, in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, s));
-    return bsconv_stats_finalize(g, cnt, stats, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+    return bsconv_stats_finalize(g, cnt, stats, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
   }
   if (cnt == 1 && !in.in_f32 && in.aff_layer < 0 && bs2k8_ok(g[0])) {   // stride-2 gather 8 -> 16 (without a shortcut beside it)
     total = bs2k8_grid_blocks(g[0]);
     URSN_TRY(pack_fits(L, 0, bs2k8_pack_elems()));
     URSN_TRY(launch_bs2k8(g[0], in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, nullptr, nullptr, 0, s));
-    return launch_bn_stats_final(stats, total, g[0].Nn, 16, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+    return launch_bn_stats_final(stats, total, g[0].Nn, 16, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
   }
   if (in.in_f32 && cnt == 1 && b0conv_ok(g[0])) {   // conv0 on the raw fp32 input: the taps are the contraction (bf16_conv0.hip)
     total = b0conv_grid_blocks(g[0]);
     URSN_TRY(pack_fits(L, 0, b0conv_pack_elems()));
     URSN_TRY(launch_b0conv(g[0], in.in_f32, n->params + L.w_off, Nw, L.wp[0], L.z, stats, s));
-    return launch_bn_stats_final(stats, total, g[0].Nn, 16, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+    return launch_bn_stats_final(stats, total, g[0].Nn, 16, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
   }
   if (in.in_f32) {   // ... or as an 8-channel layer with seven absent channels
     URSN_REQUIRE(cnt == 1 && b3conv_ok(g[0]) && g[0].K == 8, "bf16 forward: %s cannot read a scalar fp32 input", L.name.c_str());
@@ -490,7 +501,7 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
     URSN_TRY(pack_fits(L, 0, b3conv_pack_elems()));
     URSN_TRY(launch_b3conv(g[0], nullptr, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, total, s, nullptr, 0, nullptr, nullptr,
                            nullptr, nullptr, 0, in.in_f32));
-    return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+    return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
   }
   if (in.aff_layer >= 0) {   // virtual input: BatchNorm of the producer applied while staging
     const BLayer& P = n->layers[in.aff_layer];
@@ -501,7 +512,7 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
     g[0].accumulate = 0;
     URSN_TRY(pack_fits(L, 0, b3conv_pack_elems()));
     URSN_TRY(launch_b3conv(g[0], P.z, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, stats, 0, total, s, nullptr, 0, nullptr, nullptr, &af));
-    return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+    return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
   }
   for (int i = 0; i < cnt; ++i) total += bconv_grid_blocks(g[i]);
   URSN_REQUIRE(total > 0, "bf16 forward: no kernel for %s", L.name.c_str());
@@ -511,7 +522,7 @@ int conv_stats(ursn_bnet* n, int li, const BAct& in, int N, hipStream_t s, doubl
     URSN_TRY(launch_bconv(g[i], in.p, n->params + L.w_off, Kw, Nw, L.wp[0] + (size_t)i * L.wp_stride[0], L.z, stats, off, total, s));
     off += bconv_grid_blocks(g[i]);
   }
-  return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, L.mean, L.rstd, s);
+  return bconv_stats_finalize(g[0], stats, total, (int64_t)N * n->lvox[L.lout], n->cfg.bn_eps, sm, sr, s);
 }
 
 const float* beta_of(ursn_bnet* n, const BLayer& L) { return L.cout == L.kout ? n->params + L.b_off : n->beta_pad; }
@@ -562,8 +573,10 @@ int unit_fwd(ursn_bnet* n, BUnit& u, int N, hipStream_t s) {
       URSN_TRY(pack_fits(L, 0, bs2k8_pack_elems()));
       URSN_TRY(launch_bs2k8(g[0], u.in.p, n->params + L.w_off, Kw, Nw, L.wp[0], L.z, n->stats, 0, n->params + S.w_off, S.z, S.kout, s));
       const int64_t V = (int64_t)N * n->lvox[L.lout];
-      URSN_TRY(launch_bn_stats_final(n->stats, blocks, 16, 16, V, n->cfg.bn_eps, L.mean, L.rstd, s));
-      URSN_TRY(launch_bn_stats_final(n->stats + (size_t)blocks * 32, blocks, 16, 16, V, n->cfg.bn_eps, S.mean, S.rstd, s));
+      // frozen: both finalises go to the scratch pairs (same stream, one pair each)
+      URSN_TRY(launch_bn_stats_final(n->stats, blocks, 16, 16, V, n->cfg.bn_eps, bnm_mean(n->bnm, L.mean, 0), bnm_rstd(n->bnm, L.rstd, 0), s));
+      URSN_TRY(launch_bn_stats_final(n->stats + (size_t)blocks * 32, blocks, 16, 16, V, n->cfg.bn_eps, bnm_mean(n->bnm, S.mean, 1),
+                                     bnm_rstd(n->bnm, S.rstd, 1), s));
       fused_sc = true;
     }
   }
@@ -592,6 +605,11 @@ int forward(ursn_bnet* n, const float* data, int N, hipStream_t s) {
   // Weight packing: every (layer, pass) has its own packed buffer; from the second step at a batch size on, ONE launch here
   // fills them all and the launchers find their job done (bf16_pack.h).  URSN_BF16_PREPACK=0: every launcher packs for itself.
   n->ev_used = 0;
+  n->bnm.last_fwd = n->bnm.frozen ? 2 : 1;
+  if (n->bnm.frozen) {   // every layer's mean / rstd from the moving buffer, ONE launch; conv_stats keeps the finalises off them
+    BProf ps(n, s, n->conv0, 7, 0.0, 4.0 * (double)n->bnm.total, "bn_frozen_load");
+    URSN_TRY(bnm_launch_load(n->bnm, s));
+  }
   static const bool prepack = ursn_env_on("URSN_BF16_PREPACK");
   if (prepack && n->pack.d_jobs) {
     if (n->pack_N != N) { n->pack.clear(); n->pack_N = N; }
@@ -960,6 +978,8 @@ int bnet_create(const ursn_config* cfg, float* params, float* grads, void* works
   }
   if (rc) { delete n; return rc; }
   n->params = params; n->grads = grads;
+  n->bnm.eps = n->cfg.bn_eps;
+  if (bnm_upload(n->bnm)) { delete n; return 1; }
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
   if (!ursn_env_on("URSN_WGRAD_STREAM")) { *out = n; return 0; }   // weight gradients on the caller's stream (per-kernel profiling)
@@ -1016,6 +1036,11 @@ int bnet_set_wgrad_overlap(ursn_bnet* n, int on) {
 
 const ursn_sizes* bnet_sizes(const ursn_bnet* n) { return &n->sizes; }
 float* bnet_metrics(ursn_bnet* n) { return n->metrics; }
+BnmState* bnet_bnm(ursn_bnet* n) { return &n->bnm; }
+int bnet_bn_update(ursn_bnet* n, double momentum, hipStream_t s) {
+  BProf ps(n, s, n->conv0, 7, 0.0, 4.0 * (3.0 * (double)n->bnm.total), "bn_moving_update");
+  return bnm_launch_update(n->bnm, momentum, s);
+}
 
 int bnet_param(const ursn_bnet* n, int64_t index, ursn_param_info* out) {
   URSN_REQUIRE(index >= 0 && index < n->sizes.n_tensors, "param: index %lld out of range", (long long)index);

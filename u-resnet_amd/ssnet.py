@@ -201,10 +201,21 @@ class ssnet_base(object):
     # construct (lib/ssnet.py:20-89)
     # ------------------------------------------------------------------------------------------
     def construct(self, trainable=True, use_weight=True, learning_rate=None, allocate=True, device=None,
-                  seed=1234, bn_eps=1e-3, precision='fp32'):
+                  seed=1234, bn_eps=1e-3, precision='fp32', bn_moving=False, bn_decay=0.999):
         """``precision='bf16'`` (not in the reference, which is fp32 TensorFlow): mixed precision -- activations and
         gradient tensors bf16 in HBM, bf16 MFMA convolutions with fp32 accumulation; parameters, BatchNorm statistics,
-        accumulated gradients and Adam stay fp32 (BASELINE.json configs[4])."""
+        accumulated gradients and Adam stay fp32 (BASELINE.json configs[4]).
+
+        ``bn_moving`` (the half of slim.batch_norm the reference leaves dead): allocates the moving statistics of every
+        BatchNorm layer (mean 0, variance 1) and attaches them to the handle; every ``accum_gradients*`` call then folds its
+        forward's batch statistics in with momentum ``1 - bn_decay``, and ``set_bn_mode('moving')`` makes the forward-only
+        calls normalise with them.  False: nothing is allocated and every call does what it did without the keyword."""
+        if not 0.0 <= float(bn_decay) <= 1.0:
+            raise ValueError('bn_decay = %r outside [0, 1]' % (bn_decay,))
+        self._bn_tracking = bool(bn_moving)
+        self._bn_decay = float(bn_decay)
+        self._bn_mode = 'batch'
+        self._bn_buf = None
         if precision not in ('fp32', 'bf16'):
             raise ValueError("precision must be 'fp32' or 'bf16'")
         self._precision = precision
@@ -308,6 +319,16 @@ class ssnet_base(object):
         if end != self._n_params or sum(n for _, _, _, n in specs) != self._n_params:
             raise RuntimeError('parameter table does not tile the flat buffer: %d vs native %d' % (end, self._n_params))
         self._specs = specs
+        # moving statistics: per layer [moving_mean[cout] | moving_variance[cout]], unpadded, in this order (ursn_bn_attach)
+        self._bn_specs, off = [], 0
+        for l in native:
+            self._bn_specs.append((l['name'] + '/BatchNorm', l['cout'], off))
+            off += 2 * l['cout']
+        total = ctypes.c_int64(0)
+        _lib.check(lib.ursn_bn_moving_size(ctypes.byref(self._cfg), ctypes.byref(total)))
+        if total.value != off:
+            raise RuntimeError('moving-statistics table does not tile the buffer: %d vs native %d' % (off, total.value))
+        self._bn_size = off
 
     # ------------------------------------------------------------------------------------------
     # device state
@@ -325,6 +346,9 @@ class ssnet_base(object):
             self._grads = torch.zeros(n, dtype=torch.float32, device=self._device)
             self._adam_m = torch.zeros(n, dtype=torch.float32, device=self._device)
             self._adam_v = torch.zeros(n, dtype=torch.float32, device=self._device)
+        if getattr(self, '_bn_tracking', False):
+            self._bn_buf = torch.empty(self._bn_size, dtype=torch.float32, device=self._device)
+            self.reset_bn_moving()
         self.initialize_variables(seed)
 
     def initialize_variables(self, seed=1234):
@@ -379,6 +403,9 @@ class ssnet_base(object):
                                    ctypes.byref(h)))
         self._handle, self._max_batch, self._cfg = h, batch, cfg
         _lib.check(lib.ursn_set_adam_step(self._handle, step))
+        if getattr(self, '_bn_buf', None) is not None:   # caller-owned like the parameters: a new handle loses nothing
+            _lib.check(lib.ursn_bn_attach(self._handle, p(self._bn_buf)))
+            _lib.check(lib.ursn_bn_set_frozen(self._handle, int(self._bn_mode == 'moving')))
 
     def _destroy(self):
         if getattr(self, '_handle', None) is not None:
@@ -780,6 +807,7 @@ class ssnet_base(object):
         w = fd.get('input_weight') if self._use_weight else None
         _lib.check(_lib.load().ursn_accum_step(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
                                                self._ptr(w), n, out if fetch else None, self._stream(sess)))
+        self._bn_track(sess)
         self._last_feed = fd
         self._mark_consumed(fd)
         doc = ['', 'loss', 'acc. all', 'acc. nonzero']
@@ -940,6 +968,7 @@ class ssnet_base(object):
         w = fd.get('input_weight') if self._use_weight else None
         _lib.check(_lib.load().ursn_accum_step(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
                                                self._ptr(w), n, out if fetch else None, self._stream(sess)))
+        self._bn_track(sess)
         self._last_feed = fd  # keep device inputs alive until the stream has consumed them
         self._mark_consumed(fd)
         doc = ['', 'loss', 'acc. all', 'acc. nonzero']
@@ -1000,6 +1029,7 @@ class ssnet_base(object):
         (``[N, *spatial, num_class]``, device), ``loss.backward()``, then ``backward_logits(logits.grad)``.  Returns
         ``([None, loss], ['', 'loss'])`` (``None`` results with ``fetch=False``: nothing is read back)."""
         logits = self.forward_logits(sess, input_data).requires_grad_(True)
+        self._bn_track(sess)
         loss = loss_fn(logits)
         loss.backward()
         self.backward_logits(sess, logits.grad)
@@ -1022,6 +1052,7 @@ class ssnet_base(object):
         if not self._trainable:
             raise RuntimeError('apply_gradients: constructed with trainable=False')
         self.allreduce_gradients()
+        self.allreduce_bn_moving()
         self._ensure_handle(max(self._max_batch, 1))
         _lib.check(_lib.load().ursn_apply_adam(self._handle, float(self._opt._lr), self._stream(sess)))
         return [None]
@@ -1033,6 +1064,127 @@ class ssnet_base(object):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.all_reduce(self._grads, op=dist.ReduceOp.SUM)
+
+    def allreduce_bn_moving(self):
+        """Data parallelism: each rank folded its own minibatches' statistics in; the moving buffers are summed over ranks and
+        scaled by ``1 / world`` (one fp32 multiply), so that ranks stay identical like the weights do.  No-op without tracking
+        or with one rank."""
+        import torch.distributed as dist
+        if getattr(self, '_bn_buf', None) is None or not self._bn_tracking:
+            return
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(self._bn_buf, op=dist.ReduceOp.SUM)
+            self._bn_buf.mul_(1.0 / dist.get_world_size())
+
+    # ------------------------------------------------------------------------------------------
+    # BatchNorm moving statistics (slim.batch_norm's moving_mean / moving_variance, which the reference never updates nor
+    # reads: SURVEY.md Appendix B-3b/c)
+    # ------------------------------------------------------------------------------------------
+    def _bn_require(self, what):
+        if getattr(self, '_bn_buf', None) is None:
+            raise RuntimeError('%s: no moving statistics (construct(bn_moving=True) allocates them)' % what)
+
+    def _bn_track(self, sess):
+        """One ``assign_moving_average`` of every layer after a training forward (one per minibatch, as UPDATE_OPS would)."""
+        if getattr(self, '_bn_buf', None) is not None and self._bn_tracking:
+            _lib.check(_lib.load().ursn_bn_update(self._handle, 1.0 - self._bn_decay, self._stream(sess)))
+
+    def reset_bn_moving(self):
+        """slim's initial values: moving_mean 0, moving_variance 1."""
+        import torch
+        self._bn_require('reset_bn_moving')
+        host = np.zeros(self._bn_size, np.float32)
+        for _, c, off in self._bn_specs:
+            host[off + c:off + 2 * c] = 1.0
+        self._bn_buf.copy_(torch.from_numpy(host))
+
+    def bn_mode(self):
+        return self._bn_mode
+
+    def set_bn_mode(self, mode):
+        """``'batch'`` (default): every forward normalises with the statistics of the batch it is given, as the reference does.
+        ``'moving'``: the forward-only calls (``inference*``, ``run_test*``) normalise with the moving statistics, so an event's
+        result no longer depends on its batch; ``accum_gradients*``, ``forward_logits`` and ``backward_logits`` are refused."""
+        if mode not in ('batch', 'moving'):
+            raise ValueError("set_bn_mode: mode must be 'batch' or 'moving', got %r" % (mode,))
+        if mode == 'moving':
+            self._bn_require("set_bn_mode('moving')")
+        if self._handle is not None and getattr(self, '_bn_buf', None) is not None:
+            _lib.check(_lib.load().ursn_bn_set_frozen(self._handle, int(mode == 'moving')))
+        self._bn_mode = mode
+
+    def bn_calibrate(self, sess, batches, reset=True):
+        """Usable moving statistics for a checkpoint that has none (the reference's own snapshots hold the initial 0 / 1):
+        forward-only over ``batches`` (an iterable of ``input_data``) in batch mode, folding the k-th batch in with momentum
+        ``1 / k``, so the buffer ends as the cumulative mean of the batches' statistics.  Returns the number of batches; the
+        mode is left as it was found.  Every batch ends in the stream synchronisation ``ursn_infer_voxels`` / ``ursn_infer`` make."""
+        import torch
+        self._bn_require('bn_calibrate')
+        lib, mode = _lib.load(), self._bn_mode
+        self.set_bn_mode('batch')
+        try:
+            if reset:
+                self.reset_bn_moving()
+            k = 0
+            dummy = torch.empty(16, dtype=torch.uint8, device=self._device)
+            none = None
+            for data in batches:
+                fd = {'input_data': self._feed(data, self._data_size, 'data')}
+                n = int(fd['input_data'].shape[0])
+                self._ensure_handle(n)
+                if none is None or none.numel() < n + 1:   # an empty voxel list: n + 1 zero offsets (the index is never read)
+                    none = torch.zeros(n + 1, dtype=torch.int64, device=self._device)
+                if int(self._dims[-1]) == 1:   # the forward alone: an empty voxel list launches no head at all
+                    _lib.check(lib.ursn_infer_voxels(self._handle, self._ptr(fd['input_data']), None, n, self._ptr(none),
+                                                     self._ptr(none), 0, None, self._ptr(dummy), None, None, self._stream(sess)))
+                else:
+                    sm = torch.empty((n, self._label_size * self._num_class), dtype=torch.float32, device=self._device)
+                    _lib.check(lib.ursn_infer(self._handle, self._ptr(fd['input_data']), None, n, self._ptr(sm), None,
+                                              self._stream(sess)))
+                k += 1
+                _lib.check(lib.ursn_bn_update(self._handle, 1.0 / k, self._stream(sess)))
+                self._last_feed = fd
+                self._mark_consumed(fd)
+        finally:
+            self.set_bn_mode(mode)
+        return k
+
+    def bn_moving_names(self):
+        return [n + s for n, _, _ in self._bn_specs for s in ('/moving_mean', '/moving_variance')]
+
+    def get_bn_moving(self):
+        """{'UResNet/<scope>/BatchNorm/moving_mean' | '.../moving_variance': float32 [cout]}: the TF checkpoint names."""
+        self._bn_require('get_bn_moving')
+        host = self._bn_buf.detach().cpu().numpy()
+        out = {}
+        for name, c, off in self._bn_specs:
+            out[name + '/moving_mean'] = host[off:off + c].copy()
+            out[name + '/moving_variance'] = host[off + c:off + 2 * c].copy()
+        return out
+
+    def set_bn_moving(self, values, strict=True):
+        """Names and shapes are checked like ``set_variables`` does (``strict``: a missing name is a KeyError, else it keeps its
+        value); a negative or non-finite variance (or a non-finite mean) is refused.  Nothing is written unless all pass."""
+        import torch
+        todo = []
+        for name, c, off in self._bn_specs:
+            for k, suffix in enumerate(('/moving_mean', '/moving_variance')):
+                key = name + suffix
+                if key not in values:
+                    if strict:
+                        raise KeyError(key)
+                    continue
+                v = np.asarray(values[key], dtype=np.float32)
+                if tuple(v.shape) != (c,):
+                    raise ValueError('%s: shape %s, expected %s' % (key, v.shape, (c,)))
+                if not np.all(np.isfinite(v)) or (k == 1 and np.any(v < 0)):
+                    raise ValueError('%s: %s values are refused' % (key, 'negative or non-finite' if k else 'non-finite'))
+                todo.append((off + k * c, v))
+        self._bn_require('set_bn_moving')
+        host = self._bn_buf.detach().cpu().numpy().copy()
+        for at, v in todo:
+            host[at:at + v.size] = v
+        self._bn_buf.copy_(torch.from_numpy(host))
 
     def run_test(self, sess, input_data, input_label, input_weight=None, normalize_weight=False):
         fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)

@@ -164,6 +164,9 @@ class ssnet_trainval(object):
         dims = self._input_main.fetch_data(cfg.KEYWORD_DATA).dim()[1:]
         self._net = uresnet(dims=dims, num_class=cfg.NUM_CLASS, base_num_outputs=cfg.BASE_NUM_FILTERS, debug=cfg.DEBUG)
         extra = {'learning_rate': cfg.LEARNING_RATE} if cfg.TRAIN else {}
+        ana_moving = not cfg.TRAIN and cfg.ANA_BN == 'moving'
+        if cfg.BN_MOVING or ana_moving:   # default off: construct is then called exactly as before
+            extra.update(bn_moving=True, bn_decay=cfg.BN_DECAY)
         self._net.construct(trainable=cfg.TRAIN, use_weight=cfg.USE_WEIGHTS, seed=cfg.TF_RANDOM_SEED,
                             precision=cfg.PRECISION, **extra)
         self._sess = HipSession()
@@ -188,6 +191,8 @@ class ssnet_trainval(object):
                     self._saved.append(path)
         if cfg.LOAD_FILE:
             self._restore(cfg.LOAD_FILE)
+        if ana_moving:
+            self._net.set_bn_mode('moving')
         self._descr_metrics = None
 
     def _restore(self, load_file):
@@ -202,7 +207,24 @@ class ssnet_trainval(object):
                     continue
                 print('\033[95mLoading\033[00m variable', name, 'from', load_file)
                 values[name] = f[name]
+            moving = {}
+            if self._net._bn_buf is not None:   # absent from the file (a snapshot without BN_MOVING): the 0 / 1 stay
+                for name in self._net.bn_moving_names():
+                    if name not in f.files:
+                        continue
+                    if name in skip or (name + ':0') in skip:
+                        print('\033[91mSkipping\033[00m loading variable', name, 'from input weight...')
+                        continue
+                    print('\033[95mLoading\033[00m variable', name, 'from', load_file)
+                    moving[name] = f[name]
+                if not moving:
+                    print('\033[91mWarning\033[00m: no BatchNorm moving statistics loaded from %s: they keep their initial 0 / 1' % load_file
+                          + (", and ANA_BN 'moving' normalises with those -- the output is meaningless until ssnet_base.bn_calibrate "
+                             "(or a BN_MOVING training run) has given the network usable statistics" if self._cfg.ANA_BN == 'moving'
+                             and not self._cfg.TRAIN else ''))
         self._net.set_variables(values, strict=False)
+        if moving:
+            self._net.set_bn_moving(moving, strict=False)
 
     # ---- training (lib/ssnet_trainval.py:156-233) ----------------------------------------------------------
     def _plan_iteration(self):
@@ -334,7 +356,10 @@ class ssnet_trainval(object):
     def save_checkpoint(self):
         """SAVE_FILE-<iteration>.npz keyed by TF variable names; keeps the newest CHECKPOINT_NMAX files."""
         path = '%s-%d.npz' % (self._cfg.SAVE_FILE, self._iteration)
-        np.savez(path, **self._net.get_variables())
+        arrays = self._net.get_variables()
+        if self._cfg.BN_MOVING:
+            arrays.update(self._net.get_bn_moving())
+        np.savez(path, **arrays)
         if path in self._saved:
             self._saved.remove(path)
         self._saved.append(path)
