@@ -582,6 +582,41 @@ int ursn_bn_moving_update(const float* mean, const float* rstd, float* moving_me
  * "bn_moving_update" (all layers in one launch: the record carries the first layer's name). */
 int ursn_bn_set_frozen(ursn_net* net, int32_t on);
 
+/* ---- loss weights made on the device (make_weights.hip) -------------------------------------------------------------------
+ * Appended functions and one struct only: URSN_ABI_VERSION stays 9.
+ * The per-voxel loss weight as a function of the label alone (the reference reads it as a stored larcv product,
+ * config/input_train3d.cfg: Tensor3DProducer "weight"): per-event class balance plus a category of its own for the voxels where
+ * two foreground classes meet.  For voxel v of event e:
+ *   c(v) = (int)label[v] (truncation, like the dense head) if -1 < label[v] < ncls, else none (NaN included);
+ *   v is a BOUNDARY voxel iff radius >= 1, c(v) >= 1 and some u != v inside the event's volume has max_i |u_i - v_i| <= radius in
+ *     spatial coordinates, c(u) >= 1 and c(u) != c(v) (positions outside the volume, background and none voxels are never such a
+ *     u; flat-index neighbours that are not spatial neighbours do not count; in 2-D the neighbourhood is a square);
+ *   k(v) = ncls if v is boundary, else c(v); none voxels have no category;
+ *   counts[e][k], k in 0..ncls = voxels of event e in category k;
+ *   mode 0: w(v) = scale[k(v)];  mode 1: w(v) = (float)((double)scale[k(v)] / (double)counts[e][k(v)]) (one fp64 division, rounded
+ *     once); none voxels get 0.0f. */
+#define URSN_WEIGHTS_CLASS 0
+#define URSN_WEIGHTS_INVFREQ 1
+typedef struct ursn_make_weights_desc {
+  int32_t ndim, spatial[3];   /* ndim 2 | 3 (spatial[2] unused in 2-D); prod(spatial) == voxels */
+  int32_t n;                  /* events, 1..65535 */
+  int64_t voxels;             /* per event, < 2^31 */
+  int32_t ncls;               /* 1..8 */
+  int32_t radius;             /* 0..3 (Chebyshev) */
+  int32_t mode;               /* URSN_WEIGHTS_CLASS | URSN_WEIGHTS_INVFREQ */
+  float scale[9];             /* [ncls + 1] read, finite: classes 0..ncls-1, then the boundary category */
+} ursn_make_weights_desc;
+
+/* label, weight_out [n, voxels] fp32 (device, 4-byte aligned, not overlapping); counts_out [n, ncls + 1] int64 (device) or NULL.
+ * Three launches on `stream`: categorise box tiles (the tile and a radius-wide halo as one byte per voxel in LDS) into a byte map
+ * and per-workgroup histograms in the scratch; reduce each event's histograms to counts and the ncls + 1 weight table; write the
+ * weights from the map.  No atomics, no allocation, the scratch needs no initialisation, integer counts: the same arguments give
+ * the same bits.  Enqueues only, never synchronises.  scratch: 8-byte aligned, >= ursn_make_weights_scratch_bytes(...), which is 0
+ * for arguments out of domain.  Anything out of domain is refused with a message before any launch. */
+int ursn_make_weights(const ursn_make_weights_desc* d, const float* label, float* weight_out, int64_t* counts_out, void* scratch,
+                      size_t scratch_bytes, void* stream);
+size_t ursn_make_weights_scratch_bytes(int32_t ndim, const int32_t* spatial, int32_t n, int32_t ncls, int32_t radius);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

@@ -8,5 +8,6 @@ or without a GPU the compute entry points raise.
 from .config import ssnet_config  # noqa: F401
 from .ssnet import ssnet_base, HipSession  # noqa: F401
 from .uresnet import uresnet  # noqa: F401
+from .weights import WeightSpec, make_weights_numpy  # noqa: F401
 
-__all__ = ["ssnet_config", "ssnet_base", "uresnet", "HipSession"]
+__all__ = ["ssnet_config", "ssnet_base", "uresnet", "HipSession", "WeightSpec", "make_weights_numpy"]

@@ -76,6 +76,11 @@ class ursn_sym_desc(C.Structure):
                 ("ops", C.POINTER(C.c_int32))]
 
 
+class ursn_make_weights_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("voxels", C.c_int64), ("ncls", C.c_int32),
+                ("radius", C.c_int32), ("mode", C.c_int32), ("scale", C.c_float * 9)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -157,6 +162,8 @@ _SIGS = {
     "ursn_bn_update": (C.c_int, [_P, C.c_double, _P]),
     "ursn_bn_moving_update": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_double, C.c_float, _P]),
     "ursn_bn_set_frozen": (C.c_int, [_P, C.c_int32]),
+    "ursn_make_weights": (C.c_int, [C.POINTER(ursn_make_weights_desc), _P, _P, _P, _P, C.c_size_t, _P]),
+    "ursn_make_weights_scratch_bytes": (C.c_size_t, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

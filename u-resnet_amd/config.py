@@ -84,6 +84,16 @@ class ssnet_config(object):
     BN_MOVING = False
     BN_DECAY = 0.999
     ANA_BN = 'batch'
+    # not in the reference, where the pixel weight is a stored larcv product (config/input_train3d.cfg: Tensor3DProducer "weight")
+    # that an upstream module wrote from the label.  DEVICE_WEIGHTS 'class' | 'invfreq' = the train and test steps make the
+    # weights on the device from the label (ursn_make_weights; weights.py holds the definition): KEYWORD_WEIGHT is not fetched,
+    # no weight crosses PCIe and with SPARSE_IO the weight lists are dropped from the batch.  'class' = WEIGHT_SCALE[category],
+    # 'invfreq' = WEIGHT_SCALE[category] / (voxels of the event in that category).  WEIGHT_RADIUS 1..3 = foreground voxels with
+    # another foreground class within that Chebyshev distance form a category of their own, the last entry of WEIGHT_SCALE
+    # (NUM_CLASS + 1 numbers; [] = all ones).  Needs USE_WEIGHTS; composes with DEVICE_WEIGHT_NORM and AUGMENT.  '' = off
+    DEVICE_WEIGHTS = ''
+    WEIGHT_RADIUS = 0
+    WEIGHT_SCALE = []
 
     def __init__(self):
         pass
@@ -133,6 +143,15 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'BN_DECAY' and not 0.0 <= value <= 1.0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'DEVICE_WEIGHTS' and value not in ('', 'class', 'invfreq'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'WEIGHT_RADIUS' and not 0 <= value <= 3:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'WEIGHT_SCALE' and not all(type(c) in (int, float) and c == c and abs(c) != float('inf') for c in value):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'ANA_TTA' and not all(type(c) is int and 0 <= c < 48 for c in value):

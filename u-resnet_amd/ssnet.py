@@ -550,6 +550,82 @@ class ssnet_base(object):
         fd['input_weight'] = out
 
     # ------------------------------------------------------------------------------------------
+    # loss weights made on the device from the label (not in the reference, which reads them as a stored larcv product;
+    # definition and numpy statement: weights.py)
+    # ------------------------------------------------------------------------------------------
+    def _check_make_weight(self, spec, given, what):
+        """The refusals of ``make_weight=spec``, before anything touches the device."""
+        from .weights import WeightSpec
+        if not isinstance(spec, WeightSpec):
+            raise ValueError('%s: make_weight = %r, expected a WeightSpec or None' % (what, spec))
+        if given is not None:
+            raise ValueError('%s: make_weight makes the weights on the device; a weight was given as well' % what)
+        if not self._use_weight:
+            raise ValueError('%s: make_weight needs a network constructed with use_weight=True' % what)
+        spec.scales(self._num_class)
+
+    def _make_fed_weight(self, fd, spec, sess, counts=None):
+        """``fd['input_weight'] = ursn_make_weights(fd['input_label'])`` on the compute stream, into an alternating pair of feed
+        slots registered like the voxel expansion's: ``_normalize_fed_weight`` then works in place, ``last_feed`` holds the weights
+        and ``_mark_consumed`` covers them.  The scratch is cached on the object and grown on demand."""
+        import torch
+        self._copy_stream()                         # the slot table lives with the copy stream
+        lab = fd['input_label']
+        n, V = int(lab.shape[0]), int(lab.shape[1])
+        lib, nd = _lib.load(), len(self._dims) - 1
+        d = _lib.ursn_make_weights_desc()
+        d.ndim, d.n, d.voxels, d.ncls, d.radius, d.mode = nd, n, V, self._num_class, spec.radius, spec.mode_code()
+        for i in range(nd):
+            d.spatial[i] = int(self._dims[i])
+        for i, v in enumerate(spec.scales(self._num_class)):
+            d.scale[i] = float(v)
+        need = int(lib.ursn_make_weights_scratch_bytes(nd, d.spatial, n, d.ncls, d.radius))
+        scratch = getattr(self, '_mkw_scratch', None)
+        if scratch is None or scratch.numel() * 8 < need:
+            scratch = self._mkw_scratch = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=self._device)
+        slot = self._feed_slots.setdefault('made_weight', ssnet_base._FeedSlot())
+        k = slot.turn
+        slot.turn ^= 1
+        if slot.dev[k] is None or slot.dev[k].shape[0] < n:
+            slot.dev[k] = torch.empty((n, V), dtype=torch.float32, device=self._device)
+            slot.consumed[k] = None
+        out = slot.dev[k][:n]
+        _lib.check(lib.ursn_make_weights(ctypes.byref(d), self._ptr(lab), self._ptr(out), self._ptr(counts), self._ptr(scratch),
+                                         scratch.numel() * 8, self._stream(sess)))
+        fd['input_weight'] = out
+
+    def make_weights(self, sess, input_label, spec, as_numpy=False, with_counts=False):
+        """The loss weights of ``spec`` (weights.WeightSpec) for ``input_label`` [N, voxels] (host array or device tensor), made on
+        the device: a device tensor [N, voxels] (one of the net's own buffers, valid until two more batches have been made) or,
+        with ``as_numpy``, a host array.  ``with_counts``: also ``counts`` int64 [N, num_class + 1], the voxels per category."""
+        import torch
+        from .weights import WeightSpec
+        if not isinstance(spec, WeightSpec):
+            raise ValueError('make_weights: spec = %r, expected a WeightSpec' % (spec,))
+        spec.scales(self._num_class)
+        if getattr(self, '_params', None) is None:
+            raise RuntimeError('construct(allocate=True) has not been called')
+        fd = {'input_label': self._feed(input_label, self._label_size, 'label')}
+        n = int(fd['input_label'].shape[0])
+        counts = torch.empty((n, self._num_class + 1), dtype=torch.int64, device=self._device) if with_counts else None
+        self._make_fed_weight(fd, spec, sess, counts)
+        self._mark_consumed({'input_label': fd['input_label']})
+        w = fd['input_weight']
+        if as_numpy:
+            w = w.cpu().numpy()
+        if not with_counts:
+            return w
+        return w, (counts.cpu().numpy() if as_numpy else counts)
+
+    def _feed_for_made_weight(self, input_data, input_label):
+        """``feed_dict`` without a weight role (the weights are made from the fed label)."""
+        fd = {'input_data': self._feed(input_data, self._data_size, 'data'),
+              'input_label': self._feed(input_label, self._label_size, 'label')}
+        if fd['input_label'].shape[0] != fd['input_data'].shape[0]:
+            raise ValueError('input_label has batch %d, input_data has %d' % (fd['input_label'].shape[0], fd['input_data'].shape[0]))
+        return fd
+
+    # ------------------------------------------------------------------------------------------
     # cube-symmetry augmentation and test-time averaging on the device (not in the reference, whose users flip and transpose
     # the volumes with numpy before the feed; codes and their numpy definition: symmetry.py)
     # ------------------------------------------------------------------------------------------
@@ -789,16 +865,23 @@ class ssnet_base(object):
         self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
         return fd
 
-    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None):
+    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None, make_weight=None):
         """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure.  ``normalize_weight``: the expanded dense
         weight tensor is normalised per event on the device (``_normalize_fed_weight``), the same definition of the sum as the
         dense feed's; ``voxels.weight`` / ``bg_weight`` are not written and ``VoxelBatch.normalize_weights`` is not needed.
         ``symmetry``: as in ``accum_gradients``; the operation is index arithmetic inside the expansion's scatter and the list
-        is neither rewritten nor re-sorted."""
+        is neither rewritten nor re-sorted.  ``make_weight``: as in ``accum_gradients``; ``voxels.weight`` / ``bg_weight`` must be
+        None, only offsets, index, value and label travel, and the expansion has no weight role."""
         if not self._trainable:
             raise RuntimeError('accum_gradients_voxels: constructed with trainable=False')
+        if make_weight is not None:
+            self._check_make_weight(make_weight, voxels.weight, 'accum_gradients_voxels')
         self._require_single_channel('accum_gradients_voxels')
-        fd = self._feed_voxels(voxels, symmetry=symmetry)
+        if make_weight is None:
+            fd = self._feed_voxels(voxels, symmetry=symmetry)
+        else:
+            fd = self._feed_voxels(voxels, with_weight=False, symmetry=symmetry)
+            self._make_fed_weight(fd, make_weight, sess)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
@@ -815,10 +898,16 @@ class ssnet_base(object):
             return None, doc
         return [None, float(out[0]), float(out[1]), float(out[2])], doc
 
-    def run_test_voxels(self, sess, voxels, normalize_weight=False):
-        """``run_test`` fed a VoxelBatch (``normalize_weight`` as in ``accum_gradients_voxels``)."""
+    def run_test_voxels(self, sess, voxels, normalize_weight=False, make_weight=None):
+        """``run_test`` fed a VoxelBatch (``normalize_weight`` / ``make_weight`` as in ``accum_gradients_voxels``)."""
+        if make_weight is not None:
+            self._check_make_weight(make_weight, voxels.weight, 'run_test_voxels')
         self._require_single_channel('run_test_voxels')
-        fd = self._feed_voxels(voxels)
+        if make_weight is None:
+            fd = self._feed_voxels(voxels)
+        else:
+            fd = self._feed_voxels(voxels, with_weight=False)
+            self._make_fed_weight(fd, make_weight, sess)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
@@ -935,9 +1024,10 @@ class ssnet_base(object):
     def _ptr(t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
-    def make_summary(self, sess, input_data, input_label, input_weight=None, normalize_weight=False):
+    def make_summary(self, sess, input_data, input_label, input_weight=None, normalize_weight=False, make_weight=None):
         """The reference returns a serialized TensorBoard summary; here the three scalars it holds."""
-        res, _ = self.run_test(sess, input_data, input_label, input_weight, normalize_weight=normalize_weight)
+        extra = {} if make_weight is None else {'make_weight': make_weight}
+        res, _ = self.run_test(sess, input_data, input_label, input_weight, normalize_weight=normalize_weight, **extra)
         return {'loss': res[0], 'accuracy_all': res[1], 'accuracy_nonzero': res[2]}
 
     def zero_gradients(self, sess=None):
@@ -948,18 +1038,27 @@ class ssnet_base(object):
         return [None]
 
     def accum_gradients(self, sess, input_data, input_label, input_weight=None, fetch=True, normalize_weight=False,
-                        symmetry=None):
+                        symmetry=None, make_weight=None):
         """``normalize_weight`` (not in the reference, whose driver normalises on the host, lib/ssnet_trainval.py:173): the fed
         weights are divided by their per-event sums on the device before the step (``_normalize_fed_weight``); ``input_weight``
         itself, host array or device tensor, is left as it is.  ``symmetry`` (not in the reference, whose users flip and
         transpose on the host): a sequence of one code per event (symmetry.py); the step then sees data, label and weight of event
         i under operation ``symmetry[i]``, permuted on the device (``_apply_symmetry``) before the weight normalisation.  None:
-        the call is made exactly as without the keyword."""
+        the call is made exactly as without the keyword.  ``make_weight`` (a weights.WeightSpec; not in the reference, which reads
+        the weights as a stored product): ``input_weight`` must be None and no weight crosses PCIe; after the feed and the symmetry
+        (over data and label only) ``ursn_make_weights`` makes the weights on the device from the label the step will see, before
+        the optional normalisation.  None: the call is made exactly as without the keyword."""
         if not self._trainable:
             raise RuntimeError('accum_gradients: constructed with trainable=False')
-        fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
+        if make_weight is not None:
+            self._check_make_weight(make_weight, input_weight, 'accum_gradients')
+            fd = self._feed_for_made_weight(input_data, input_label)
+        else:
+            fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
         if symmetry is not None:
             fd = self._apply_symmetry(fd, symmetry, sess)
+        if make_weight is not None:
+            self._make_fed_weight(fd, make_weight, sess)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])
@@ -1186,8 +1285,13 @@ class ssnet_base(object):
             host[at:at + v.size] = v
         self._bn_buf.copy_(torch.from_numpy(host))
 
-    def run_test(self, sess, input_data, input_label, input_weight=None, normalize_weight=False):
-        fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
+    def run_test(self, sess, input_data, input_label, input_weight=None, normalize_weight=False, make_weight=None):
+        if make_weight is not None:
+            self._check_make_weight(make_weight, input_weight, 'run_test')
+            fd = self._feed_for_made_weight(input_data, input_label)
+            self._make_fed_weight(fd, make_weight, sess)
+        else:
+            fd = self.feed_dict(input_data=input_data, input_label=input_label, input_weight=input_weight)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
         n = int(fd['input_data'].shape[0])

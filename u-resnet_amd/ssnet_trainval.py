@@ -37,6 +37,7 @@ from .config import ssnet_config
 from .ssnet import HipSession, ana_csv_header, ana_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
+from .weights import WeightSpec
 
 
 def _dist():
@@ -86,6 +87,7 @@ class ssnet_trainval(object):
         self._sess = None
         self._net = None
         self._writer_train = self._writer_test = None
+        self._weight_spec = None
 
     def __del__(self):
         try:
@@ -147,6 +149,12 @@ class ssnet_trainval(object):
         if cfg.ANA_TTA and not cfg.TRAIN and cfg.ANA_CSV:
             raise ValueError('ANA_TTA cannot be combined with ANA_CSV: the per-class statistics are reduced on the device from the '
                              'logits of ONE forward pass, a test-time average only exists as scores after several passes')
+        self._weight_spec = None
+        if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
+            if not cfg.USE_WEIGHTS:
+                raise ValueError('DEVICE_WEIGHTS needs USE_WEIGHTS True')
+            self._weight_spec = WeightSpec(cfg.DEVICE_WEIGHTS, cfg.WEIGHT_RADIUS, cfg.WEIGHT_SCALE or None)
+            self._weight_spec.scales(cfg.NUM_CLASS)
         self._input_main = self._open_stream('MainIO', cfg.MAIN_INPUT_CONFIG, cfg.MINIBATCH_SIZE)
         if cfg.TEST_INPUT_CONFIG:
             self._input_test = self._open_stream('TestIO', cfg.TEST_INPUT_CONFIG, cfg.TEST_BATCH_SIZE)
@@ -242,7 +250,7 @@ class ssnet_trainval(object):
         data = io.fetch_data(kd).data()
         label = io.fetch_data(kl).data()
         weight = None
-        if self._cfg.USE_WEIGHTS:
+        if self._cfg.USE_WEIGHTS and self._weight_spec is None:   # DEVICE_WEIGHTS: made on the device, KEYWORD_WEIGHT is not fetched
             weight = io.fetch_data(kw).data()
             if not self._cfg.DEVICE_WEIGHT_NORM:
                 weight /= np.sum(weight, axis=1).reshape([weight.shape[0], 1])
@@ -253,14 +261,20 @@ class ssnet_trainval(object):
         over an event = listed weights + unlisted voxels x background weight, in float64).  With DEVICE_WEIGHT_NORM the list is
         handed on as it is and the expanded dense tensor is normalised on the device."""
         vb = io.fetch_voxels()
+        if self._weight_spec is not None:   # DEVICE_WEIGHTS: the weight lists stay on the host
+            from .ssnet import VoxelBatch
+            return VoxelBatch(vb.offsets, vb.index, vb.value, vb.label, None, None, vb.voxels)
         if self._cfg.USE_WEIGHTS and not self._cfg.DEVICE_WEIGHT_NORM:
             vb.normalize_weights()
         return vb
 
     def _norm_kw(self):
-        """Keyword of the network calls that are fed what ``_pull`` / ``_pull_voxels`` returned.  Empty with the default
-        DEVICE_WEIGHT_NORM False: those calls are then made exactly as before."""
-        return {'normalize_weight': True} if self._cfg.DEVICE_WEIGHT_NORM and self._cfg.USE_WEIGHTS else {}
+        """Keywords of the network calls that are fed what ``_pull`` / ``_pull_voxels`` returned.  Empty with the defaults
+        DEVICE_WEIGHT_NORM False and DEVICE_WEIGHTS '': those calls are then made exactly as before."""
+        kw = {'normalize_weight': True} if self._cfg.DEVICE_WEIGHT_NORM and self._cfg.USE_WEIGHTS else {}
+        if self._weight_spec is not None:   # DEVICE_WEIGHTS: the call makes the weights from the label it is fed
+            kw['make_weight'] = self._weight_spec
+        return kw
 
     def _sym_kw(self, minibatch, n):
         """Keyword of the accumulate calls.  Empty with the default AUGMENT '': those calls are then made exactly as before.  Else
