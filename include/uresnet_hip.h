@@ -617,6 +617,97 @@ int ursn_make_weights(const ursn_make_weights_desc* d, const float* label, float
                       size_t scratch_bytes, void* stream);
 size_t ursn_make_weights_scratch_bytes(int32_t ndim, const int32_t* spatial, int32_t n, int32_t ncls, int32_t radius);
 
+/* ---- guarded optimiser step (opt_guard.hip) ----------------------------------------------------------------------------------
+ * Appended functions and three structs only: URSN_ABI_VERSION stays 9.
+ * A deterministic segmented reduction over a flat fp32 gradient buffer, one segment per trainable tensor, and an Adam launch that
+ * takes its decision (clip coefficient, skip) from the result on the device: no host round trip.  No atomics, no workgroup waits on
+ * another, nothing is read that the same call or ursn_opt_state_init did not write, so the same arguments give the same bits.
+ *
+ * The STATE is caller-owned device memory (16-byte aligned, >= ursn_opt_state_size bytes; ursn_opt_state_layout gives the byte
+ * offsets): a 64-byte header, the status record (ursn_opt_status), per-tensor results (ursn_opt_tensor[n_seg]), per-chunk fp64
+ * partials (32 bytes per chunk), the segment table and the chunk table.  Segments are cut into chunks of URSN_OPT_CHUNK elements, a
+ * segment's last chunk is ragged and a chunk never crosses a segment.
+ *
+ * Definitions (x finite: neither NaN nor +-Inf; a non-finite element contributes 0 to the sums and the maximum and is only
+ * counted, so the sums stay comparable):
+ *   per tensor   g_sumsq = sum (double)g * (double)g (each square exact), p_sumsq likewise over the parameters (0 without them),
+ *                g_maxabs = max |g|, nonfinite = number of non-finite g;
+ *   summation    inside a chunk a thread owns fixed elements, then lanes by shuffles, then waves in wave order; a tensor's chunks
+ *                are added in chunk order, the tensors in index order;
+ *   status       sumsq = sum over tensors of g_sumsq, norm = sqrt(sumsq) in fp64, nonfinite = total count;
+ *   decision     coef = clip_norm > 0 && norm > clip_norm ? (float)((double)clip_norm / norm) : 1.0f  (fp64 division, rounded once),
+ *                skip = skip_nonfinite && nonfinite > 0;
+ *   update       on skip nothing is written to p, m or v.  Otherwise per element g' = g * coef (one fp32 multiply), then for tensors
+ *                whose decay flag is set p' = p * decay (one fp32 multiply, rounded on its own) with
+ *                decay = (float)(1.0 - (double)lr * (double)weight_decay) formed on the host (decoupled AdamW), then the Adam element
+ *                update of ursn_adam with lr_t formed on the host from t exactly as ursn_adam forms it.  With coef == 1, no decay
+ *                flag used (weight_decay == 0) and no skip the result equals ursn_adam's bit for bit.
+ * The step counter: the host cannot know a skip without a synchronisation, so t advances on EVERY guarded call, skipped or not (a
+ * skipped step costs one step of bias correction); skipped_total in the status record counts the skips.  A device-side pow would
+ * keep t exact and lose the bit-equality with the unguarded path. */
+#define URSN_OPT_CHUNK 4096
+typedef struct ursn_opt_desc {
+  float lr;               /* > 0 */
+  float clip_norm;        /* <= 0: no clipping */
+  float weight_decay;     /* 0: none; lr * weight_decay must lie in [0, 1] */
+  int32_t skip_nonfinite; /* != 0: a step with any non-finite gradient element writes nothing */
+} ursn_opt_desc;
+typedef struct ursn_opt_status {
+  double sumsq, norm;
+  int64_t nonfinite;
+  float coef;             /* 1.0f after a stats call, the clip coefficient after a decision */
+  int32_t skip;           /* 0 after a stats call */
+  int64_t calls;          /* decisions taken since ursn_opt_state_init */
+  int64_t skipped_total;  /* of those, skips */
+} ursn_opt_status;
+typedef struct ursn_opt_tensor {
+  double g_sumsq, p_sumsq;
+  float g_maxabs;
+  int32_t reserved_;      /* written 0 */
+  int64_t nonfinite;
+} ursn_opt_tensor;
+
+/* Bytes of the state for n_seg tensors of nelem_host[i] elements; 0 for arguments out of domain (n_seg outside [1, 65536], an
+ * element count < 1, 2^31 or more chunks).  No device access. */
+size_t ursn_opt_state_size(const int64_t* nelem_host, int32_t n_seg);
+/* out6 = {bytes, byte offset of the status record, of the per-tensor results, of the chunk partials, number of chunks,
+ * URSN_OPT_CHUNK}.  No device access. */
+int ursn_opt_state_layout(const int64_t* nelem_host, int32_t n_seg, int64_t* out6);
+/* Builds the tables on the host, uploads them and zeroes the status record (cumulative counters included).  offsets_host /
+ * nelem_host in floats from the start of the flat buffers, decay_host the per-tensor decay flags; segments must not overlap.
+ * Synchronises (blocking copies), like ursn_create.  Too small or misaligned state and anything out of domain are refused. */
+int ursn_opt_state_init(void* state, size_t bytes, const int64_t* offsets_host, const int64_t* nelem_host,
+                        const int32_t* decay_host, int32_t n_seg);
+/* Two launches on `stream`: one workgroup per chunk writes the chunk's partials, then ONE workgroup writes the per-tensor results
+ * and the status record (coef 1.0f, skip 0; calls and skipped_total are kept).  g (and p when given) must cover every segment of
+ * the table and be 4-byte aligned; 16-byte loads are used where a chunk's ADDRESS allows them.  Enqueues only. */
+int ursn_opt_stats(void* state, const float* g, const float* p_or_null, void* stream);
+/* One single-thread launch: sets coef and skip in the status record from what the preceding ursn_opt_stats left there, adds 1 to
+ * calls and skip to skipped_total.  Enqueues only. */
+int ursn_opt_decide(void* state, const ursn_opt_desc* desc, void* stream);
+/* One launch over the chunk table: loads coef and skip from the status record and applies the update defined above for step t >= 1
+ * (the caller's counter).  Chunks that do not lie inside [0, n) are not touched.  Enqueues only. */
+int ursn_opt_adam(void* state, float* p, const float* g, float* m, float* v, int64_t n, const ursn_opt_desc* desc, int64_t t,
+                  void* stream);
+/* Copies the status record and (tensors_out != NULL) the n_seg per-tensor results to the host after everything enqueued on
+ * `stream`: the ONLY synchronising call of this group besides the init. */
+int ursn_opt_state_read(const void* state, int32_t n_seg, ursn_opt_status* status_out, ursn_opt_tensor* tensors_out, void* stream);
+
+/* Net level, both plans alike (parameters, gradients and Adam slots are fp32 in both). */
+/* Bytes of the state of a configuration's parameter list; no device access. */
+int ursn_opt_state_bytes(const ursn_config* cfg, int64_t* out);
+/* Builds the table from the handle's own parameter list (ursn_param order; decay flag = rank > 1, so BatchNorm beta is never
+ * decayed) in the caller's buffer and attaches it; NULL detaches.  Synchronises like ursn_opt_state_init. */
+int ursn_opt_attach(ursn_net* net, void* state, size_t bytes);
+/* ursn_opt_stats over the handle's gradient buffer (and parameters when with_param_norms != 0).  Needs an attached state. */
+int ursn_grad_stats(ursn_net* net, int32_t with_param_norms, void* stream);
+/* Statistics, decision, Adam on `stream` (four launches), in place of ursn_apply_adam: advances the step counter by one on every
+ * call, skipped or not (see above), and marks a pending ursn_forward_logits as ursn_apply_adam does.  desc->lr <= 0 means 1e-3 like
+ * ursn_apply_adam, and lr_t is formed exactly as ursn_apply_adam forms it, so a neutral guarded step equals that call bit for bit.  Refused with a message when no state is attached. */
+int ursn_apply_adam_guarded(ursn_net* net, const ursn_opt_desc* desc, void* stream);
+/* ursn_opt_state_read on the attached state; tensors_out (or NULL) holds n_tensors records in ursn_param order. */
+int ursn_opt_read(ursn_net* net, ursn_opt_status* status_out, ursn_opt_tensor* tensors_out, void* stream);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

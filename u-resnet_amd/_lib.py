@@ -81,6 +81,20 @@ class ursn_make_weights_desc(C.Structure):
                 ("radius", C.c_int32), ("mode", C.c_int32), ("scale", C.c_float * 9)]
 
 
+class ursn_opt_desc(C.Structure):
+    _fields_ = [("lr", C.c_float), ("clip_norm", C.c_float), ("weight_decay", C.c_float), ("skip_nonfinite", C.c_int32)]
+
+
+class ursn_opt_status(C.Structure):
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_double), ("nonfinite", C.c_int64), ("coef", C.c_float), ("skip", C.c_int32),
+                ("calls", C.c_int64), ("skipped_total", C.c_int64)]
+
+
+class ursn_opt_tensor(C.Structure):
+    _fields_ = [("g_sumsq", C.c_double), ("p_sumsq", C.c_double), ("g_maxabs", C.c_float), ("reserved_", C.c_int32),
+                ("nonfinite", C.c_int64)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -164,6 +178,18 @@ _SIGS = {
     "ursn_bn_set_frozen": (C.c_int, [_P, C.c_int32]),
     "ursn_make_weights": (C.c_int, [C.POINTER(ursn_make_weights_desc), _P, _P, _P, _P, C.c_size_t, _P]),
     "ursn_make_weights_scratch_bytes": (C.c_size_t, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]),
+    "ursn_opt_state_size": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32]),
+    "ursn_opt_state_layout": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64)]),
+    "ursn_opt_state_init": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32]),
+    "ursn_opt_stats": (C.c_int, [_P, _P, _P, _P]),
+    "ursn_opt_decide": (C.c_int, [_P, C.POINTER(ursn_opt_desc), _P]),
+    "ursn_opt_adam": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(ursn_opt_desc), C.c_int64, _P]),
+    "ursn_opt_state_read": (C.c_int, [_P, C.c_int32, C.POINTER(ursn_opt_status), C.POINTER(ursn_opt_tensor), _P]),
+    "ursn_opt_state_bytes": (C.c_int, [C.POINTER(ursn_config), C.POINTER(C.c_int64)]),
+    "ursn_opt_attach": (C.c_int, [_P, _P, C.c_size_t]),
+    "ursn_grad_stats": (C.c_int, [_P, C.c_int32, _P]),
+    "ursn_apply_adam_guarded": (C.c_int, [_P, C.POINTER(ursn_opt_desc), _P]),
+    "ursn_opt_read": (C.c_int, [_P, C.POINTER(ursn_opt_status), C.POINTER(ursn_opt_tensor), _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -94,6 +94,22 @@ class ssnet_config(object):
     DEVICE_WEIGHTS = ''
     WEIGHT_RADIUS = 0
     WEIGHT_SCALE = []
+    # not in the reference, whose optimiser applies the summed minibatch gradients unseen (lib/ssnet.py:72-80).  All off by default:
+    # the step is then the plain Adam call.  CLIP_GRAD_NORM > 0 = the gradient is scaled so that its global L2 norm does not exceed
+    # it; WEIGHT_DECAY > 0 = decoupled AdamW on every tensor of rank > 1 (never BatchNorm beta); SKIP_NONFINITE True = a step whose
+    # gradient holds a NaN or Inf leaves parameters and Adam slots untouched (decided on the device, ssnet_base.set_optimizer; the
+    # step counter still advances).  GRAD_STATS True = summary steps append the global gradient norm and the per-tensor gradient
+    # and weight norms to LOGDIR/train/scalars.jsonl and report steps print gnorm= and the steps skipped since the last report.
+    # The learning rate is optim.lr_at(iteration): linear warm-up over LR_WARMUP_STEPS iterations from
+    # LEARNING_RATE / LR_WARMUP_STEPS, then LEARNING_RATE * LR_DECAY_RATE ** (iteration // LR_DECAY_STEPS); a pure function of the
+    # iteration, so a resumed run repeats it
+    CLIP_GRAD_NORM = 0.
+    WEIGHT_DECAY = 0.
+    SKIP_NONFINITE = False
+    GRAD_STATS = False
+    LR_WARMUP_STEPS = 0
+    LR_DECAY_STEPS = 0
+    LR_DECAY_RATE = 1.
 
     def __init__(self):
         pass
@@ -152,6 +168,15 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'WEIGHT_SCALE' and not all(type(c) in (int, float) and c == c and abs(c) != float('inf') for c in value):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key in ('CLIP_GRAD_NORM', 'WEIGHT_DECAY') and not 0.0 <= value < float('inf'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key in ('LR_WARMUP_STEPS', 'LR_DECAY_STEPS') and value < 0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'LR_DECAY_RATE' and not 0.0 < value < float('inf'):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'ANA_TTA' and not all(type(c) is int and 0 <= c < 48 for c in value):

@@ -86,6 +86,8 @@ struct ursn_net {
   int vdz_layer = -1, vdz_relu = 0, vdz_cs = 0;
   const float* vdz_g = nullptr;
   int64_t adam_t = 0;
+  void* opt_state = nullptr;   // guarded optimiser step (opt_guard.hip): the caller's state buffer, attached by ursn_opt_attach
+  int64_t opt_nchunks = 0;
   int last_n = 0;
   // external loss boundary: the forward of ursn_forward_logits that ursn_backward_logits may still continue
   // (0 none ran, 1 pending, 2 consumed by a backward, 3 overwritten by another run call, 4 parameters changed by apply_adam)
@@ -1184,6 +1186,84 @@ extern "C" int ursn_apply_adam(ursn_net* net, float lr, void* stream) {
   double lr_t = (double)lr * sqrt(1.0 - pow(b2, (double)net->adam_t)) / (1.0 - pow(b1, (double)net->adam_t));
   return launch_adam(net->params, net->grads, net->adam_m, net->adam_v, net->sizes.n_params, (float)lr_t, (float)b1,
                      (float)b2, 1e-8f, (hipStream_t)stream);
+}
+
+// ---- guarded optimiser step (opt_guard.hip) ---------------------------------------------------------------------------------
+namespace {
+// (offset, nelem, decay flag = rank > 1) of every trainable tensor in ursn_param order
+int opt_param_table(const ursn_net* net, std::vector<int64_t>& off, std::vector<int64_t>& nel, std::vector<int32_t>& dec) {
+  const int64_t nt = net->sizes.n_tensors;
+  off.resize(nt); nel.resize(nt); dec.resize(nt);
+  ursn_param_info info;
+  for (int64_t i = 0; i < nt; ++i) {
+    URSN_TRY(ursn_param(net, i, &info));
+    off[i] = info.offset; nel[i] = info.nelem; dec[i] = info.rank > 1;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int ursn_opt_state_bytes(const ursn_config* cfg, int64_t* out) {
+  URSN_REQUIRE(cfg && out, "opt_state_bytes: null argument");
+  ursn_net tmp;
+  tmp.cfg = *cfg;
+  tmp.cfg.act_dtype = 0;            // same tensors and element counts in both precisions
+  Arena A;
+  URSN_TRY(plan(&tmp, A));
+  std::vector<int64_t> off, nel;
+  std::vector<int32_t> dec;
+  URSN_TRY(opt_param_table(&tmp, off, nel, dec));
+  const size_t bytes = ursn_opt_state_size(nel.data(), (int32_t)nel.size());
+  URSN_REQUIRE(bytes > 0, "opt_state_bytes: the parameter list is out of the optimiser state's domain");
+  *out = (int64_t)bytes;
+  return 0;
+}
+
+extern "C" int ursn_opt_attach(ursn_net* net, void* state, size_t bytes) {
+  URSN_REQUIRE(net, "opt_attach: null handle");
+  if (!state) { net->opt_state = nullptr; net->opt_nchunks = 0; return 0; }
+  URSN_REQUIRE(net->grads, "opt_attach: net is not trainable");
+  std::vector<int64_t> off, nel;
+  std::vector<int32_t> dec;
+  URSN_TRY(opt_param_table(net, off, nel, dec));
+  URSN_TRY(ursn_opt_state_init(state, bytes, off.data(), nel.data(), dec.data(), (int32_t)nel.size()));
+  int64_t lay[6];
+  URSN_TRY(ursn_opt_state_layout(nel.data(), (int32_t)nel.size(), lay));
+  net->opt_state = state;
+  net->opt_nchunks = lay[4];
+  return 0;
+}
+
+extern "C" int ursn_grad_stats(ursn_net* net, int32_t with_param_norms, void* stream) {
+  URSN_REQUIRE(net && net->grads, "grad_stats: net is not trainable");
+  URSN_REQUIRE(net->opt_state, "grad_stats: no optimiser state is attached (ursn_opt_attach)");
+  return opt_launch_stats(net->opt_state, net->grads, with_param_norms ? net->params : nullptr, net->opt_nchunks, (hipStream_t)stream);
+}
+
+extern "C" int ursn_apply_adam_guarded(ursn_net* net, const ursn_opt_desc* desc, void* stream) {
+  URSN_REQUIRE(net && net->grads, "apply_adam_guarded: net is not trainable");
+  URSN_REQUIRE(net->opt_state, "apply_adam_guarded: no optimiser state is attached (ursn_opt_attach)");
+  URSN_REQUIRE(desc, "apply_adam_guarded: null desc");
+  ursn_opt_desc d = *desc;
+  if (d.lr <= 0.f) d.lr = 1e-3f;   // as ursn_apply_adam
+  const double shrink = (double)d.lr * (double)d.weight_decay;
+  URSN_REQUIRE(shrink >= 0.0 && shrink <= 1.0, "apply_adam_guarded: lr * weight_decay = %g outside [0, 1]", shrink);
+  hipStream_t s = (hipStream_t)stream;
+  URSN_TRY(opt_launch_stats(net->opt_state, net->grads, nullptr, net->opt_nchunks, s));
+  URSN_TRY(ursn_opt_decide(net->opt_state, &d, s));
+  const double b1 = 0.9, b2 = 0.999;
+  if (net->pend_state == 1) net->pend_state = 4;
+  net->adam_t += 1;   // on every guarded call, skipped or not: the host cannot know a skip without a synchronisation
+  const double lr_t = (double)d.lr * sqrt(1.0 - pow(b2, (double)net->adam_t)) / (1.0 - pow(b1, (double)net->adam_t));
+  const float decay = (float)(1.0 - shrink);
+  return opt_launch_adam(net->opt_state, net->params, net->grads, net->adam_m, net->adam_v, net->sizes.n_params, (float)lr_t, decay,
+                         net->opt_nchunks, s);
+}
+
+extern "C" int ursn_opt_read(ursn_net* net, ursn_opt_status* status_out, ursn_opt_tensor* tensors_out, void* stream) {
+  URSN_REQUIRE(net, "opt_read: null handle");
+  URSN_REQUIRE(net->opt_state, "opt_read: no optimiser state is attached (ursn_opt_attach)");
+  return ursn_opt_state_read(net->opt_state, (int32_t)net->sizes.n_tensors, status_out, tensors_out, stream);
 }
 
 extern "C" int ursn_eval(ursn_net* net, const float* data, const float* label, const float* weight, int32_t n,

@@ -46,6 +46,25 @@ __device__ __forceinline__ void ursn_sacc_final(float piv, float s1, float s2, f
   S1 = a + m * K;
   S2 = (double)s2 + 2.0 * K * a + m * K * K;
 }
+
+// ---- Adam element update (TF form) ----------------------------------------------------------------------------------
+// The ONE statement of the update, used by adam_kernel (elementwise.hip) and opt_adam_kernel (opt_guard.hip).  Contraction is off
+// inside it: every operation is rounded on its own in both kernels, whatever their loops look like, so a neutral guarded step and a
+// plain step give the same bits.
+__device__ __forceinline__ void ursn_adam_element(float& p, float gi, float& m, float& v, float lr_t, float b1, float b2,
+                                                  float eps) {
+#pragma clang fp contract(off)
+  float mi = b1 * m + (1.f - b1) * gi;
+  float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi;
+  v = vi;
+  p -= lr_t * mi / (sqrtf(vi) + eps);
+}
+// One fp32 multiply, rounded on its own: never contracted into the add or subtract that consumes it.
+__device__ __forceinline__ float ursn_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 #endif   // rename the last dispatch without counting a launch
 long ursn_kernel_launch_count();
 // roctx ranges (URSN_ROCTX=1): "UResNet/<scope>:<pass>" around every launch group, so rocprofv3 --marker-trace
@@ -319,6 +338,12 @@ int launch_cstats(const ursn_vscores_desc* d, const float* label, const ursn_cla
 
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2,
                 float eps, hipStream_t s);
+// Guarded optimiser step (opt_guard.hip): the launches behind ursn_opt_stats / ursn_opt_adam with the grid sized by the caller.
+// The kernels take the chunk count from the state's header and stride over the chunk table, so any grid >= 1 gives the same bits;
+// nchunks_hint <= 0 (the op-level entries, which do not know the table) launches a fixed grid.  lr_t as launch_adam takes it.
+int opt_launch_stats(void* state, const float* g, const float* p, int64_t nchunks_hint, hipStream_t s);
+int opt_launch_adam(void* state, float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float decay,
+                    int64_t nchunks_hint, hipStream_t s);
 int launch_fill(float* p, float value, int64_t n, hipStream_t s);
 // dst[i] += sum_c src[c*n + i]
 int launch_reduce_accum(float* dst, const float* src, int64_t n, int nchunks, hipStream_t s);

@@ -381,6 +381,7 @@ class ssnet_base(object):
             t = ctypes.c_int64(0)
             _lib.check(lib.ursn_get_adam_step(self._handle, ctypes.byref(t)))
             step = t.value
+            self._opt_carry_counters()
             self._destroy()
         cfg = self._native_config(max_batch=batch)
         sizes = _lib.ursn_sizes()
@@ -406,6 +407,8 @@ class ssnet_base(object):
         if getattr(self, '_bn_buf', None) is not None:   # caller-owned like the parameters: a new handle loses nothing
             _lib.check(lib.ursn_bn_attach(self._handle, p(self._bn_buf)))
             _lib.check(lib.ursn_bn_set_frozen(self._handle, int(self._bn_mode == 'moving')))
+        if getattr(self, '_opt_state', None) is not None:   # caller-owned as well; attaching rebuilds the tables for this handle
+            _lib.check(lib.ursn_opt_attach(self._handle, p(self._opt_state), self._opt_state.numel()))
 
     def _destroy(self):
         if getattr(self, '_handle', None) is not None:
@@ -1147,14 +1150,110 @@ class ssnet_base(object):
         _lib.check(_lib.load().ursn_read_metrics(self._handle, out, self._stream(sess)))
         return [float(out[0]), float(out[1]), float(out[2])]
 
-    def apply_gradients(self, sess=None):
+    def apply_gradients(self, sess=None, lr=None):
+        """All-reduce over ranks, then Adam.  ``lr`` (None: the constructor's learning rate) is this step's learning rate, what the
+        driver's schedule passes.  After ``set_optimizer`` with anything switched on the step is the guarded one
+        (``ursn_apply_adam_guarded``: gradient statistics, clip / skip decision and Adam on the stream, no host round trip);
+        otherwise it is ``ursn_apply_adam`` exactly as before.  The all-reduce stays first: every rank then reduces the same
+        buffer and reaches the same decision, and a NaN on one rank skips the step on all of them."""
         if not self._trainable:
             raise RuntimeError('apply_gradients: constructed with trainable=False')
         self.allreduce_gradients()
         self.allreduce_bn_moving()
         self._ensure_handle(max(self._max_batch, 1))
-        _lib.check(_lib.load().ursn_apply_adam(self._handle, float(self._opt._lr), self._stream(sess)))
+        step_lr = float(self._opt._lr) if lr is None else float(lr)
+        o = getattr(self, '_optimizer', None)
+        if o is not None and (o['clip_norm'] > 0 or o['weight_decay'] > 0 or o['skip_nonfinite']):
+            self._opt_require_state()
+            d = _lib.ursn_opt_desc()
+            d.lr, d.clip_norm, d.weight_decay, d.skip_nonfinite = step_lr, o['clip_norm'], o['weight_decay'], int(o['skip_nonfinite'])
+            _lib.check(_lib.load().ursn_apply_adam_guarded(self._handle, ctypes.byref(d), self._stream(sess)))
+        else:
+            _lib.check(_lib.load().ursn_apply_adam(self._handle, step_lr, self._stream(sess)))
+        self._last_lr = step_lr
         return [None]
+
+    # ------------------------------------------------------------------------------------------
+    # guarded optimiser step (not in the reference, lib/ssnet.py:72-80 applies the summed gradients unseen; numpy statement
+    # of the definitions: optim.py)
+    # ------------------------------------------------------------------------------------------
+    def set_optimizer(self, clip_norm=0., weight_decay=0., skip_nonfinite=False):
+        """What ``apply_gradients`` does besides Adam: ``clip_norm`` > 0 scales the gradient so that its global L2 norm does not
+        exceed it, ``weight_decay`` > 0 is decoupled AdamW on every tensor of rank > 1 (never BatchNorm beta),
+        ``skip_nonfinite`` leaves parameters and Adam slots untouched on a step whose gradient holds a NaN or Inf (the step
+        counter still advances; ``last_apply_status`` counts the skips).  With everything off ``apply_gradients`` stays the
+        plain call.  Allocates the device state of the statistics pass and attaches it (again after a handle is re-created)."""
+        clip_norm, weight_decay = float(clip_norm), float(weight_decay)
+        if not self._trainable:
+            raise RuntimeError('set_optimizer: constructed with trainable=False')
+        if clip_norm != clip_norm or clip_norm < 0 or clip_norm == float('inf'):
+            raise ValueError('set_optimizer: clip_norm = %r, expected a finite number >= 0' % (clip_norm,))
+        if not 0.0 <= weight_decay < float('inf'):
+            raise ValueError('set_optimizer: weight_decay = %r, expected a finite number >= 0' % (weight_decay,))
+        self._optimizer = {'clip_norm': clip_norm, 'weight_decay': weight_decay, 'skip_nonfinite': bool(skip_nonfinite)}
+        if getattr(self, '_params', None) is not None:
+            self._opt_require_state()
+
+    def _opt_require_state(self):
+        """The state buffer of ``ursn_opt_attach``: allocated once, attached to the current handle."""
+        import torch
+        if getattr(self, '_opt_state', None) is not None and self._handle is not None:
+            return
+        lib = _lib.load()
+        if getattr(self, '_opt_state', None) is None:
+            need = ctypes.c_int64(0)
+            _lib.check(lib.ursn_opt_state_bytes(ctypes.byref(self._cfg), ctypes.byref(need)))
+            self._opt_counters = [0, 0]                     # calls / skips of handles that are gone
+            state = torch.empty(int(need.value), dtype=torch.uint8, device=self._device)
+            if self._handle is not None:
+                _lib.check(lib.ursn_opt_attach(self._handle, self._ptr(state), state.numel()))
+            self._opt_state = state
+        if self._handle is None:
+            self._ensure_handle(max(self._max_batch, 1))    # attaches
+
+    def _opt_carry_counters(self):
+        """Before a handle is destroyed: attaching the state to its successor zeroes the cumulative counters, keep them here."""
+        if getattr(self, '_opt_state', None) is None or self._handle is None:
+            return
+        st = _lib.ursn_opt_status()
+        _lib.check(_lib.load().ursn_opt_read(self._handle, ctypes.byref(st), None, self._stream(None)))
+        self._opt_counters[0] += int(st.calls)
+        self._opt_counters[1] += int(st.skipped_total)
+
+    def grad_stats(self, sess, with_param_norms=True):
+        """Per-tensor statistics of the flat gradient buffer as it stands (after ``accum_gradients``; after ``apply_gradients`` it
+        still holds the step's summed gradient), reduced on the device in one pass: a dict keyed by the TF variable names with
+        ``grad_norm`` / ``grad_sumsq`` / ``grad_maxabs`` / ``nonfinite`` and, with ``with_param_norms``, ``param_norm`` /
+        ``param_sumsq`` of the weights (else 0.0), plus ``'global'`` = ``grad_norm`` / ``grad_sumsq`` / ``nonfinite``.  Non-finite
+        elements count and contribute nothing to the sums (optim.grad_stats_numpy is the definition).  Synchronises.  It
+        rewrites the decision fields of ``last_apply_status`` (coef 1, skip 0); the cumulative counters stay."""
+        if not self._trainable:
+            raise RuntimeError('grad_stats: constructed with trainable=False')
+        self._opt_require_state()
+        lib, nt = _lib.load(), len(self._specs)
+        _lib.check(lib.ursn_grad_stats(self._handle, int(bool(with_param_norms)), self._stream(sess)))
+        st, rows = _lib.ursn_opt_status(), (_lib.ursn_opt_tensor * nt)()
+        _lib.check(lib.ursn_opt_read(self._handle, ctypes.byref(st), rows, self._stream(sess)))
+        info, out = _lib.ursn_param_info(), {}
+        for i in range(nt):
+            _lib.check(lib.ursn_param(self._handle, i, ctypes.byref(info)))
+            r = rows[i]
+            out[info.name.decode()] = {'grad_sumsq': r.g_sumsq, 'grad_norm': math.sqrt(r.g_sumsq), 'grad_maxabs': float(r.g_maxabs),
+                                       'nonfinite': int(r.nonfinite), 'param_sumsq': r.p_sumsq, 'param_norm': math.sqrt(r.p_sumsq)}
+        out['global'] = {'grad_sumsq': st.sumsq, 'grad_norm': st.norm, 'nonfinite': int(st.nonfinite)}
+        return out
+
+    def last_apply_status(self, sess=None):
+        """The status record after the last guarded ``apply_gradients``: ``sumsq`` / ``norm`` / ``nonfinite`` of the gradient it saw,
+        the ``coef`` it multiplied the gradient by, ``skip`` (1: nothing was written), the cumulative ``calls`` and
+        ``skipped_total`` of guarded steps since ``set_optimizer``, and ``lr``, the learning rate of the last ``apply_gradients``.
+        Synchronises: the only way the host learns of a skip."""
+        self._opt_require_state()
+        st = _lib.ursn_opt_status()
+        _lib.check(_lib.load().ursn_opt_read(self._handle, ctypes.byref(st), None, self._stream(sess)))
+        return {'sumsq': st.sumsq, 'norm': st.norm, 'nonfinite': int(st.nonfinite), 'coef': float(st.coef), 'skip': int(st.skip),
+                'calls': int(st.calls) + self._opt_counters[0], 'skipped_total': int(st.skipped_total) + self._opt_counters[1],
+                'lr': getattr(self, '_last_lr', None)}
 
     def allreduce_gradients(self):
         """Data parallelism (not in the reference): every rank accumulated its own minibatches, the

@@ -32,7 +32,7 @@ import time
 
 import numpy as np
 
-from . import symmetry
+from . import optim, symmetry
 from .config import ssnet_config
 from .ssnet import HipSession, ana_csv_header, ana_csv_row
 from .synthetic_io import synthetic_threadio
@@ -178,6 +178,9 @@ class ssnet_trainval(object):
         self._net.construct(trainable=cfg.TRAIN, use_weight=cfg.USE_WEIGHTS, seed=cfg.TF_RANDOM_SEED,
                             precision=cfg.PRECISION, **extra)
         self._sess = HipSession()
+        self._skipped_reported = 0
+        if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
+            self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
         if bad and not cfg.TRAIN:
             raise ValueError('ANA_TTA: codes %s are not symmetry operations of the image shape %s' % (bad, list(dims[:-1])))
@@ -287,6 +290,14 @@ class ssnet_trainval(object):
         codes = symmetry.group(c.AUGMENT, [int(x) for x in self._net._dims[:-1]])
         return {'symmetry': symmetry.draw(c.AUGMENT_SEED, self._iteration, minibatch, d.get_rank() if d is not None else 0, n, codes)}
 
+    def _step_lr(self):
+        """The learning rate of the current iteration's optimiser step: what the step is given, the report line prints and the
+        summary records.  With a schedule on it is a function of the iteration alone (a resumed run repeats it), else the
+        constructor's rate, which the reference's report reads from the optimiser (lib/ssnet_trainval.py:209)."""
+        if optim.schedule_on(self._cfg):
+            return optim.lr_at(self._cfg, self._iteration)
+        return self._net._opt._lr
+
     def _run_minibatches(self, want_metrics):
         """zero -> NUM_MINIBATCHES x accumulate -> apply.  Returns the per-minibatch metrics [M, 3] when asked for
         (each read is a stream synchronisation), else None; in both cases ``self._last_minibatch`` holds the
@@ -309,7 +320,10 @@ class ssnet_trainval(object):
                 rows.append(res[1:])
             self._advance_main()
         self._last_minibatch = net.last_feed()
-        net.apply_gradients(self._sess)   # all-reduce(sum) over ranks + Adam
+        if optim.schedule_on(c):
+            net.apply_gradients(self._sess, lr=self._step_lr())
+        else:
+            net.apply_gradients(self._sess)   # all-reduce(sum) over ranks + Adam
         return np.asarray(rows, np.float32) if want_metrics else None
 
     def _mean_over_ranks(self, metrics):
@@ -335,6 +349,14 @@ class ssnet_trainval(object):
             else:
                 test = self._pull(self._input_test, c.KEYWORD_TEST_DATA, c.KEYWORD_TEST_LABEL, c.KEYWORD_TEST_WEIGHT)
 
+        gstats = None
+        if self._cfg.GRAD_STATS and (plan.report or plan.summary):
+            # the report already synchronises.  The status first: grad_stats rewrites its decision fields
+            applied = self._net.last_apply_status(self._sess)
+            gstats = self._net.grad_stats(self._sess, with_param_norms=plan.summary)
+            skipped_since = applied['skipped_total'] - self._skipped_reported
+            if plan.report:
+                self._skipped_reported = applied['skipped_total']
         if plan.report:
             # report_step is the same on every rank, so the collective inside is safe
             train_mean = self._mean_over_ranks(per_minibatch.mean(axis=0))
@@ -346,15 +368,25 @@ class ssnet_trainval(object):
             if _is_rank0():
                 stamp = datetime.datetime.fromtimestamp(time.time()).strftime('%Y-%m-%d %H:%M:%S')
                 sys.stdout.write('@ iteration {:d} LR {:g} Mem {:g} @ {:s}\n'.format(
-                    plan.iteration, self._net._opt._lr, self.report_memory(), stamp))
+                    plan.iteration, self._step_lr(), self.report_memory(), stamp))
                 sys.stdout.write('Train set: ')
                 self._report(train_mean, self._descr_metrics)
+                if gstats is not None:
+                    sys.stdout.write('Optimiser: gnorm=%.6g   nonfinite=%d   skipped=%d\n'
+                                     % (gstats['global']['grad_norm'], gstats['global']['nonfinite'],
+                                        skipped_since))
                 if tested is not None:
                     sys.stdout.write('Test set: ')
                     self._report(*tested)
         if plan.summary:
             last = self._last_minibatch   # already normalised, on the host or on the device: never again here
             summ = self._net.make_summary(self._sess, last['input_data'], last['input_label'], last.get('input_weight'))
+            if gstats is not None:
+                summ['gnorm'] = gstats['global']['grad_norm']
+                summ['lr'] = float(self._step_lr())
+                summ['skipped_total'] = applied['skipped_total']
+                summ['grad_norm'] = {k: v['grad_norm'] for k, v in gstats.items() if k != 'global'}
+                summ['weight_norm'] = {k: v['param_norm'] for k, v in gstats.items() if k != 'global'}
             if self._writer_train:
                 self._writer_train.add_summary(summ, plan.iteration)
             if self._writer_test and test is not None:
