@@ -708,6 +708,75 @@ int ursn_apply_adam_guarded(ursn_net* net, const ursn_opt_desc* desc, void* stre
 /* ursn_opt_state_read on the attached state; tensors_out (or NULL) holds n_tensors records in ursn_param order. */
 int ursn_opt_read(ursn_net* net, ursn_opt_status* status_out, ursn_opt_tensor* tensors_out, void* stream);
 
+/* ---- tiling: crops of large voxel-list events and the way back (tiling.hip) --------------------------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * The network is built for one spatial size; real volumes are several times larger per axis.  The usual practice -- train on
+ * crops, analyse a large event tile by tile and stitch -- done at the voxel-list boundary on the device: a LARGE batch (lists as in
+ * ursn_voxel_batch, indices row-major in the shape `big`) goes up once, boxes of one size `tile` are cut out of it as a complete
+ * ursn_voxel_batch at prod(tile) voxels per event, and the gather head's rows come back to the large event's own list order.
+ *
+ * Box b covers the voxels x of event box_event[b] with 0 <= x[a] - box_origin[b][a] < tile[a] on every axis a.  An origin may be
+ * negative and a box may overhang the volume: what lies outside is background and contributes no entry.  Boxes may overlap, repeat
+ * and be empty; a box whose event lies outside [0, n) is empty.  The CORE of a box, core_lo[b][a] <= x[a] - box_origin[b][a] <
+ * core_hi[b][a] in box-local coordinates (NULL, NULL: the whole box), is the part whose voxels the box OWNS: with cores that
+ * partition the volume every list entry is owned by exactly one box.
+ *
+ * All calls below enqueue only and never synchronise; no global atomics, the scratch needs no initialisation, the same arguments
+ * give the same bits.  Null, misaligned, out-of-domain and too-small arguments are refused with a message before any launch. */
+typedef struct ursn_crop_desc {   /* every pointer is a DEVICE pointer */
+  int32_t ndim;                   /* 2 | 3 */
+  int32_t big[3];                 /* shape of the large events, prod < 2^31 (big[2] unused in 2-D) */
+  int32_t tile[3];                /* shape of every box, prod < 2^31 */
+  int32_t n;                      /* large events, 1..65535 */
+  int32_t boxes;                  /* B, 1..2^20 */
+  int64_t m_total;                /* list entries the arrays below hold, < 2^31: positions at or beyond it are never read */
+  const int64_t* offsets;         /* [n+1] as in ursn_voxel_batch */
+  const int32_t* index;           /* [m_total] row-major in `big`, strictly increasing per event */
+  const float* value;             /* [m_total]; value / label / weight / bg_weight may be NULL when no output asks for them */
+  const float* label;
+  const float* weight;
+  const float* bg_weight;         /* [n] */
+  const int32_t* box_event;       /* [B] */
+  const int32_t* box_origin;      /* [B, ndim] */
+  const int32_t* core_lo;         /* [B, ndim] box-local, or NULL together with core_hi */
+  const int32_t* core_hi;
+} ursn_crop_desc;
+
+/* count_out[b] = list entries inside box b, owned_out[b] = of those, entries inside its core: int64 [B] each (device).  Three
+ * launches: per box the contiguous range of the event's list that its slowest-axis slab covers (two binary searches), per part of
+ * that range the counts (wave64 ballot / popcount), per box their sum in part order.
+ * scratch: 8-byte aligned, >= ursn_crop_scratch_bytes(ndim, big, tile, boxes), which is 0 for arguments out of domain. */
+int ursn_crop_count(const ursn_crop_desc* d, int64_t* count_out, int64_t* owned_out, void* scratch, size_t scratch_bytes,
+                    void* stream);
+size_t ursn_crop_scratch_bytes(int32_t ndim, const int32_t* big, const int32_t* tile, int32_t boxes);
+
+typedef struct ursn_crop_out {    /* DEVICE pointers; a complete ursn_voxel_batch of B events at prod(tile) voxels, plus src / owned */
+  int64_t* offsets;               /* [B+1], offsets[0] = 0: the TRUE counts, whatever cap is */
+  int32_t* index;                 /* [cap] box-local row-major index, strictly increasing per box */
+  float* value;                   /* [cap] gathered from the large list; value / label / weight each optional (NULL) */
+  float* label;
+  float* weight;                  /* together with bg_weight */
+  float* bg_weight;               /* [B] bg_weight[b] = d->bg_weight[box_event[b]] (0 for a box of an event outside [0, n)) */
+  int32_t* src;                   /* [cap] position of the entry in the large list (optional) */
+  uint8_t* owned;                 /* [cap] 1: the entry lies inside the box's core, else 0 (optional) */
+  int64_t cap;                    /* entries whose position is >= cap are never written (ursn_labels_to_voxels' convention) */
+} ursn_crop_out;
+
+/* The boxes of d as one voxel batch: the range and count launches of ursn_crop_count, a one-workgroup scan in box order, and the
+ * write pass -- a stable compaction of each box's range, so every box's list is sorted without a sort.  A run of a longer box list
+ * is that list's arrays at an offset.  The result is what ursn_voxels_to_dense, ursn_voxels_to_dense_sym and ursn_infer_voxels take
+ * as it is.  Scratch as for ursn_crop_count. */
+int ursn_crop_write(const ursn_crop_desc* d, const ursn_crop_out* out, void* scratch, size_t scratch_bytes, void* stream);
+
+/* After ursn_infer_voxels on a crop batch: rows j < m with owned[j] == 1 are copied to row src[j] of the outputs, which are laid
+ * out in the large batch's list order (scores_out [rows_out, ncls] fp32, pred_out / ana_out [rows_out] uint8).  Rows that are not
+ * owned, or whose src lies outside [0, rows_out), write nothing.  Each (input, output) pair is optional and comes together, not all
+ * three absent.  With cores that partition the volume every output row is written exactly once over all crop batches: no atomics,
+ * and the order of the batches does not matter.  One launch; m = 0 launches nothing. */
+int ursn_scores_scatter(const int32_t* src, const uint8_t* owned, int64_t m, int32_t ncls, const float* scores,
+                        const uint8_t* pred, const uint8_t* ana, float* scores_out, uint8_t* pred_out, uint8_t* ana_out,
+                        int64_t rows_out, void* stream);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

@@ -95,6 +95,18 @@ class ursn_opt_tensor(C.Structure):
                 ("nonfinite", C.c_int64)]
 
 
+class ursn_crop_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("big", C.c_int32 * 3), ("tile", C.c_int32 * 3), ("n", C.c_int32), ("boxes", C.c_int32),
+                ("m_total", C.c_int64), ("offsets", C.c_void_p), ("index", C.c_void_p), ("value", C.c_void_p),
+                ("label", C.c_void_p), ("weight", C.c_void_p), ("bg_weight", C.c_void_p), ("box_event", C.c_void_p),
+                ("box_origin", C.c_void_p), ("core_lo", C.c_void_p), ("core_hi", C.c_void_p)]
+
+
+class ursn_crop_out(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("index", C.c_void_p), ("value", C.c_void_p), ("label", C.c_void_p),
+                ("weight", C.c_void_p), ("bg_weight", C.c_void_p), ("src", C.c_void_p), ("owned", C.c_void_p), ("cap", C.c_int64)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -190,6 +202,10 @@ _SIGS = {
     "ursn_grad_stats": (C.c_int, [_P, C.c_int32, _P]),
     "ursn_apply_adam_guarded": (C.c_int, [_P, C.POINTER(ursn_opt_desc), _P]),
     "ursn_opt_read": (C.c_int, [_P, C.POINTER(ursn_opt_status), C.POINTER(ursn_opt_tensor), _P]),
+    "ursn_crop_count": (C.c_int, [C.POINTER(ursn_crop_desc), _P, _P, _P, C.c_size_t, _P]),
+    "ursn_crop_scratch_bytes": (C.c_size_t, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
+    "ursn_crop_write": (C.c_int, [C.POINTER(ursn_crop_desc), C.POINTER(ursn_crop_out), _P, C.c_size_t, _P]),
+    "ursn_scores_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -110,6 +110,22 @@ class ssnet_config(object):
     LR_WARMUP_STEPS = 0
     LR_DECAY_STEPS = 0
     LR_DECAY_RATE = 1.
+    # not in the reference, whose network and events share one size.  All off by default and all need SPARSE_IO True; the synthetic
+    # IO then produces events of the LARGE shape while the network keeps the image shape of the input configuration.
+    # ANA_TILE [large spatial shape] (with TRAIN False) = ana_step uploads every batch once as a voxel list at that shape and
+    # analyses it tile by tile (ssnet_base.inference_tiled_voxel_scores: boxes of the network's size at stride tile - 2 *
+    # ANA_TILE_HALO, the boxes that own no listed voxel dropped, ANA_TILE_BATCH boxes per forward pass); every listed voxel gets the
+    # scores of the one tile that owns it and the output is SPARSE_SCORES' per-event lists.  Tiled scores are not the scores of a
+    # network built at the large shape (the receptive field exceeds any halo); ANA_BN 'moving' makes a tile independent of its
+    # batch-mates.  Refused together with ANA_CSV and ANA_TTA.  TRAIN_CROP [large spatial shape] (with TRAIN True) = every training
+    # and test minibatch is one crop of the network's size per large event, cut out on the device around a listed voxel
+    # (tiling.random_boxes, a function of (CROP_SEED, iteration, minibatch, rank) alone, so a resumed run repeats the crops);
+    # composes with AUGMENT, DEVICE_WEIGHTS and DEVICE_WEIGHT_NORM.  [] = off
+    ANA_TILE = []
+    ANA_TILE_HALO = 0
+    ANA_TILE_BATCH = 4
+    TRAIN_CROP = []
+    CROP_SEED = 0
 
     def __init__(self):
         pass
@@ -180,6 +196,15 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'ANA_TTA' and not all(type(c) is int and 0 <= c < 48 for c in value):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key in ('ANA_TILE', 'TRAIN_CROP') and not (len(value) in (0, 2, 3) and all(type(c) is int and c >= 1 for c in value)):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'ANA_TILE_HALO' and value < 0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'ANA_TILE_BATCH' and value < 1:
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             setattr(self, key, value)

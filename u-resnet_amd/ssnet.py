@@ -132,6 +132,14 @@ class VoxelBatch(object):
         return VoxelBatch(off, cat('index'), cat('value'), cat('label'), cat('weight'), cat('bg_weight'), V)
 
 
+class _DeviceVoxelBatch(object):
+    """What ``ssnet_base.upload_voxels`` returns: a large VoxelBatch resident on the device.  ``dev`` owns the memory, ``ptr`` maps
+    the array names to device addresses, ``big`` is the events' shape, ``n`` / ``m`` the events and list entries; ``offsets`` /
+    ``index`` are host copies (results are split and labelled with them), ``weight`` is None iff there is no weight list."""
+
+    __slots__ = ('dev', 'ptr', 'big', 'n', 'm', 'offsets', 'index', 'weight')
+
+
 def class_stats_from_counts(conf, other, score_sum, score_sq, nonzero=None):
     """The per-event quantities of example_scripts/ana_csv.py:67-116 from what ``ursn_class_stats`` returns: ``conf`` [n, C, C]
     (label, prediction) counts, ``other`` [n, 2] labels outside [0, C) {> 0, the rest}, ``score_sum`` / ``score_sq`` [n, C] fp64 sums
@@ -836,6 +844,28 @@ class ssnet_base(object):
         self.feed_stats['h2d_calls'] += 1
         self.feed_stats['staged_bytes'] += nbytes
 
+        base = dst.data_ptr()
+        b = _lib.ursn_voxel_batch()
+        b.n, b.voxels = n, V
+        b.offsets, b.index, b.value = base + at['offsets'], base + at['index'], base + at['value']
+        b.label = base + at['label'] if with_label else None
+        b.weight = base + at['weight'] if with_weight else None
+        b.bg_weight = base + at['bg_weight'] if with_weight else None
+        fd = self._expand_voxel_list(b, with_label, with_weight, symmetry)
+        done = torch.cuda.Event()
+        done.record(cur)
+        slot.consumed[i] = done                    # the list buffer is free once the expansion has read it
+        # inference_voxel_scores reads offsets / index again after the forward pass and moves `consumed` behind its own launch
+        self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
+        return fd
+
+    def _expand_voxel_list(self, b, with_label, with_weight, symmetry=None):
+        """A device-resident ``ursn_voxel_batch`` (``_feed_voxels``' copy, or a crop batch ``ursn_crop_write`` made) -> the dense
+        device tensors of ``feed_dict``, expanded on the compute stream into per-role device tensors (two sets, alternating,
+        registered as feed slots so ``last_feed`` / ``_mark_consumed`` treat them like fed tensors)."""
+        import torch
+        self._copy_stream()                         # the slot table lives with the copy stream
+        n, V = int(b.n), int(b.voxels)
         fd, roles = {}, ['data'] + (['label'] if with_label else []) + (['weight'] if with_weight else [])
         for role in roles:
             ds = self._feed_slots.setdefault('voxel_' + role, ssnet_base._FeedSlot())
@@ -845,13 +875,6 @@ class ssnet_base(object):
                 ds.dev[k] = torch.empty((n, V), dtype=torch.float32, device=self._device)
                 ds.consumed[k] = None
             fd['input_' + role] = ds.dev[k][:n]
-        base = dst.data_ptr()
-        b = _lib.ursn_voxel_batch()
-        b.n, b.voxels = n, V
-        b.offsets, b.index, b.value = base + at['offsets'], base + at['index'], base + at['value']
-        b.label = base + at['label'] if with_label else None
-        b.weight = base + at['weight'] if with_weight else None
-        b.bg_weight = base + at['bg_weight'] if with_weight else None
         if symmetry is None:
             _lib.check(_lib.load().ursn_voxels_to_dense(ctypes.byref(b), self._ptr(fd['input_data']),
                                                         self._ptr(fd.get('input_label')), self._ptr(fd.get('input_weight')),
@@ -861,29 +884,31 @@ class ssnet_base(object):
                                                             self._sym_ops(symmetry, n), self._ptr(fd['input_data']),
                                                             self._ptr(fd.get('input_label')), self._ptr(fd.get('input_weight')),
                                                             self._stream(None)))
-        done = torch.cuda.Event()
-        done.record(cur)
-        slot.consumed[i] = done                    # the list buffer is free once the expansion has read it
-        # inference_voxel_scores reads offsets / index again after the forward pass and moves `consumed` behind its own launch
-        self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
         return fd
 
-    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None, make_weight=None):
+    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None, make_weight=None, crop=None):
         """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure.  ``normalize_weight``: the expanded dense
         weight tensor is normalised per event on the device (``_normalize_fed_weight``), the same definition of the sum as the
         dense feed's; ``voxels.weight`` / ``bg_weight`` are not written and ``VoxelBatch.normalize_weights`` is not needed.
         ``symmetry``: as in ``accum_gradients``; the operation is index arithmetic inside the expansion's scatter and the list
         is neither rewritten nor re-sorted.  ``make_weight``: as in ``accum_gradients``; ``voxels.weight`` / ``bg_weight`` must be
-        None, only offsets, index, value and label travel, and the expansion has no weight role."""
+        None, only offsets, index, value and label travel, and the expansion has no weight role.  ``crop`` (crop training, see
+        "tiling" below): ``(big_batch, boxes)`` with ``big_batch`` from ``upload_voxels`` and ``boxes`` a ``tiling.Boxes`` of the
+        network's own size (``tiling.random_boxes``); ``voxels`` must then be None, the minibatch is one event per box, cut out of
+        the resident large batch by ``ursn_crop_write`` and fed through the same expansion, so ``symmetry``, ``make_weight`` and
+        ``normalize_weight`` compose as they do for a fed batch.  None: the call is made exactly as without the keyword."""
         if not self._trainable:
             raise RuntimeError('accum_gradients_voxels: constructed with trainable=False')
+        if crop is not None:
+            voxels = self._crop_source(voxels, crop, 'accum_gradients_voxels')
         if make_weight is not None:
             self._check_make_weight(make_weight, voxels.weight, 'accum_gradients_voxels')
         self._require_single_channel('accum_gradients_voxels')
+        feed = self._feed_voxels if crop is None else (lambda vb, **kw: self._feed_crop(vb, crop[1], sess, **kw))
         if make_weight is None:
-            fd = self._feed_voxels(voxels, symmetry=symmetry)
+            fd = feed(voxels, symmetry=symmetry)
         else:
-            fd = self._feed_voxels(voxels, with_weight=False, symmetry=symmetry)
+            fd = feed(voxels, with_weight=False, symmetry=symmetry)
             self._make_fed_weight(fd, make_weight, sess)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
@@ -901,15 +926,18 @@ class ssnet_base(object):
             return None, doc
         return [None, float(out[0]), float(out[1]), float(out[2])], doc
 
-    def run_test_voxels(self, sess, voxels, normalize_weight=False, make_weight=None):
-        """``run_test`` fed a VoxelBatch (``normalize_weight`` / ``make_weight`` as in ``accum_gradients_voxels``)."""
+    def run_test_voxels(self, sess, voxels, normalize_weight=False, make_weight=None, crop=None):
+        """``run_test`` fed a VoxelBatch (``normalize_weight`` / ``make_weight`` / ``crop`` as in ``accum_gradients_voxels``)."""
+        if crop is not None:
+            voxels = self._crop_source(voxels, crop, 'run_test_voxels')
         if make_weight is not None:
             self._check_make_weight(make_weight, voxels.weight, 'run_test_voxels')
         self._require_single_channel('run_test_voxels')
+        feed = self._feed_voxels if crop is None else (lambda vb, **kw: self._feed_crop(vb, crop[1], sess, **kw))
         if make_weight is None:
-            fd = self._feed_voxels(voxels)
+            fd = feed(voxels)
         else:
-            fd = self._feed_voxels(voxels, with_weight=False)
+            fd = feed(voxels, with_weight=False)
             self._make_fed_weight(fd, make_weight, sess)
         if normalize_weight:
             self._normalize_fed_weight(fd, sess)
@@ -1003,6 +1031,255 @@ class ssnet_base(object):
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
+        return res
+
+    # ------------------------------------------------------------------------------------------
+    # tiling: volumes larger than the network (not in the reference, whose events have the network's size; boxes, their
+    # cores and the numpy statement of the device passes: tiling.py)
+    # ------------------------------------------------------------------------------------------
+    def upload_voxels(self, vb, big):
+        """A device-resident LARGE batch: ``vb`` is a VoxelBatch whose events have the shape ``big`` (same number of axes as the
+        network, any extents with ``prod(big) < 2^31``), not the network's.  Every array is packed into one page-locked buffer
+        and travels in ONE copy on the copy stream, under the staging discipline of ``_feed_voxels``: the call returns once the
+        copy is done and never waits for compute.  Unlike a fed batch the device buffer belongs to the returned object and is
+        never reused: ``inference_tiled_voxel_scores`` and ``crop=`` read it as often as they like."""
+        import torch
+        self._require_single_channel('upload_voxels')
+        big = tuple(int(s) for s in big)
+        if len(big) != len(self._dims) - 1:
+            raise ValueError('upload_voxels: big = %r for a network of %d spatial axes' % (big, len(self._dims) - 1))
+        if vb.voxels != int(np.prod(big, dtype=np.int64)):
+            raise ValueError('upload_voxels: VoxelBatch of %d voxels per event, prod(big) = %d'
+                             % (vb.voxels, int(np.prod(big, dtype=np.int64))))
+        vb.validate()
+        if not 1 <= vb.n <= 65535:
+            raise ValueError('upload_voxels: %d events outside [1, 65535]' % vb.n)
+        parts = [(name, getattr(vb, name)) for name in ('offsets', 'index', 'value', 'label', 'weight', 'bg_weight')
+                 if getattr(vb, name) is not None]
+        at, nbytes = {}, 0
+        for name, a in parts:                      # every section starts on a 16-byte boundary
+            at[name] = nbytes
+            nbytes += (a.nbytes + 15) & ~15
+        nbytes = max(nbytes, 16)
+        cs = self._copy_stream()
+        cur = torch.cuda.current_stream(self._device)
+        pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        stage = pinned.numpy()
+        for name, a in parts:
+            stage[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
+        cs.wait_stream(cur)                        # as in _feed: the block may come back with kernels still pending on it
+        dev.record_stream(cs)
+        with torch.cuda.stream(cs):
+            dev.copy_(pinned, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cs)
+        cur.wait_event(ev)
+        ev.synchronize()                           # copy only; kernels of earlier minibatches keep running
+        self.feed_stats['h2d_bytes'] += nbytes
+        self.feed_stats['h2d_calls'] += 1
+        self.feed_stats['staged_bytes'] += nbytes
+        res = _DeviceVoxelBatch()
+        res.dev, res.big, res.n, res.m = dev, big, vb.n, int(vb.offsets[-1])
+        res.offsets, res.index = vb.offsets.copy(), vb.index.copy()
+        res.weight = None if vb.weight is None else True      # what _check_make_weight asks: is a weight list there
+        res.ptr = {name: dev.data_ptr() + at[name] for name, _ in parts}
+        return res
+
+    def _crop_desc(self, big_batch, boxes, dev_boxes, first=0, count=None):
+        """``ursn_crop_desc`` over a resident large batch and the run ``[first, first + count)`` of uploaded box arrays."""
+        nd = len(self._dims) - 1
+        d = _lib.ursn_crop_desc()
+        d.ndim, d.n, d.m_total = nd, big_batch.n, big_batch.m
+        for i in range(nd):
+            d.big[i], d.tile[i] = big_batch.big[i], int(self._dims[i])
+        B = len(boxes)
+        count = B - first if count is None else count
+        d.boxes = count
+        for name in ('offsets', 'index', 'value', 'label', 'weight', 'bg_weight'):
+            setattr(d, name, big_batch.ptr.get(name))
+        # dev_boxes: int32 [B * (1 + nd (+ 2 nd))] = event | origin | core_lo | core_hi
+        base = dev_boxes.data_ptr()
+        d.box_event = base + 4 * first
+        d.box_origin = base + 4 * (B + first * nd)
+        if boxes.core_lo is not None:
+            d.core_lo = base + 4 * (B + B * nd + first * nd)
+            d.core_hi = base + 4 * (B + 2 * B * nd + first * nd)
+        return d
+
+    def _upload_boxes(self, boxes, what):
+        import torch
+        from .tiling import Boxes
+        if not isinstance(boxes, Boxes):
+            raise ValueError('%s: boxes = %r, expected a tiling.Boxes' % (what, boxes))
+        if boxes.ndim != len(self._dims) - 1:
+            raise ValueError('%s: boxes of %d axes for a network of %d' % (what, boxes.ndim, len(self._dims) - 1))
+        if not 1 <= len(boxes) <= 1 << 20:
+            raise ValueError('%s: %d boxes outside [1, 2^20]' % (what, len(boxes)))
+        parts = [boxes.event, boxes.origin.reshape(-1)]
+        if boxes.core_lo is not None:
+            parts += [boxes.core_lo.reshape(-1), boxes.core_hi.reshape(-1)]
+        return torch.from_numpy(np.concatenate(parts)).to(self._device)
+
+    def _crop_scratch(self, d):
+        import torch
+        need = int(_lib.load().ursn_crop_scratch_bytes(d.ndim, d.big, d.tile, d.boxes))
+        if need == 0:
+            raise ValueError('tiling: shapes big = %r, tile = %r, %d boxes are out of domain'
+                             % (list(d.big)[:d.ndim], list(d.tile)[:d.ndim], d.boxes))
+        scratch = getattr(self, '_crop_scratch_buf', None)
+        if scratch is None or scratch.numel() * 8 < need:
+            scratch = self._crop_scratch_buf = torch.empty((need + 7) // 8, dtype=torch.int64, device=self._device)
+        return scratch
+
+    def _crop_source(self, voxels, crop, what):
+        """The refusals of ``crop=(big_batch, boxes)``; returns the resident large batch, which stands in for ``voxels``."""
+        from .tiling import Boxes
+        if voxels is not None:
+            raise ValueError('%s: crop cuts the minibatch out of the resident batch; voxels must be None' % what)
+        if not (isinstance(crop, (tuple, list)) and len(crop) == 2 and isinstance(crop[0], _DeviceVoxelBatch)
+                and isinstance(crop[1], Boxes)):
+            raise ValueError('%s: crop = %r, expected (upload_voxels(...), tiling.Boxes)' % (what, crop))
+        if len(crop[1]) > 65535:
+            raise ValueError('%s: %d boxes make a minibatch of more than 65535 events' % (what, len(crop[1])))
+        return crop[0]
+
+    def _feed_crop(self, big_batch, boxes, sess, with_label=True, with_weight=None, symmetry=None):
+        """``_feed_voxels`` for a crop: the minibatch (one event per box) is written on the device by ``ursn_crop_write`` into a
+        list buffer of its own and expanded by ``_expand_voxel_list`` like a fed list.  No count comes back to the host: the
+        buffers hold as many entries as the boxes' events have (a box holds no more than its event), capped at a full tile."""
+        import torch
+        if with_weight is None:
+            with_weight = self._use_weight
+        if with_weight and 'weight' not in big_batch.ptr:
+            sys.stderr.write('Network configured to use loss pixel-weighting. Cannot run w/ weight=None...\n')
+            raise TypeError
+        if with_label and 'label' not in big_batch.ptr:
+            raise ValueError('_feed_crop: the resident batch has no label list')
+        dev_boxes = self._upload_boxes(boxes, 'crop')
+        d = self._crop_desc(big_batch, boxes, dev_boxes)
+        scratch = self._crop_scratch(d)
+        B, V = len(boxes), self._label_size
+        per_event = np.diff(big_batch.offsets)
+        ev = boxes.event.astype(np.int64)
+        ok = (ev >= 0) & (ev < big_batch.n)
+        cap = int(np.minimum(per_event[np.where(ok, ev, 0)] * ok, V).sum())
+        f32 = lambda: torch.empty(max(cap, 1), dtype=torch.float32, device=self._device)
+        bufs = {'offsets': torch.empty(B + 1, dtype=torch.int64, device=self._device),
+                'index': torch.empty(max(cap, 1), dtype=torch.int32, device=self._device), 'value': f32()}
+        if with_label:
+            bufs['label'] = f32()
+        if with_weight:
+            bufs['weight'], bufs['bg_weight'] = f32(), torch.empty(B, dtype=torch.float32, device=self._device)
+        o = _lib.ursn_crop_out()
+        for name, t in bufs.items():
+            setattr(o, name, t.data_ptr())
+        o.cap = cap
+        _lib.check(_lib.load().ursn_crop_write(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), scratch.numel() * 8,
+                                               self._stream(sess)))
+        b = _lib.ursn_voxel_batch()
+        b.n, b.voxels = B, V
+        for name, t in bufs.items():
+            setattr(b, name, t.data_ptr())
+        fd = self._expand_voxel_list(b, with_label, with_weight, symmetry)
+        cur = torch.cuda.current_stream(self._device)
+        for t in list(bufs.values()) + [dev_boxes]:
+            t.record_stream(cur)                   # freed with the expansion still pending: the allocator waits for it
+        return fd
+
+    def inference_tiled_voxel_scores(self, sess, big_batch, big, halo=0, tile_batch=None, want=('scores', 'pred', 'ana')):
+        """``inference_voxel_scores`` for events LARGER than the network: every event of ``big_batch`` (``upload_voxels(vb, big)``,
+        or a VoxelBatch at ``prod(big)``, which is uploaded first) is analysed tile by tile with the network's own spatial size as
+        the tile, and every listed voxel gets the scores of the ONE tile that owns it.
+
+        1. ``tiling.grid(big, tile, halo)``: boxes at stride ``tile - 2 * halo`` per axis, the last one flush with the end of the
+           volume, and cores that partition the volume (the boundary lies in the middle of the overlap of two neighbours);
+        2. ``ursn_crop_count`` on the device and ONE small D2H of the per-box counts, the only synchronisation before the forwards;
+        3. every box that OWNS no listed voxel is dropped (most tiles of a sparse event);
+        4. the rest, in box order, in batches of ``tile_batch`` (None: 4);
+        5. per batch ``ursn_crop_write`` (the boxes as a voxel batch at the tile's size), the expansion, forward pass and gather
+           head of ``inference_voxel_scores``, then ``ursn_scores_scatter`` of the owned rows to the large event's list order.
+        The list goes up once and the scores come back once.  Returns the dict of ``inference_voxel_scores`` (without labels) per
+        large event, plus ``tiles_total``, ``tiles_run`` and ``forwards``.
+
+        What tiling is NOT: the network's receptive field exceeds any sensible halo, so the scores of a tiled event are not the
+        scores a network built at the large shape would give -- a voxel near a tile's border sees zeros where its neighbours in
+        the next tile are.  A larger halo moves the owned voxels away from the borders at the price of more tiles.  With
+        batch-statistics BatchNorm (the reference's only mode) a tile's scores also depend on its batch-mates and on how much of
+        it is empty, so ``construct(bn_moving=True)`` and ``set_bn_mode('moving')`` are the intended mode: a tile's result then
+        depends on the tile alone (up to the reduction order of a batch size, as for any batch)."""
+        import torch
+        from . import tiling
+        self._require_single_channel('inference_tiled_voxel_scores')
+        want = tuple(want)
+        if not want or any(w not in ('scores', 'pred', 'ana') for w in want):
+            raise ValueError("inference_tiled_voxel_scores: want = %r, expected a non-empty subset of ('scores', 'pred', 'ana')"
+                             % (want,))
+        if 'ana' in want and self._num_class < 3:
+            raise ValueError('inference_tiled_voxel_scores: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
+        if tile_batch is not None and int(tile_batch) < 1:
+            raise ValueError('inference_tiled_voxel_scores: tile_batch = %r < 1' % (tile_batch,))
+        big = tuple(int(s) for s in big)
+        if not isinstance(big_batch, _DeviceVoxelBatch):
+            big_batch = self.upload_voxels(big_batch, big)
+        if big_batch.big != big:
+            raise ValueError('inference_tiled_voxel_scores: the resident batch has shape %r, big = %r' % (big_batch.big, big))
+        lib, C, n, M, V = _lib.load(), self._num_class, big_batch.n, big_batch.m, self._label_size
+        tile = tuple(int(d) for d in self._dims[:-1])
+        boxes = tiling.grid(big, tile, halo, n)
+        dev_boxes = self._upload_boxes(boxes, 'inference_tiled_voxel_scores')
+        d = self._crop_desc(big_batch, boxes, dev_boxes)
+        scratch = self._crop_scratch(d)
+        counts = torch.empty((2, len(boxes)), dtype=torch.int64, device=self._device)
+        _lib.check(lib.ursn_crop_count(ctypes.byref(d), self._ptr(counts[0]), self._ptr(counts[1]), self._ptr(scratch),
+                                       scratch.numel() * 8, self._stream(sess)))
+        host_counts = counts.cpu().numpy()
+        keep = np.flatnonzero(host_counts[1] > 0)
+        kinds = {'scores': ((max(M, 1), C), torch.float32), 'pred': ((max(M, 1),), torch.uint8), 'ana': ((max(M, 1),), torch.uint8)}
+        out = {w: torch.zeros(kinds[w][0], dtype=kinds[w][1], device=self._device) for w in want}
+        forwards = 0
+        if keep.size:
+            run = boxes.select(keep)
+            per_box = host_counts[0][keep]
+            dev_run = self._upload_boxes(run, 'inference_tiled_voxel_scores')
+            tb = min(4 if tile_batch is None else int(tile_batch), len(run))
+            self._ensure_handle(tb)
+            cap = max(int(per_box[i:i + tb].sum()) for i in range(0, len(run), tb))
+            i32 = lambda k: torch.empty(max(k, 1), dtype=torch.int32, device=self._device)
+            bufs = {'offsets': torch.empty(tb + 1, dtype=torch.int64, device=self._device), 'index': i32(cap),
+                    'value': torch.empty(max(cap, 1), dtype=torch.float32, device=self._device), 'src': i32(cap),
+                    'owned': torch.empty(max(cap, 1), dtype=torch.uint8, device=self._device)}
+            rows = {w: torch.empty((max(cap, 1),) + kinds[w][0][1:], dtype=kinds[w][1], device=self._device) for w in want}
+            o = _lib.ursn_crop_out()
+            for name, t in bufs.items():
+                setattr(o, name, t.data_ptr())
+            for first in range(0, len(run), tb):
+                nb = min(tb, len(run) - first)
+                m = int(per_box[first:first + nb].sum())
+                dr = self._crop_desc(big_batch, run, dev_run, first, nb)
+                o.cap = m
+                _lib.check(lib.ursn_crop_write(ctypes.byref(dr), ctypes.byref(o), self._ptr(scratch), scratch.numel() * 8,
+                                               self._stream(sess)))
+                b = _lib.ursn_voxel_batch()
+                b.n, b.voxels = nb, V
+                b.offsets, b.index, b.value = o.offsets, o.index, o.value
+                fd = self._expand_voxel_list(b, False, False)
+                _lib.check(lib.ursn_infer_voxels(self._handle, self._ptr(fd['input_data']), None, nb, ctypes.c_void_p(o.offsets),
+                                                 ctypes.c_void_p(o.index), m, self._ptr(rows.get('scores')),
+                                                 self._ptr(rows.get('pred')), self._ptr(rows.get('ana')), None, self._stream(sess)))
+                _lib.check(lib.ursn_scores_scatter(ctypes.c_void_p(o.src), ctypes.c_void_p(o.owned), m, C,
+                                                   self._ptr(rows.get('scores')), self._ptr(rows.get('pred')),
+                                                   self._ptr(rows.get('ana')), self._ptr(out.get('scores')),
+                                                   self._ptr(out.get('pred')), self._ptr(out.get('ana')), M, self._stream(sess)))
+                self._last_feed = fd
+                self._mark_consumed(fd)
+                forwards += 1
+        off = big_batch.offsets
+        res = {'index': [big_batch.index[off[i]:off[i + 1]].copy() for i in range(n)]}
+        for w in want:
+            host = out[w][:M].cpu().numpy()
+            res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
+        res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 
     # ------------------------------------------------------------------------------------------

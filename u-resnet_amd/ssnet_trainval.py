@@ -32,7 +32,7 @@ import time
 
 import numpy as np
 
-from . import optim, symmetry
+from . import optim, symmetry, tiling
 from .config import ssnet_config
 from .ssnet import HipSession, ana_csv_header, ana_csv_row
 from .synthetic_io import synthetic_threadio
@@ -131,8 +131,14 @@ class ssnet_trainval(object):
             io.shard(d.get_rank(), d.get_world_size())   # rank r reads entries r, r+W, r+2W, ...
         if self._cfg.SPARSE_IO:
             io.produce_voxels()
+            if self._big_shape():   # ANA_TILE / TRAIN_CROP: the voxel batches hold events of the large shape
+                io.produce_large(self._big_shape())
         io.start_manager(batch)
         return io
+
+    def _big_shape(self):
+        """The large spatial shape of a tiled run: TRAIN_CROP when training, ANA_TILE when analysing; [] = the keys are off."""
+        return list(self._cfg.TRAIN_CROP if self._cfg.TRAIN else self._cfg.ANA_TILE)
 
     def _advance_main(self):
         keep = not self._cfg.TRAIN
@@ -149,6 +155,13 @@ class ssnet_trainval(object):
         if cfg.ANA_TTA and not cfg.TRAIN and cfg.ANA_CSV:
             raise ValueError('ANA_TTA cannot be combined with ANA_CSV: the per-class statistics are reduced on the device from the '
                              'logits of ONE forward pass, a test-time average only exists as scores after several passes')
+        if self._big_shape():
+            key = 'TRAIN_CROP' if cfg.TRAIN else 'ANA_TILE'
+            if not cfg.SPARSE_IO:
+                raise ValueError('%s needs SPARSE_IO True: large events travel as voxel lists only' % key)
+            if not cfg.TRAIN and (cfg.ANA_CSV or cfg.ANA_TTA):
+                raise ValueError('ANA_TILE cannot be combined with ANA_CSV or ANA_TTA: a tiled analysis returns the scores at the '
+                                 'listed voxels of the large event')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -267,14 +280,16 @@ class ssnet_trainval(object):
         if self._weight_spec is not None:   # DEVICE_WEIGHTS: the weight lists stay on the host
             from .ssnet import VoxelBatch
             return VoxelBatch(vb.offsets, vb.index, vb.value, vb.label, None, None, vb.voxels)
-        if self._cfg.USE_WEIGHTS and not self._cfg.DEVICE_WEIGHT_NORM:
-            vb.normalize_weights()
+        if self._cfg.USE_WEIGHTS and not self._cfg.DEVICE_WEIGHT_NORM and not self._big_shape():
+            vb.normalize_weights()   # TRAIN_CROP: the event that is fed only exists on the device, see _norm_kw
         return vb
 
     def _norm_kw(self):
         """Keywords of the network calls that are fed what ``_pull`` / ``_pull_voxels`` returned.  Empty with the defaults
         DEVICE_WEIGHT_NORM False and DEVICE_WEIGHTS '': those calls are then made exactly as before."""
         kw = {'normalize_weight': True} if self._cfg.DEVICE_WEIGHT_NORM and self._cfg.USE_WEIGHTS else {}
+        if self._big_shape() and self._cfg.USE_WEIGHTS:   # TRAIN_CROP: the sum over a crop can only be taken on the device
+            kw['normalize_weight'] = True
         if self._weight_spec is not None:   # DEVICE_WEIGHTS: the call makes the weights from the label it is fed
             kw['make_weight'] = self._weight_spec
         return kw
@@ -289,6 +304,24 @@ class ssnet_trainval(object):
         d = _dist()
         codes = symmetry.group(c.AUGMENT, [int(x) for x in self._net._dims[:-1]])
         return {'symmetry': symmetry.draw(c.AUGMENT_SEED, self._iteration, minibatch, d.get_rank() if d is not None else 0, n, codes)}
+
+    def _crop_args(self, vb, minibatch):
+        """The ``voxels`` argument and the extra keyword of the ``*_voxels`` calls.  With the default TRAIN_CROP [] the batch
+        itself and nothing: those calls are then made exactly as before.  Else the large batch goes up once
+        (``upload_voxels``) and the call cuts one crop of the network's size per event out of it on the device; the boxes are a
+        function of (CROP_SEED, iteration, minibatch, rank) alone (``minibatch`` -1: the test stream), so a resumed run repeats
+        them and every rank draws its own."""
+        big = self._big_shape()
+        if not big:
+            return vb, {}
+        d = _dist()
+        seed = [int(self._cfg.CROP_SEED), int(self._iteration), int(minibatch) + 1, d.get_rank() if d is not None else 0]
+        boxes = tiling.random_boxes(seed, vb, big, [int(x) for x in self._net._dims[:-1]])
+        return None, {'crop': (self._net.upload_voxels(vb, big), boxes)}
+
+    def _run_test_voxels(self, test):
+        voxels, crop = self._crop_args(test, -1)
+        return self._net.run_test_voxels(self._sess, voxels, **self._norm_kw(), **crop)
 
     def _step_lr(self):
         """The learning rate of the current iteration's optimiser step: what the step is given, the report line prints and the
@@ -309,7 +342,9 @@ class ssnet_trainval(object):
         for minibatch in range(c.NUM_MINIBATCHES):
             if c.SPARSE_IO:
                 vb = self._pull_voxels(self._input_main)
-                res, doc = net.accum_gradients_voxels(self._sess, vb, fetch=want_metrics, **norm, **self._sym_kw(minibatch, vb.n))
+                voxels, crop = self._crop_args(vb, minibatch)
+                res, doc = net.accum_gradients_voxels(self._sess, voxels, fetch=want_metrics, **norm, **crop,
+                                                      **self._sym_kw(minibatch, vb.n))
             else:
                 data, label, weight = self._pull(self._input_main, c.KEYWORD_DATA, c.KEYWORD_LABEL, c.KEYWORD_WEIGHT)
                 res, doc = net.accum_gradients(sess=self._sess, input_data=data, input_label=label, input_weight=weight,
@@ -363,7 +398,7 @@ class ssnet_trainval(object):
             tested = None
             if test is not None:
                 norm = self._norm_kw()
-                tested = (self._net.run_test_voxels(self._sess, test, **norm) if self._cfg.SPARSE_IO
+                tested = (self._run_test_voxels(test) if self._cfg.SPARSE_IO
                           else self._net.run_test(self._sess, *test, **norm))
             if _is_rank0():
                 stamp = datetime.datetime.fromtimestamp(time.time()).strftime('%Y-%m-%d %H:%M:%S')
@@ -391,7 +426,7 @@ class ssnet_trainval(object):
                 self._writer_train.add_summary(summ, plan.iteration)
             if self._writer_test and test is not None:
                 if self._cfg.SPARSE_IO:
-                    t3, _ = self._net.run_test_voxels(self._sess, test, **self._norm_kw())
+                    t3, _ = self._run_test_voxels(test)
                     tsum = {'loss': t3[0], 'accuracy_all': t3[1], 'accuracy_nonzero': t3[2]}
                 else:
                     tsum = self._net.make_summary(self._sess, *test, **self._norm_kw())
@@ -427,6 +462,8 @@ class ssnet_trainval(object):
         io = self._input_main
         vb = io.fetch_voxels()
         entries = io.fetch_entries()
+        if self._cfg.ANA_TILE:
+            return self._ana_step_tiled(vb, entries, batch_mode)
         if self._cfg.SPARSE_SCORES:
             return self._ana_step_voxel_scores(vb, entries, batch_mode)
         softmax = data = label = None
@@ -479,6 +516,37 @@ class ssnet_trainval(object):
                        'label': vb.label[off[i]:off[i + 1]].copy(), 'scores': r['scores'][i], 'pred': r['pred'][i]}
                       for i in range(vb.n)]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
+        self._advance_main()
+        return result
+
+    def _ana_step_tiled(self, vb, entries, batch_mode):
+        """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
+        (``inference_tiled_voxel_scores``).  Records and the interactive result are those of ``_ana_step_voxel_scores`` with
+        indices in the large shape, plus ``tiles`` = (run, total).  Only the listed voxels have scores: ``acc_nonzero`` (over
+        data > 0, which all lie in the list) is exact, ``acc_all`` is None."""
+        c = self._cfg
+        want = ('scores', 'pred') + (('ana',) if self._output else ())
+        r = self._net.inference_tiled_voxel_scores(self._sess, vb, c.ANA_TILE, halo=c.ANA_TILE_HALO, tile_batch=c.ANA_TILE_BATCH,
+                                                   want=want)
+        lit = vb.value > 0
+        hit = np.concatenate(r['pred']).astype(np.float32) == vb.label
+        acc_all, acc_nonzero = None, float(hit[lit].sum()) / max(int(lit.sum()), 1)
+        if self._output:
+            for i in range(vb.n):
+                keep = r['ana'][i] != 0
+                print('Entry', entries[i], 'Acc', acc_nonzero, 'Tiles', r['tiles_run'], 'of', r['tiles_total'])
+                np.save(self._output, r['index'][i][keep])
+                np.save(self._output, r['ana'][i][keep])
+                np.save(self._output, r['scores'][i][keep])
+            self._output.flush()
+        result = None
+        if not batch_mode:
+            off = vb.offsets
+            events = [{'index': r['index'][i], 'value': vb.value[off[i]:off[i + 1]].copy(),
+                       'label': vb.label[off[i]:off[i + 1]].copy(), 'scores': r['scores'][i], 'pred': r['pred'][i]}
+                      for i in range(vb.n)]
+            result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
+                      'tiles': (r['tiles_run'], r['tiles_total'])}
         self._advance_main()
         return result
 

@@ -155,6 +155,7 @@ class synthetic_threadio(object):
         self._cursor = 0
         self._batch = 0
         self._voxels = False
+        self._large = None
 
     def configure(self, cfg):
         """cfg: dict with 'filler_cfg' = path of a synthetic input cfg or an inline dict
@@ -177,6 +178,15 @@ class synthetic_threadio(object):
     def produce_voxels(self, on=True):
         """Also build every batch as a VoxelBatch on the producer thread (``fetch_voxels``); call before start_manager."""
         self._voxels = bool(on)
+
+    def produce_large(self, big):
+        """Tiling (ANA_TILE / TRAIN_CROP): the voxel batches hold events of the spatial shape ``big`` instead of ``Dims`` -- the
+        same generator at the large shape, one event at a time.  ``fetch_data(key).dim()`` keeps reporting ``Dims`` (the network
+        is built from it) and the dense buffers are not filled.  Needs ``produce_voxels``; call before start_manager."""
+        big = [int(s) for s in big]
+        if len(big) != len(self._dims) - 1 or min(big) < 1:
+            raise ValueError('produce_large: big = %r for Dims = %r' % (big, self._dims))
+        self._large = big + [self._dims[-1]]
 
     def start_manager(self, batch_size):
         self._batch = int(batch_size)
@@ -204,6 +214,14 @@ class synthetic_threadio(object):
         n = self._batch
         data, label, weight = bufs['data'], bufs['label'], bufs['weight']
         entries = []
+        if self._large is not None and self._voxels:
+            from .ssnet import VoxelBatch
+            events = []
+            for i in range(n):
+                e = (self._offset + (first + i) * self._stride) % self._num_entries
+                events.append(dense_to_voxels(*self._gen(self._large, self._num_class, e)))
+                entries.append(e)
+            return dict(data=data, label=label, weight=weight, entries=entries, voxels=VoxelBatch.concat(events))
         for i in range(n):
             e = (self._offset + (first + i) * self._stride) % self._num_entries
             d, l, w = self._gen(self._dims, self._num_class, e)
