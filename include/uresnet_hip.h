@@ -777,6 +777,35 @@ int ursn_scores_scatter(const int32_t* src, const uint8_t* owned, int64_t m, int
                         const uint8_t* pred, const uint8_t* ana, float* scores_out, uint8_t* pred_out, uint8_t* ana_out,
                         int64_t rows_out, void* stream);
 
+/* ---- frozen-BatchNorm training (elementwise.hip, bf16_elementwise.hip) ----------------------------------------------------------
+ * Appended functions only: URSN_ABI_VERSION stays 9.
+ * Fine-tuning on FIXED statistics: the forward is the frozen one of ursn_bn_set_frozen, and the backward differentiates through
+ * constants mean / rstd instead of through a batch's moments.  With g = dy * relu-mask
+ *     dz = rstd * g        d(beta) += sum g        (join: dz2 = rstd2 * g, d(beta2) += sum g;  dres (=|+=) g)
+ * -- both projection terms of the batch form, mean(g) and xhat * mean(g * xhat), are gone (beta stays trainable).  Where a layer's
+ * BatchNorm backward ran as a reduce pass and an apply pass it is ONE pass that reads g and what the mask needs (y, or z for
+ * bn(z) > 0 with the forward's own fmaf, or the mask bits / bytes), writes dz and sums g per channel on the way; the sum goes through
+ * the batch form's partials and finalise, in its order, so d(beta) has the same bits on either route.  Where the sums come out of
+ * the epilogue of the kernel that produced dy, or dz is formed on load by the layer's data-gradient kernel, those kernels run
+ * unchanged and the finalise hands them zero means.  URSN_BN_FROZEN_FUSED=0 (A/B) takes that second route everywhere.
+ * When profiling, the single pass is recorded under pass id 5 as "bn_bwd_frozen" / "bbn_bwd_frozen" with the bytes it moves.
+ *
+ * ursn_bn_frozen_train: on != 0 lets the training entries run while the handle is frozen -- ursn_accum_step, ursn_forward_logits and
+ * ursn_backward_logits, on both plans -- with the frozen forward and the derivative above.  Refused with a message unless the handle
+ * is frozen (ursn_bn_set_frozen); ursn_bn_set_frozen(net, 0) clears it.  ursn_bn_update stays refused after such a forward (its mean
+ * / rstd are the moving statistics), a step in this mode never enters or replays a URSN_GRAPH graph, and a pending
+ * ursn_forward_logits does not survive a change of this setting.  Host state only: no launch, no synchronisation. */
+int ursn_bn_frozen_train(ursn_net* net, int32_t on);
+/* Op level, fp32: g = dy * (relu ? mask : 1) with mask = y > 0 (y given) or bn(z) > 0 (y NULL: z, mean, rstd, beta given);
+ * dz = rstd * g, dbeta += sum g.  Compact [voxels, channels] tensors; z, mean and beta may be NULL where the mask does not need
+ * them.  scratch >= ursn_bn_scratch_bytes(voxels, channels).  Two launches, enqueues only. */
+int ursn_bn_backward_frozen(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
+                            const float* beta, float* dz, float* dbeta, int64_t voxels, int32_t channels, int32_t relu,
+                            void* scratch, size_t scratch_bytes, void* stream);
+/* Op level, bf16: ursn_bn_bf16_backward's descriptor, unchanged, with its mean / rstd (mean2 / rstd2) used as given; the single pass
+ * reads z only for the bn(z) > 0 mask and z2 never.  scratch >= ursn_bn_bf16_scratch_bytes(voxels, channels). */
+int ursn_bn_bf16_backward_frozen(const ursn_bn_bf16_desc* d, void* scratch, size_t scratch_bytes, void* stream);
+
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
 

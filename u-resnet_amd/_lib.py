@@ -188,6 +188,9 @@ _SIGS = {
     "ursn_bn_update": (C.c_int, [_P, C.c_double, _P]),
     "ursn_bn_moving_update": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_double, C.c_float, _P]),
     "ursn_bn_set_frozen": (C.c_int, [_P, C.c_int32]),
+    "ursn_bn_frozen_train": (C.c_int, [_P, C.c_int32]),
+    "ursn_bn_backward_frozen": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
+    "ursn_bn_bf16_backward_frozen": (C.c_int, [C.POINTER(ursn_bn_bf16_desc), _P, C.c_size_t, _P]),
     "ursn_make_weights": (C.c_int, [C.POINTER(ursn_make_weights_desc), _P, _P, _P, _P, C.c_size_t, _P]),
     "ursn_make_weights_scratch_bytes": (C.c_size_t, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32]),
     "ursn_opt_state_size": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32]),

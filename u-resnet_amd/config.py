@@ -81,9 +81,13 @@ class ssnet_config(object):
     # UResNet/<scope>/BatchNorm/moving_mean | moving_variance and a restore loads them when the file has them (else 0 / 1).
     # ANA_BN 'batch' | 'moving' = which statistics the ana driver's forward passes normalise with, in all its output modes;
     # 'moving' makes an event's result independent of the events that share its batch.  Defaults: off, as the reference behaves
+    # TRAIN_BN 'batch' | 'frozen' = which statistics the TRAINING steps normalise with.  'frozen' fine-tunes on the loaded moving
+    # statistics (small batches, crops, a new sample): forward and backward treat them as constants, the moving buffer is not
+    # updated, weights and beta train as usual; it implies the moving buffer (as BN_MOVING allocates it).  Ignored without TRAIN
     BN_MOVING = False
     BN_DECAY = 0.999
     ANA_BN = 'batch'
+    TRAIN_BN = 'batch'
     # not in the reference, where the pixel weight is a stored larcv product (config/input_train3d.cfg: Tensor3DProducer "weight")
     # that an upstream module wrote from the label.  DEVICE_WEIGHTS 'class' | 'invfreq' = the train and test steps make the
     # weights on the device from the label (ursn_make_weights; weights.py holds the definition): KEYWORD_WEIGHT is not fetched,
@@ -172,6 +176,9 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'ANA_BN' and value not in ('batch', 'moving'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'TRAIN_BN' and value not in ('batch', 'frozen'):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'BN_DECAY' and not 0.0 <= value <= 1.0:

@@ -202,8 +202,10 @@ struct BBnBwdArgs {   // as BnBwdArgs (ursn_common.h) on bf16 tensors; the relu 
   const double* pre_partial; int pre_nblocks;   // the reductions came out of the producing kernel's epilogue: [pre_nblocks][3][C]
   const unsigned char* mask;                    // relu mask bytes written by launch_bbn_act (mask_out); replaces the y reads
   const bf16_t* dy2; int dy2cs;                 // second contribution to the output gradient (C = 8, mask = bn(z) > 0 only): g = dy + dy2
+  int frozen;                                   // as BnBwdArgs.frozen: fixed statistics, dz = rstd * g (bbn_bwd_frozen_kernel without pre_partial)
 };
 int launch_bbn_bwd(const BBnBwdArgs& a, hipStream_t s);
+static inline bool bbn_bwd_single_pass(const BBnBwdArgs& a) { return a.frozen && !a.pre_partial && ursn_bn_frozen_fused(); }
 size_t bbn_scratch_bytes(int64_t V, int C);
 struct BHeadArgs {    // logits = bn(z); z, dlogits bf16 with channel stride 8
   const bf16_t* z; int z_cs; const float* mean; const float* rstd; const float* beta;

@@ -348,6 +348,81 @@ __global__ __launch_bounds__(256) void bbn_bwd_apply_kernel(BBnBwdArgs a, int sh
   }
 }
 
+// Frozen-BatchNorm backward in ONE pass (fixed mean / rstd): dz = rstd * g, dz2 = rstd2 * g, dres (=|+=) g, and sum g on the way.
+// Operands as bbn_bwd_apply_kernel takes them; z is loaded only for MASK == 2 and z2 never.  It runs on the REDUCE grid with the
+// reduce kernel's chunk walk and per-thread fp32 sums, and stores row 0 of the same [block][3][C] partials: the unchanged finalise
+// then adds the dbeta bits the two-pass form adds.
+template <bool C8, int MASK, bool HAS2, bool DRES, bool D2 = false>
+__global__ __launch_bounds__(256) void bbn_bwd_frozen_kernel(BBnBwdArgs a, int shift, double* __restrict__ partial) {
+  BEW_MAP;
+  float acc[1][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[0][j] = 0.f;
+  if (c < a.C) {
+    float rs[8], rs2[8], be[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      rs[j] = a.rstd[c + j];
+      rs2[j] = HAS2 ? a.rstd2[c + j] : 0.f;
+      be[j] = MASK == 2 ? a.beta[c + j] - a.mean[c + j] * rs[j] : 0.f;
+    }
+    const bool dacc = DRES && a.dres_accumulate;
+    for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+      const int64_t vb = ch * chunkv + vr;
+      auto body = [&](auto FULL) {
+        constexpr bool full = decltype(FULL)::value;
+        u32x4 gp[U], zp[U], yp[U], drp[U], g2p[U];
+        unsigned mk[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int64_t v = vb + (int64_t)u * VPB;
+          if (full || v < a.V) {
+            gp[u] = ld16(a.dy + v * a.dycs + c);
+            if constexpr (MASK == 3) mk[u] = a.mask[v * (a.C >> 3) + (c >> 3)];
+            if constexpr (D2) g2p[u] = ld16(a.dy2 + v * a.dy2cs + c);
+            if constexpr (MASK == 2) zp[u] = ld16(a.z + v * a.zcs + c);
+            if constexpr (MASK == 1) yp[u] = ld16(a.y + v * a.ycs + c);
+            if constexpr (DRES) { if (dacc) drp[u] = ld16(a.dres + v * a.drescs + c); }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int64_t v = vb + (int64_t)u * VPB;
+          if (!full && v >= a.V) continue;
+          float g[8], z[8], y[8], dr[8], dz[8], dz2[8];
+          unpack8(gp[u], g);
+          if constexpr (D2) {
+            float g2[8];
+            unpack8(g2p[u], g2);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) g[j] += g2[j];
+          }
+          if constexpr (MASK == 2) unpack8(zp[u], z);
+          if constexpr (MASK == 1) unpack8(yp[u], y);
+          if constexpr (DRES) { if (dacc) unpack8(drp[u], dr); }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float gj = g[j];
+            if constexpr (MASK == 1) { if (!(y[j] > 0.f)) gj = 0.f; }
+            if constexpr (MASK == 2) { if (!(fmaf(z[j], rs[j], be[j]) > 0.f)) gj = 0.f; }
+            if constexpr (MASK == 3) { if (!((mk[u] >> j) & 1u)) gj = 0.f; }
+            acc[0][j] += gj;
+            dz[j] = rs[j] * gj;
+            if constexpr (HAS2) dz2[j] = rs2[j] * gj;
+            if constexpr (DRES) dr[j] = dacc ? dr[j] + gj : gj;
+          }
+          st16(a.dz + v * a.dzcs + c, pack8(dz));
+          if constexpr (HAS2) st16(a.dz2 + v * a.dz2cs + c, pack8(dz2));
+          if constexpr (DRES) st16(a.dres + v * a.drescs + c, pack8(dr));
+        }
+      };
+      if ((ch + 1) * chunkv <= a.V) body(std::true_type{});
+      else body(std::false_type{});
+    }
+  }
+  block_reduce_store8<1>(acc, CP, a.C, partial + (size_t)blockIdx.x * 3 * a.C);
+}
+
 // ---- head (lib/ssnet.py:57-71): logits = bn(z), 8-channel bf16 pieces ----------------------------------------------------------
 __global__ __launch_bounds__(256) void bhead_kernel(BHeadArgs a, double* __restrict__ partial) {
   const int64_t P = (int64_t)a.n * a.pix;
@@ -539,13 +614,28 @@ int launch_bbn_bwd(const BBnBwdArgs& a, hipStream_t s) {
 #define BRED3(c8) do { if (mask == 0) BRED2(c8, 0); else if (mask == 1) BRED2(c8, 1); else if (mask == 3) BRED2(c8, 3); else BRED2(c8, 2); } while (0)
   const bool d2 = a.dy2 != nullptr;
   if (d2) URSN_REQUIRE(a.C == 8 && mask == 2 && !a.z2 && !a.dres && !a.pre_partial && (a.dy2cs & 7) == 0, "bf16 bn_bwd: a second gradient operand is supported for 8-channel conv-BN-ReLU layers only");
+  if (bbn_bwd_single_pass(a)) {   // fixed statistics: one pass on the reduce grid, then the finalise for dbeta
+#define BFRZ(c8, mk, h2, dr) hipLaunchKernelGGL((bbn_bwd_frozen_kernel<c8, mk, h2, dr>), dim3(rgrid), dim3(256), 0, s, a, m.shift, partial)
+#define BFRZ1(c8, mk, h2) do { if (a.dres) BFRZ(c8, mk, h2, true); else BFRZ(c8, mk, h2, false); } while (0)
+#define BFRZ2(c8, mk) do { if (a.z2) BFRZ1(c8, mk, true); else BFRZ1(c8, mk, false); } while (0)
+#define BFRZ3(c8) do { if (mask == 0) BFRZ2(c8, 0); else if (mask == 1) BFRZ2(c8, 1); else if (mask == 3) BFRZ2(c8, 3); else BFRZ2(c8, 2); } while (0)
+    if (d2) hipLaunchKernelGGL((bbn_bwd_frozen_kernel<true, 2, false, false, true>), dim3(rgrid), dim3(256), 0, s, a, m.shift, partial);
+    else if (a.C == 8) BFRZ3(true); else BFRZ3(false);
+#undef BFRZ3
+#undef BFRZ2
+#undef BFRZ1
+#undef BFRZ
+    URSN_HIP(hipGetLastError());
+    return launch_bn_bwd_final(partial, rgrid, a.C, a.V, finals, a.dbeta, a.z2 ? a.dbeta2 : nullptr, a.Cw > 0 ? a.Cw : a.C, s, nullptr, nullptr,
+                               nullptr, nullptr, 1);
+  }
   if (a.pre_partial) { /* sums taken by the kernel that produced dy */ }
   else if (d2) hipLaunchKernelGGL((bbn_bwd_reduce_kernel<true, 2, false, true>), dim3(rgrid), dim3(256), 0, s, a, m.shift, partial);
   else if (a.C == 8) BRED3(true);
   else BRED3(false);
   URSN_HIP(hipGetLastError());
   URSN_TRY(launch_bn_bwd_final(a.pre_partial ? a.pre_partial : partial, a.pre_partial ? a.pre_nblocks : rgrid, a.C, a.V, finals, a.dbeta,
-                               a.z2 ? a.dbeta2 : nullptr, a.Cw > 0 ? a.Cw : a.C, s));
+                               a.z2 ? a.dbeta2 : nullptr, a.Cw > 0 ? a.Cw : a.C, s, nullptr, nullptr, nullptr, nullptr, a.frozen ? 1 : 0));
 #define BAPP(c8, mk, h2, dr) hipLaunchKernelGGL((bbn_bwd_apply_kernel<c8, mk, h2, dr>), dim3(agrid), dim3(256), 0, s, a, m.shift, (const double*)finals)
 #define BAPP1(c8, mk, h2) do { if (a.dres) BAPP(c8, mk, h2, true); else BAPP(c8, mk, h2, false); } while (0)
 #define BAPP2(c8, mk) do { if (a.z2) BAPP1(c8, mk, true); else BAPP1(c8, mk, false); } while (0)

@@ -24,6 +24,7 @@ struct BnmState {
   int64_t total = 0;              // 2 * sum C: floats of the moving buffer
   float* moving = nullptr;        // caller-owned, attached
   bool frozen = false;
+  bool frozen_train = false;      // frozen only: the training entries run, with the fixed-statistics derivative (ursn_bn_frozen_train)
   int last_fwd = 0;               // 0: no forward has run, 1: batch statistics, 2: frozen
   float eps = 1e-3f;
 };

@@ -744,6 +744,25 @@ extern "C" int ursn_bn_backward(const float* dy, const float* y, const float* z,
   return launch_bn_bwd(a, s);
 }
 
+// fixed statistics: dz = rstd * g, dbeta += sum g (the single pass, or with URSN_BN_FROZEN_FUSED=0 reduce + zero-mean finalise + apply)
+extern "C" int ursn_bn_backward_frozen(const float* dy, const float* y, const float* z, const float* mean, const float* rstd,
+                                       const float* beta, float* dz, float* dbeta, int64_t voxels, int32_t channels, int32_t relu,
+                                       void* scratch, size_t scratch_bytes, void* stream) {
+  URSN_REQUIRE(dy && rstd && dz && dbeta && scratch, "bn_backward_frozen: null argument");
+  URSN_REQUIRE(voxels >= 1 && channels >= 1, "bn_backward_frozen: voxels = %lld, channels = %d", (long long)voxels, (int)channels);
+  URSN_REQUIRE(!relu || y || (z && mean && beta), "bn_backward_frozen: the relu mask needs y, or z, mean and beta");
+  URSN_REQUIRE(scratch_bytes >= ursn_bn_scratch_bytes(voxels, channels), "bn_backward_frozen: scratch too small");
+  // the two-pass route reads z and mean for xhat, whose term the zero means cancel: it needs them readable
+  URSN_REQUIRE(ursn_bn_frozen_fused() || (z && mean), "bn_backward_frozen: URSN_BN_FROZEN_FUSED=0 needs z and mean");
+  BnBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.dy = dy; a.dycs = channels; a.y = relu ? y : nullptr; a.ycs = channels; a.z = z; a.zcs = channels;
+  a.mean = mean; a.rstd = rstd; a.dz = dz; a.dzcs = channels; a.dbeta = dbeta;
+  a.beta = beta;
+  a.V = voxels; a.C = channels; a.relu = relu; a.scratch = scratch; a.frozen = 1;
+  return launch_bn_bwd(a, (hipStream_t)stream);
+}
+
 // ---- bf16 BatchNorm passes at op level ------------------------------------------------------------------------------
 extern "C" size_t ursn_bn_bf16_scratch_bytes(int64_t voxels, int32_t channels) { return bbn_scratch_bytes(voxels, channels) + 256; }
 
@@ -763,8 +782,16 @@ extern "C" int ursn_bn_bf16_forward(const ursn_bn_bf16_desc* d, void* stream) {
   return launch_bbn_act(a, (hipStream_t)stream);
 }
 
+static int bn_bf16_backward(const ursn_bn_bf16_desc* d, void* scratch, size_t scratch_bytes, void* stream, int frozen);
 extern "C" int ursn_bn_bf16_backward(const ursn_bn_bf16_desc* d, void* scratch, size_t scratch_bytes, void* stream) {
   URSN_REQUIRE(d && d->dy && d->z && d->mean && d->rstd && d->dz && d->dbeta && scratch, "bn_bf16_backward: null argument");
+  return bn_bf16_backward(d, scratch, scratch_bytes, stream, 0);
+}
+extern "C" int ursn_bn_bf16_backward_frozen(const ursn_bn_bf16_desc* d, void* scratch, size_t scratch_bytes, void* stream) {
+  URSN_REQUIRE(d && d->dy && d->z && d->mean && d->rstd && d->dz && d->dbeta && scratch, "bn_bf16_backward_frozen: null argument");
+  return bn_bf16_backward(d, scratch, scratch_bytes, stream, 1);
+}
+static int bn_bf16_backward(const ursn_bn_bf16_desc* d, void* scratch, size_t scratch_bytes, void* stream, int frozen) {
   URSN_REQUIRE(scratch_bytes >= bbn_scratch_bytes(d->voxels, d->channels), "bn_bf16_backward: scratch too small");
   BBnBwdArgs a;
   memset(&a, 0, sizeof(a));
@@ -781,7 +808,7 @@ extern "C" int ursn_bn_bf16_backward(const ursn_bn_bf16_desc* d, void* scratch, 
     a.dz2 = (bf16_t*)d->dz2; a.dz2cs = d->dz2_cstride > 0 ? d->dz2_cstride : C; a.dbeta2 = d->dbeta2;
   }
   if (d->dres) { a.dres = (bf16_t*)d->dres; a.drescs = d->dres_cstride > 0 ? d->dres_cstride : C; a.dres_accumulate = d->dres_accumulate; }
-  a.V = d->voxels; a.C = C; a.Cw = C; a.relu = d->relu; a.scratch = scratch;
+  a.V = d->voxels; a.C = C; a.Cw = C; a.relu = d->relu; a.scratch = scratch; a.frozen = frozen;
   return launch_bbn_bwd(a, (hipStream_t)stream);
 }
 

@@ -138,7 +138,8 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
 }
 
 // One block per channel: 256 threads stride over the per-block partials, tree-reduce in LDS (double).
-template <int NS>
+// ROWS: rows per block of the partials (the first NS are summed; the others are not read)
+template <int NS, int ROWS = NS>
 __device__ inline void reduce_partials(const double* __restrict__ partial, int nblocks, int C, int c, double (&out)[NS]) {
   __shared__ double sm[NS][256];
   double acc[NS];
@@ -146,7 +147,7 @@ __device__ inline void reduce_partials(const double* __restrict__ partial, int n
   for (int k = 0; k < NS; ++k) acc[k] = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 256) {
 #pragma unroll
-    for (int k = 0; k < NS; ++k) acc[k] += partial[((size_t)b * NS + k) * C + c];  // C = channel stride of the partials
+    for (int k = 0; k < NS; ++k) acc[k] += partial[((size_t)b * ROWS + k) * C + c];  // C = channel stride of the partials
   }
 #pragma unroll
   for (int k = 0; k < NS; ++k) sm[k][threadIdx.x] = acc[k];
@@ -366,24 +367,36 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BnBwdArgs a, int shi
 }
 
 // finals: [3][C] doubles = mean(g), mean(g*xhat), mean(g*xhat2); dbeta(+2) += sum g
+// frozen (fixed statistics): the three means ARE zero -- written, not computed: rows 1 and 2 of the partials may be unwritten and
+// are not read; row 0 is summed in the order the batch form sums it, so dbeta has the same bits whoever wrote the partials
 __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restrict__ partial, int nblocks, int C,
                                                            int64_t V, double* __restrict__ finals,
                                                            float* __restrict__ dbeta, float* __restrict__ dbeta2, int Cw,
                                                            float* __restrict__ coef, const float* __restrict__ mean,
-                                                           const float* __restrict__ rstd, const float* __restrict__ beta) {
+                                                           const float* __restrict__ rstd, const float* __restrict__ beta,
+                                                           int frozen) {
   const int c = blockIdx.x;
   double s[3];
-  reduce_partials<3>(partial, nblocks, C, c, s);
+  if (frozen) {   // uniform over the grid
+    double s0[1];
+    reduce_partials<1, 3>(partial, nblocks, C, c, s0);
+    s[0] = s0[0];
+    s[1] = s[2] = 0.0;
+  } else {
+    reduce_partials<3>(partial, nblocks, C, c, s);
+  }
   if (threadIdx.x != 0) return;
-  finals[c] = s[0] / (double)V;
+  finals[c] = frozen ? 0.0 : s[0] / (double)V;
   finals[C + c] = s[1] / (double)V;
   finals[2 * C + c] = s[2] / (double)V;
   if (coef) {   // dz = A g' + B (z - mu) + C for the data-gradient kernel that applies this BatchNorm backward on load
+    // ONE block for both modes, the expressions as they always were: a separate frozen block made the compiler form T as
+    // multiply + subtract instead of the fma bn_act uses, which flipped relu-mask bits in batch mode
     const float r = rstd[c], mu = mean[c];
     const float mg = (float)finals[c], mgx = (float)finals[C + c];   // the apply kernel's fp32 constants
     coef[c] = r;
-    coef[C + c] = -(r * r) * mgx;
-    coef[2 * C + c] = -r * mg;
+    coef[C + c] = frozen ? 0.f : -(r * r) * mgx;   // frozen: dz = rstd g'
+    coef[2 * C + c] = frozen ? 0.f : -r * mg;
     coef[3 * C + c] = mu;
     coef[4 * C + c] = r;
     coef[5 * C + c] = beta ? beta[c] - mu * r : 0.f;   // bn_act's shift (same expression: the mask must be the forward's)
@@ -463,12 +476,88 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a, int shif
   }
 }
 
+// Frozen-BatchNorm backward in ONE pass: with fixed mean / rstd  dz = rstd * g,  dz2 = rstd2 * g,  dres (=|+=) g  need no reduction,
+// so the apply pass runs alone and sums g on the way.  Operands as bn_bwd_apply_kernel takes them, except that z is loaded only
+// for the bn(z) > 0 mask and z2 never.  Grid, thread-to-voxel mapping and summation order are bn_bwd_reduce_kernel's, and the sum
+// goes to row 0 of the same [block][3][C] partials: the unchanged finalise then adds the same dbeta bits as the two-pass form.
+template <int VEC>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(BnBwdArgs a, int shift, double* __restrict__ partial) {
+  const int CP = 1 << shift;
+  const int VPB = 256 >> shift;
+  const int c = (threadIdx.x & (CP - 1)) * VEC;
+  const int vr = threadIdx.x >> shift;
+  double acc[1][VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc[0][j] = 0.0;
+  if (c < a.C) {
+    float rs[VEC], rs2[VEC], be[VEC];
+    const bool bmask = VEC == 4 && a.relu && a.mask != nullptr;
+    const bool ymask = !bmask && a.relu && a.y != nullptr, zmask = !bmask && a.relu && a.y == nullptr;
+    const bool dacc = a.dres && a.dres_accumulate;
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      rs[j] = a.rstd[c + j];
+      rs2[j] = a.z2 ? a.rstd2[c + j] : 0.f;
+      be[j] = zmask ? a.beta[c + j] - a.mean[c + j] * rs[j] : 0.f;   // shift of the forward pass
+    }
+    constexpr int U = URSN_EW_U;
+    const int64_t stride = (int64_t)gridDim.x * VPB;
+    for (int64_t v0 = (int64_t)blockIdx.x * VPB + vr; v0 < a.V; v0 += stride * U) {
+      typename VT<VEC>::T gv[U], xv[U], yv[U], drv[U];
+      unsigned long long mw[U][VEC];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t v = v0 + u * stride;
+        if (v < a.V) {
+          gv[u] = ldv<VEC>(a.dy + v * a.dycs + c);
+          if (zmask) xv[u] = ldv<VEC>(a.z + v * a.zcs + c);
+          if (ymask) yv[u] = ldv<VEC>(a.y + v * a.ycs + c);
+          if (dacc) drv[u] = ldv<VEC>(a.dres + v * a.drescs + c);
+          if (bmask) {
+            const int64_t grp = ((v - (lane >> shift)) * a.C) >> 8;
+            const ulonglong2* mp = (const ulonglong2*)(a.mask + grp * 4);
+            const ulonglong2 m0 = mp[0], m1 = mp[1];
+            mw[u][0] = m0.x; mw[u][1] = m0.y; mw[u][VEC > 2 ? 2 : 0] = m1.x; mw[u][VEC > 3 ? 3 : 0] = m1.y;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t v = v0 + u * stride;
+        if (v >= a.V) continue;
+        typename VT<VEC>::T dz, dz2, dr = drv[u];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float gj = elem(gv[u], j);
+          if (ymask && !(elem(yv[u], j) > 0.f)) gj = 0.f;
+          if (zmask && !(fmaf(elem(xv[u], j), rs[j], be[j]) > 0.f)) gj = 0.f;   // same expression as bn_act
+          if (bmask && !((mw[u][j] >> lane) & 1ull)) gj = 0.f;
+          acc[0][j] += (double)gj;
+          setelem(dz, j, rs[j] * gj);
+          if (a.z2) setelem(dz2, j, rs2[j] * gj);
+          if (a.dres) setelem(dr, j, dacc ? elem(dr, j) + gj : gj);
+        }
+        stv<VEC>(a.dz + v * a.dzcs + c, dz);
+        if (a.z2) stv<VEC>(a.dz2 + v * a.dz2cs + c, dz2);
+        if (a.dres) stv<VEC>(a.dres + v * a.drescs + c, dr);
+      }
+    }
+  }
+  block_reduce_store<1, VEC>(acc, CP, a.C, partial + (size_t)blockIdx.x * 3 * a.C);
+}
+
 int launch_bn_bwd_final(const double* partial, int nblocks, int C, int64_t V, double* finals, float* dbeta, float* dbeta2,
-                        int Cw, hipStream_t s, float* coef_out, const float* mean, const float* rstd, const float* beta) {
+                        int Cw, hipStream_t s, float* coef_out, const float* mean, const float* rstd, const float* beta, int frozen) {
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(256), 0, s, partial, nblocks, C, V, finals, dbeta, dbeta2, Cw, coef_out, mean, rstd,
-                     beta);
+                     beta, frozen);
   URSN_HIP(hipGetLastError());
   return 0;
+}
+
+bool ursn_bn_frozen_fused() {
+  static const bool on = ursn_env_on("URSN_BN_FROZEN_FUSED");
+  return on;
 }
 
 int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
@@ -482,6 +571,16 @@ int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
   double* partial = (double*)a.scratch;
   double* finals = partial + (size_t)m.grid * 3 * a.C;
   int nblocks = m.grid;
+  const int frozen = a.frozen ? 1 : 0;
+  if (bn_bwd_single_pass(a)) {
+    if (v4) hipLaunchKernelGGL(bn_bwd_frozen_kernel<4>, dim3(m.grid), dim3(256), 0, s, a, m.shift, partial);
+    else hipLaunchKernelGGL(bn_bwd_frozen_kernel<1>, dim3(m.grid), dim3(256), 0, s, a, m.shift, partial);
+    URSN_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(a.C), dim3(256), 0, s, (const double*)partial, nblocks, a.C, a.V, finals,
+                       a.dbeta, a.z2 ? a.dbeta2 : nullptr, a.Cw > 0 ? a.Cw : a.C, (float*)nullptr, a.mean, a.rstd, (const float*)nullptr, 1);
+    URSN_HIP(hipGetLastError());
+    return 0;
+  }
   if (a.pre_partial) {   // sum g, sum g xhat(, sum g xhat2) came out of the epilogue of the kernel that produced dy
     partial = const_cast<double*>(a.pre_partial);
     nblocks = a.pre_nblocks;
@@ -492,7 +591,7 @@ int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
   }
   if (a.coef_out) URSN_REQUIRE(!a.z2 && !a.dres && !a.mask && !(a.relu && a.y), "bn_bwd: apply-on-load coefficients need a single BatchNorm, no residual share and the bn(z) > 0 mask");
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(a.C), dim3(256), 0, s, (const double*)partial, nblocks, a.C, a.V, finals,
-                     a.dbeta, a.z2 ? a.dbeta2 : nullptr, a.Cw > 0 ? a.Cw : a.C, a.coef_out, a.mean, a.rstd, a.relu ? a.beta : nullptr);
+                     a.dbeta, a.z2 ? a.dbeta2 : nullptr, a.Cw > 0 ? a.Cw : a.C, a.coef_out, a.mean, a.rstd, a.relu ? a.beta : nullptr, frozen);
   URSN_HIP(hipGetLastError());
   if (a.coef_out) return 0;   // dz is formed (and stored) by the layer's data-gradient kernel
   if (v4) hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(m.grid), dim3(256), 0, s, a, m.shift, (const double*)finals);

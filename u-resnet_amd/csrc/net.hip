@@ -803,6 +803,14 @@ int bn_back(ursn_net* n, int li, const float* dy, int dycs, const float* y, int 
     a.coef_out = L.coef;
     n->vdz_layer = li; n->vdz_relu = relu; n->vdz_g = dy; n->vdz_cs = dycs;
   }
+  a.frozen = n->bnm.frozen && n->bnm.frozen_train;   // fixed statistics: dz = rstd * g
+  if (bn_bwd_single_pass(a)) {   // one pass: g (+ y | z for the mask, + dres when it accumulates) in; dz (+ dz2, dres) out; mask bits 1/32
+    const double words = 1 + (relu && !mask) + (dres && dres_acc) + 1 + (li2 >= 0) + (dres != nullptr) + (relu && mask ? 1.0 / 32 : 0.0);
+    ProfScope ps(n, s, li, 5, 0.0, 4.0 * a.V * a.C * words);
+    URSN_TRY(launch_bn_bwd(a, s));
+    ps.done("bn_bwd_frozen");
+    return 0;
+  }
   ProfScope ps(n, s, li, 5, 0.0, 4.0 * a.V * a.C * (2.0 * (2 + (relu && !mask) + (li2 >= 0)) + 1 + (li2 >= 0) + (dres != nullptr)));
   URSN_TRY(launch_bn_bwd(a, s));
   ps.done("bn_bwd");
@@ -913,10 +921,11 @@ int read_metrics(ursn_net* n, float* out, int cnt, hipStream_t s) {
 
 BnmState& bnm_of(ursn_net* n) { return n->bf ? *bnet_bnm(n->bf) : n->bnm; }
 
-// training_entry: the name of a call that runs (or continues into) a backward pass; refused while frozen
+// training_entry: the name of a call that runs (or continues into) a backward pass; refused while frozen, unless the handle was
+// told to train through the fixed statistics (ursn_bn_frozen_train)
 int check_call(ursn_net* n, const float* data, int N, const char* training_entry = nullptr) {
   URSN_REQUIRE(n, "null handle");
-  URSN_REQUIRE(!(training_entry && bnm_of(n).frozen),
+  URSN_REQUIRE(!(training_entry && bnm_of(n).frozen && !bnm_of(n).frozen_train),
                "%s: refused while BatchNorm is frozen on its moving statistics (ursn_bn_set_frozen): frozen mode is forward-only",
                training_entry);
   if (n->pend_state == 1) n->pend_state = 3;   // every run call overwrites the activations a pending forward_logits stored
@@ -1093,7 +1102,8 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
   URSN_REQUIRE(!net->cfg.use_weight || weight, "Network configured to use loss pixel-weighting. Cannot run w/ input_weight=None");
   hipStream_t s = (hipStream_t)stream;
   net->last_n = n;
-  bnm_of(net).last_fwd = 1;   // never frozen; set here too: a hipGraph replay below does not pass through forward()
+  const bool frozen_step = bnm_of(net).frozen;   // accepted above: ursn_bn_frozen_train is on
+  bnm_of(net).last_fwd = frozen_step ? 2 : 1;   // set here too: a hipGraph replay below does not pass through forward()
   if (net->bf) {
     URSN_TRY(bnet_step(net->bf, data, label, weight, n, 0, nullptr, nullptr, s));
     if (out3) URSN_TRY(read_metrics(net, out3, 3, s));
@@ -1108,7 +1118,8 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
   // pool of branch streams and faults on the host.
   // URSN_GRAPH=1: when the batch holds <= 2^20 voxels, 2: always.  Never while profiling (events per launch).
   static const int gmode = ursn_env_int("URSN_GRAPH", 0);
-  bool geligible = gmode > 0 && !net->profile && !net->graph_broken && !ursn_roctx_on() &&
+  // a frozen step neither enters nor replays a graph: a captured graph holds the launches of the mode it was captured in
+  bool geligible = gmode > 0 && !frozen_step && !net->profile && !net->graph_broken && !ursn_roctx_on() &&
                    (gmode > 1 || (int64_t)n * net->lvox[0] <= ((int64_t)1 << 20));
   auto run_on = [&](hipStream_t rs) -> int {
     URSN_TRY(forward(net, data, n, rs));
@@ -1399,7 +1410,7 @@ extern "C" int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, 
   URSN_REQUIRE(((uintptr_t)logits_out & 3) == 0, "forward_logits: logits_out must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   net->last_n = n;
-  bnm_of(net).last_fwd = 1;   // never frozen
+  bnm_of(net).last_fwd = bnm_of(net).frozen ? 2 : 1;
   if (net->bf) {
     URSN_TRY(bnet_forward_logits(net->bf, data, n, logits_out, s));
   } else {
@@ -1423,17 +1434,18 @@ extern "C" int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, 
 extern "C" int ursn_backward_logits(ursn_net* net, const float* data, const float* dlogits, int32_t n, float* dinput_out,
                                     void* stream) {
   URSN_REQUIRE(net, "backward_logits: null handle");
-  URSN_REQUIRE(!bnm_of(net).frozen, "backward_logits: refused while BatchNorm is frozen on its moving statistics (ursn_bn_set_frozen): "
+  URSN_REQUIRE(!bnm_of(net).frozen || bnm_of(net).frozen_train, "backward_logits: refused while BatchNorm is frozen on its moving statistics (ursn_bn_set_frozen): "
                                     "frozen mode is forward-only");
   URSN_REQUIRE(net->cfg.trainable && net->grads, "backward_logits: net constructed with trainable=False");
   URSN_REQUIRE(data && dlogits, "backward_logits: null data / dlogits");
   URSN_REQUIRE((((uintptr_t)dlogits | (uintptr_t)dinput_out) & 3) == 0, "backward_logits: dlogits / dinput_out must be 4-byte aligned");
-  static const char* const why[5] = {
+  static const char* const why[6] = {
       "no ursn_forward_logits has run on this handle", "",
       "the pending ursn_forward_logits was already consumed by an ursn_backward_logits",
       "another run call (accum_step, eval, infer*, forward_logits) overwrote the activations of the pending ursn_forward_logits",
-      "ursn_apply_adam changed the parameters after the pending ursn_forward_logits"};
-  URSN_REQUIRE(net->pend_state == 1, "backward_logits: %s", why[net->pend_state >= 0 && net->pend_state < 5 ? net->pend_state : 0]);
+      "ursn_apply_adam changed the parameters after the pending ursn_forward_logits",
+      "ursn_bn_frozen_train changed the BatchNorm derivative after the pending ursn_forward_logits"};
+  URSN_REQUIRE(net->pend_state == 1, "backward_logits: %s", why[net->pend_state >= 0 && net->pend_state < 6 ? net->pend_state : 0]);
   URSN_REQUIRE(n == net->pend_n, "backward_logits: batch %d, but the pending ursn_forward_logits ran batch %d", (int)n, net->pend_n);
   URSN_REQUIRE(data == net->pend_data, "backward_logits: data is not the tensor the pending ursn_forward_logits read");
   hipStream_t s = (hipStream_t)stream;
@@ -1508,6 +1520,17 @@ extern "C" int ursn_bn_set_frozen(ursn_net* net, int32_t on) {
   BnmState& st = bnm_of(net);
   URSN_REQUIRE(!on || st.moving, "bn_set_frozen: no moving buffer is attached (ursn_bn_attach)");
   st.frozen = on != 0;
+  if (!st.frozen) st.frozen_train = false;
+  return 0;
+}
+
+extern "C" int ursn_bn_frozen_train(ursn_net* net, int32_t on) {
+  URSN_REQUIRE(net, "bn_frozen_train: null handle");
+  BnmState& st = bnm_of(net);
+  URSN_REQUIRE(!on || st.frozen, "bn_frozen_train: BatchNorm is not frozen on its moving statistics (ursn_bn_set_frozen)");
+  // a forward_logits that ran under the other derivative must not be continued under this one
+  if (st.frozen_train != (on != 0) && net->pend_state == 1) net->pend_state = 5;
+  st.frozen_train = on != 0;
   return 0;
 }
 

@@ -826,6 +826,13 @@ int bn_back(ursn_bnet* n, int li, const bf16_t* dy, int dycs, const bf16_t* y, i
   a.V = (int64_t)N * n->lvox[L.lout]; a.C = L.kout; a.Cw = L.cout; a.relu = relu; a.scratch = n->bn_scratch;
   if (n->bs_layer == li && a.C == 8) { a.pre_partial = n->bs_scratch; a.pre_nblocks = n->bs_blocks; }
   n->bs_layer = -1;
+  a.frozen = n->bnm.frozen && n->bnm.frozen_train;   // fixed statistics: dz = rstd * g
+  if (bbn_bwd_single_pass(a)) {   // one pass: dy (+ dy2, + y | z for the mask, + dres when it accumulates) in; dz (+ dz2, dres) out
+    const double pieces = 1 + (dy2 != nullptr) + (relu && !mask) + (dres && dres_acc) + 1 + (li2 >= 0) + (dres != nullptr) +
+                          (relu && mask ? 1.0 / 16 : 0.0);
+    BProf ps(n, s, li, 5, 0.0, 2.0 * a.V * a.C * pieces, "bbn_bwd_frozen");
+    return launch_bbn_bwd(a, s);
+  }
   // reduce: dy, z (+ y | z2); apply: the same again + dz (+ dz2 | dres); the mask bytes are 1/16 of a tensor
   BProf ps(n, s, li, 5, 0.0, 2.0 * a.V * a.C * (2.0 * (2 + (relu && y && !mask) + (li2 >= 0)) + 1 + (li2 >= 0) + (dres != nullptr)), "bbn_bwd");
   return launch_bbn_bwd(a, s);

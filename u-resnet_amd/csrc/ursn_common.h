@@ -300,8 +300,15 @@ struct BnBwdArgs {
   // {A, B, C, mu, S, T} with dz = A g' + B (z - mu) + C, g' = g (* (fma(z, S, T) > 0)), and the layer's data-gradient kernel
   // forms and stores dz while it stages its operand (ursn_conv_desc.vdz_*)
   float* coef_out;
+  // mean / rstd are FIXED statistics (frozen-BatchNorm training): dz = rstd * g, dz2 = rstd2 * g, both projection terms vanish.
+  // Without pre_partial / coef_out one pass forms dz and sums g (bn_bwd_frozen_kernel, URSN_BN_FROZEN_FUSED=0: off); otherwise
+  // the finalise writes zero means and every consumer of them produces rstd * g unchanged.
+  int frozen;
 };
 int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s);
+bool ursn_bn_frozen_fused();   // URSN_BN_FROZEN_FUSED=0: frozen BatchNorm backward as reduce + zero-mean finalise + apply (A/B)
+// does launch_bn_bwd run this call as the single frozen pass?  (the profiler names and sizes the launch by it)
+static inline bool bn_bwd_single_pass(const BnBwdArgs& a) { return a.frozen && !a.pre_partial && !a.coef_out && ursn_bn_frozen_fused(); }
 
 // Head: logits = bn(z) (mean/rstd/beta may be null => z are logits already).
 struct HeadArgs {
@@ -322,9 +329,10 @@ size_t head_scratch_bytes(int n, int64_t pix);
 int head_blocks(int n, int64_t pix);
 int launch_head_final(const double* partial, int nblocks, int n, int64_t pix, float* metrics, hipStream_t s);
 // finals [3][C] = mean(g), mean(g xhat), mean(g xhat2) from [nblocks][3][C] partials; dbeta(2)[c < Cw] += sum g
+// frozen: all three means (and coef rows B, C) are written as 0 and only row 0 of the partials is read
 int launch_bn_bwd_final(const double* partial, int nblocks, int C, int64_t V, double* finals, float* dbeta, float* dbeta2,
                         int Cw, hipStream_t s, float* coef_out = nullptr, const float* mean = nullptr, const float* rstd = nullptr,
-                        const float* beta = nullptr);
+                        const float* beta = nullptr, int frozen = 0);
 int launch_head(const HeadArgs& a, hipStream_t s);
 // Gather head (voxel_io.hip): ursn_scores_at_voxels with the list length when the host knows it (m_total < 0: unknown; rows at or
 // beyond m_total are never written, 0 launches nothing).  Validates like the C entry point.

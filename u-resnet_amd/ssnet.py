@@ -19,6 +19,11 @@ from . import _lib
 from .resnet_module import Graph, SymTensor
 
 
+class _NoMovingStatistics(RuntimeError, ValueError):
+    """``set_bn_mode('frozen')`` on a network without moving statistics: a missing buffer (the RuntimeError every other entry
+    raises for it) and a mode this network cannot take (the ValueError an unknown mode raises)."""
+
+
 class HipSession(object):
     """Stands in for ``tf.Session`` (lib/ssnet_trainval.py:112): names the device and stream the
     fetch-sets run on.  Every run method also accepts ``sess=None`` (current device/stream)."""
@@ -217,7 +222,8 @@ class ssnet_base(object):
         ``bn_moving`` (the half of slim.batch_norm the reference leaves dead): allocates the moving statistics of every
         BatchNorm layer (mean 0, variance 1) and attaches them to the handle; every ``accum_gradients*`` call then folds its
         forward's batch statistics in with momentum ``1 - bn_decay``, and ``set_bn_mode('moving')`` makes the forward-only
-        calls normalise with them.  False: nothing is allocated and every call does what it did without the keyword."""
+        calls normalise with them; ``set_bn_mode('frozen')`` also trains on them as constants (fine-tuning, no update of the buffer).
+        False: nothing is allocated and every call does what it did without the keyword."""
         if not 0.0 <= float(bn_decay) <= 1.0:
             raise ValueError('bn_decay = %r outside [0, 1]' % (bn_decay,))
         self._bn_tracking = bool(bn_moving)
@@ -414,7 +420,9 @@ class ssnet_base(object):
         _lib.check(lib.ursn_set_adam_step(self._handle, step))
         if getattr(self, '_bn_buf', None) is not None:   # caller-owned like the parameters: a new handle loses nothing
             _lib.check(lib.ursn_bn_attach(self._handle, p(self._bn_buf)))
-            _lib.check(lib.ursn_bn_set_frozen(self._handle, int(self._bn_mode == 'moving')))
+            _lib.check(lib.ursn_bn_set_frozen(self._handle, int(self._bn_mode in ('moving', 'frozen'))))
+            if self._bn_mode == 'frozen':
+                _lib.check(lib.ursn_bn_frozen_train(self._handle, 1))
         if getattr(self, '_opt_state', None) is not None:   # caller-owned as well; attaching rebuilds the tables for this handle
             _lib.check(lib.ursn_opt_attach(self._handle, p(self._opt_state), self._opt_state.numel()))
 
@@ -1542,10 +1550,12 @@ class ssnet_base(object):
 
     def allreduce_bn_moving(self):
         """Data parallelism: each rank folded its own minibatches' statistics in; the moving buffers are summed over ranks and
-        scaled by ``1 / world`` (one fp32 multiply), so that ranks stay identical like the weights do.  No-op without tracking
-        or with one rank."""
+        scaled by ``1 / world`` (one fp32 multiply), so that ranks stay identical like the weights do.  No-op without tracking,
+        with one rank, or in ``'frozen'`` mode (the buffer does not change there)."""
         import torch.distributed as dist
         if getattr(self, '_bn_buf', None) is None or not self._bn_tracking:
+            return
+        if self._bn_mode == 'frozen':   # constant, identical on every rank: summing and scaling it would only round it
             return
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.all_reduce(self._bn_buf, op=dist.ReduceOp.SUM)
@@ -1561,7 +1571,7 @@ class ssnet_base(object):
 
     def _bn_track(self, sess):
         """One ``assign_moving_average`` of every layer after a training forward (one per minibatch, as UPDATE_OPS would)."""
-        if getattr(self, '_bn_buf', None) is not None and self._bn_tracking:
+        if getattr(self, '_bn_buf', None) is not None and self._bn_tracking and self._bn_mode != 'frozen':
             _lib.check(_lib.load().ursn_bn_update(self._handle, 1.0 - self._bn_decay, self._stream(sess)))
 
     def reset_bn_moving(self):
@@ -1579,13 +1589,22 @@ class ssnet_base(object):
     def set_bn_mode(self, mode):
         """``'batch'`` (default): every forward normalises with the statistics of the batch it is given, as the reference does.
         ``'moving'``: the forward-only calls (``inference*``, ``run_test*``) normalise with the moving statistics, so an event's
-        result no longer depends on its batch; ``accum_gradients*``, ``forward_logits`` and ``backward_logits`` are refused."""
-        if mode not in ('batch', 'moving'):
-            raise ValueError("set_bn_mode: mode must be 'batch' or 'moving', got %r" % (mode,))
+        result no longer depends on its batch; ``accum_gradients*``, ``forward_logits`` and ``backward_logits`` are refused.
+        ``'frozen'``: as ``'moving'`` for the forward-only calls, and the training entries run too (``accum_gradients``,
+        ``accum_gradients_voxels``, ``accum_gradients_custom``, ``forward_logits`` / ``backward_logits``, ``UResNetFunction``):
+        fine-tuning on fixed statistics, with the derivative that treats mean / rstd as constants (``dz = rstd * g``).  The moving
+        buffer is neither updated per minibatch nor all-reduced in this mode; weights and beta train as usual."""
+        if mode not in ('batch', 'moving', 'frozen'):
+            raise ValueError("set_bn_mode: mode must be 'batch', 'moving' or 'frozen', got %r" % (mode,))
         if mode == 'moving':
             self._bn_require("set_bn_mode('moving')")
+        if mode == 'frozen' and getattr(self, '_bn_buf', None) is None:
+            raise _NoMovingStatistics("set_bn_mode('frozen'): no moving statistics (construct(bn_moving=True) allocates them)")
         if self._handle is not None and getattr(self, '_bn_buf', None) is not None:
-            _lib.check(_lib.load().ursn_bn_set_frozen(self._handle, int(mode == 'moving')))
+            lib = _lib.load()
+            _lib.check(lib.ursn_bn_set_frozen(self._handle, int(mode != 'batch')))   # off clears the training switch as well
+            if mode != 'batch':
+                _lib.check(lib.ursn_bn_frozen_train(self._handle, int(mode == 'frozen')))
         self._bn_mode = mode
 
     def bn_calibrate(self, sess, batches, reset=True):

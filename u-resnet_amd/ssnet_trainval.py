@@ -186,7 +186,8 @@ class ssnet_trainval(object):
         self._net = uresnet(dims=dims, num_class=cfg.NUM_CLASS, base_num_outputs=cfg.BASE_NUM_FILTERS, debug=cfg.DEBUG)
         extra = {'learning_rate': cfg.LEARNING_RATE} if cfg.TRAIN else {}
         ana_moving = not cfg.TRAIN and cfg.ANA_BN == 'moving'
-        if cfg.BN_MOVING or ana_moving:   # default off: construct is then called exactly as before
+        train_frozen = cfg.TRAIN and cfg.TRAIN_BN == 'frozen'
+        if cfg.BN_MOVING or ana_moving or train_frozen:   # default off: construct is then called exactly as before
             extra.update(bn_moving=True, bn_decay=cfg.BN_DECAY)
         self._net.construct(trainable=cfg.TRAIN, use_weight=cfg.USE_WEIGHTS, seed=cfg.TF_RANDOM_SEED,
                             precision=cfg.PRECISION, **extra)
@@ -217,6 +218,8 @@ class ssnet_trainval(object):
             self._restore(cfg.LOAD_FILE)
         if ana_moving:
             self._net.set_bn_mode('moving')
+        if train_frozen:
+            self._net.set_bn_mode('frozen')
         self._descr_metrics = None
 
     def _restore(self, load_file):
@@ -245,7 +248,10 @@ class ssnet_trainval(object):
                     print('\033[91mWarning\033[00m: no BatchNorm moving statistics loaded from %s: they keep their initial 0 / 1' % load_file
                           + (", and ANA_BN 'moving' normalises with those -- the output is meaningless until ssnet_base.bn_calibrate "
                              "(or a BN_MOVING training run) has given the network usable statistics" if self._cfg.ANA_BN == 'moving'
-                             and not self._cfg.TRAIN else ''))
+                             and not self._cfg.TRAIN else '')
+                          + (", and TRAIN_BN 'frozen' normalises with those -- the training is meaningless until ssnet_base.bn_calibrate "
+                             "(or a BN_MOVING training run) has given the network usable statistics" if self._cfg.TRAIN_BN == 'frozen'
+                             and self._cfg.TRAIN else ''))
         self._net.set_variables(values, strict=False)
         if moving:
             self._net.set_bn_moving(moving, strict=False)
