@@ -255,7 +255,10 @@ typedef struct ursn_conv_desc {
 /* y = conv(x, w).  w layout [k..,Cin,Cout] (transposed: [k..,Cout,Cin]). */
 int ursn_conv_forward(const ursn_conv_desc* d, const float* x, const float* w, float* y, void* stream);
 /* y = conv(x, w) plus the batch statistics BatchNorm needs: mean[cout], rstd[cout] = rsqrt(var+eps)
- * (slim.batch_norm as normalizer_fn, lib/uresnet.py:42).  scratch >= ursn_bn_scratch_bytes(out voxels, cout). */
+ * (slim.batch_norm as normalizer_fn, lib/uresnet.py:42).  scratch: 8-byte aligned device buffer of at least
+ * ursn_conv_stats_scratch_bytes(d) bytes (declared at the end of this header) -- the per-workgroup partial sums of the kernel
+ * family this descriptor dispatches to, NOT a function of the voxel count alone; a smaller buffer is refused before any launch
+ * ("scratch too small").  The scratch needs no initialisation. */
 int ursn_conv_forward_stats(const ursn_conv_desc* d, const float* x, const float* w, float* y, float* mean,
                             float* rstd, float eps, void* scratch, size_t scratch_bytes, void* stream);
 /* dx (=|+=) conv^T(dy, w); accumulate != 0 adds into dx. */
@@ -808,6 +811,15 @@ int ursn_bn_bf16_backward_frozen(const ursn_bn_bf16_desc* d, void* scratch, size
 
 /* MFMA lane-layout probe used by tests (writes 64*16 floats). */
 int ursn_mfma_probe(int32_t which, float* out, void* stream);
+
+/* ---- statistics scratch of ursn_conv_forward_stats (conv_api.hip) --------------------------------------------------------------
+ * Appended function only: URSN_ABI_VERSION stays 9.
+ * Exactly the number ursn_conv_forward_stats compares its scratch_bytes against for this descriptor: the partial-sum rows of the
+ * kernel family the descriptor dispatches to (same predicate chain as the call, dtype 1 included), or the separate reduction's
+ * buffer for the shapes no fused-statistics kernel takes.  A multiple of 8; 0 where the call refuses the descriptor for another
+ * reason (bf16 transposed convs, a fused form the shape has no kernel for, a forced algo that does not take the shape).  Host logic
+ * only: no device access. */
+size_t ursn_conv_stats_scratch_bytes(const ursn_conv_desc* d);
 
 #ifdef __cplusplus
 }

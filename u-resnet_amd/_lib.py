@@ -209,6 +209,7 @@ _SIGS = {
     "ursn_crop_scratch_bytes": (C.c_size_t, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
     "ursn_crop_write": (C.c_int, [C.POINTER(ursn_crop_desc), C.POINTER(ursn_crop_out), _P, C.c_size_t, _P]),
     "ursn_scores_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "ursn_conv_stats_scratch_bytes": (C.c_size_t, [C.POINTER(ursn_conv_desc)]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

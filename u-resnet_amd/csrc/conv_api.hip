@@ -533,6 +533,74 @@ extern "C" int ursn_conv_forward_stats(const ursn_conv_desc* d, const float* x, 
   return launch_bn_stats(y, ocs, V, d->cout, eps, mean, rstd, scratch, s);
 }
 
+// The number ursn_conv_forward_stats compares scratch_bytes against for this descriptor: the same predicate chain, one
+// return per URSN_REQUIRE("... scratch too small") above (bf16: in bf16_conv_op), 0 where the call refuses the descriptor
+// for another reason.  Host logic only.
+static size_t bf16_stats_scratch_need(const ursn_conv_desc& d0) {
+  ursn_conv_desc d = d0;
+  if (d.transposed) return 0;
+  const bool scalar_in = d.cin == 1;
+  if (scalar_in) {
+    if (d.k != 3 || d.stride != 1 || d.in_mean || d.in_split) return 0;
+    d.cin = 8; d.in_cstride = 8;
+  }
+  if (d.in_split || d.pw_dy) return 0;   // data-gradient forms
+  GatherGeom g[8];
+  const int n = build_geoms(d, PASS_FWD, g);
+  if (n < 1) return 0;
+  if (scalar_in || d.in_mean) {
+    if (n != 1 || !b3conv_ok(g[0])) return 0;
+    if (d.in_mean && !(d.in_rstd && d.in_beta && b3conv_aff_ok(g[0]))) return 0;
+    size_t need = bconv_stats_scratch_doubles(g[0]) * sizeof(double);
+    if (scalar_in) {
+      stored_weight_strides(g[0], 1, d.cout);
+      if (b0conv_ok(g[0])) {
+        const size_t b0 = (size_t)b0conv_grid_blocks(g[0]) * 32 * sizeof(double);
+        if (b0 > need) need = b0;
+      } else if (g[0].K != 8) {
+        return 0;
+      }
+    }
+    return need;
+  }
+  if (n == 1 && bs2k8_ok(g[0])) return (size_t)bs2k8_grid_blocks(g[0]) * 32 * sizeof(double);
+  if (bsconv_ok(g, n)) return bsconv_stats_scratch_doubles(g, n) * sizeof(double);
+  size_t need = 0;
+  for (int i = 0; i < n; ++i) {
+    if (g[i].ntaps == 0) continue;
+    if (!bconv_pack_elems(g[i])) return 0;
+    const size_t b = bconv_stats_scratch_doubles(g[i]) * sizeof(double) * n;
+    if (b > need) need = b;
+  }
+  return need;
+}
+
+extern "C" size_t ursn_conv_stats_scratch_bytes(const ursn_conv_desc* d) {
+  if (!d) return 0;
+  if (d->dtype == 1) return bf16_stats_scratch_need(*d);
+  GatherGeom g[8];
+  if (build_geoms(*d, PASS_FWD, g) < 1) return 0;
+  if (d->in_mean && !(d->in_rstd && d->in_beta && tiled_conv_supported(*d, PASS_FWD))) return 0;
+  if (d->in_split && !(pointwise_conv_supported(*d, PASS_FWD, 0) || tiled_conv_supported(*d, PASS_FWD))) return 0;
+  if ((d->algo == 0 || d->algo == 5 || d->in_split) && pointwise_conv_supported(*d, PASS_FWD, 0))
+    return pointwise_stats_scratch_doubles(*d) * sizeof(double);
+  if (d->algo == 0 && deep_conv_supported(*d, PASS_FWD)) return deep_conv_stats_scratch_doubles(*d) * sizeof(double);
+  if ((d->algo == 0 || d->algo == 4) && igemm_conv_supported(*d, PASS_FWD)) return igemm_stats_scratch_doubles(*d) * sizeof(double);
+  if ((d->algo == 0 || d->algo == 6) && stride2_conv_supported(*d, PASS_FWD)) return stride2_stats_scratch_doubles(*d) * sizeof(double);
+  if ((d->algo == 0 && prefer_lds_scatter(*d, PASS_FWD)) || (d->algo == 7 && lds_scatter_supported(*d, PASS_FWD)))
+    return lds_scatter_stats_scratch_doubles(*d) * sizeof(double);
+  if ((d->algo == 0 || d->algo == 3) && tiled_deconv_supported(*d, PASS_FWD)) return tiled_deconv_stats_scratch_doubles(*d) * sizeof(double);
+  if ((d->algo == 0 || d->algo == 3 || d->in_split || d->in_mean) && tiled_conv_supported(*d, PASS_FWD))
+    return tiled_conv_stats_scratch_doubles(*d) * sizeof(double);
+  // the separate reduction behind conv_dispatch: what conv_dispatch refuses for a forward pass is refused here
+  if (d->vdz_z || d->bs_partial || d->pw_dy || d->in_mean || d->in_split) return 0;
+  if (d->algo >= 3 && d->algo <= 7) return 0;   // a forced family that does not take the shape
+  int64_t V = (int64_t)d->n;
+  for (int j = 0; j < 3; ++j) V *= g[0].out_d[j];
+  if (d->transposed) { V = (int64_t)d->n; for (int j = 0; j < d->ndim; ++j) V *= 2 * d->in_sp[j]; }
+  return reduce_scratch_bytes(V, d->cout, 2);
+}
+
 extern "C" int ursn_conv_backward_data(const ursn_conv_desc* d, const float* dy, const float* w, float* dx,
                                        int32_t accumulate, void* stream) {
   URSN_REQUIRE(d && dy && w && dx, "conv_backward_data: null argument");
