@@ -821,6 +821,58 @@ int ursn_mfma_probe(int32_t which, float* out, void* stream);
  * only: no device access. */
 size_t ursn_conv_stats_scratch_bytes(const ursn_conv_desc* d);
 
+/* ---- device loss head (loss_head.hip) ---------------------------------------------------------------------------------------
+ * Appended functions and one struct only: URSN_ABI_VERSION stays 9.
+ * A second head beside the reference's weighted softmax cross-entropy: focal exponent, label smoothing and a batch soft-Dice term,
+ * computed from conv2's stored operands straight into the plan's d(logits) tensor; no dense logits tensor exists.  Per voxel p with
+ * logits z, q = softmax(z), C = ncls, l = (int)label[p] (truncated toward zero), w = weight[p] (1 without a weight), P = n * voxels:
+ *     t_k   = (1 - smoothing) [k == l] + smoothing / C            ce_p = -sum_k t_k log q_k          f_p = (1 - q_l)^gamma
+ *     L_ce  = (1/n) sum_p w_p f_p ce_p                            (sum over voxels, mean over events: the reference's reduction)
+ *     I_c = sum_p q_pc [l_p == c], S_c = sum_p q_pc, Y_c = sum_p [l_p == c]      (all P voxels of the batch, unweighted)
+ *     L_dice = 1 - (1/C) sum_c (2 I_c + dice_eps) / (S_c + Y_c + dice_eps)       L = L_ce + dice_weight * L_dice
+ * A voxel with l == ignore_label adds nothing to L_ce, the Dice sums or d L / d z (its stored gradient is zero) but still counts in
+ * the accuracies; any other label outside [0, C) makes the loss NaN, as in the head.
+ * Domain: gamma == 0 or gamma >= 1 (finite), 0 <= smoothing < 1, dice_weight >= 0 (finite), dice_eps > 0 (finite); ignore_label -1:
+ * none.  With gamma == 0, smoothing == 0, dice_weight == 0 and ignore_label == -1 the kernel takes the heads' own statements and its
+ * stored dlogits, metrics and BatchNorm-backward partials carry the bits of head_kernel (fp32 z: expf / logf) or bhead_kernel (bf16
+ * z: the fast __expf / __logf; every other spec uses expf / logf on either dtype). */
+typedef struct ursn_loss_desc {
+  double gamma, smoothing, dice_weight, dice_eps;
+  int32_t ignore_label;
+} ursn_loss_desc;
+
+/* d: n, voxels, ncls, z / z_cstride / dtype, mean / rstd / beta as in ursn_logits_dense, data [n, voxels] or NULL (acc_nonzero is
+ * NaN without it); offsets / index unused.  label [n, voxels] fp32, weight nullable.
+ * dlog_out (NULL: loss and metrics only), in the three layouts of ursn_dlogits_pack: out_dtype 0 with out_cstride 4, <= 4 classes and
+ * 16-byte alignment: one 16-byte store, pad lanes zero; any other fp32 stride >= ncls: the ncls values only; out_dtype 1: stride 8,
+ * 16-byte aligned, bf16 round-to-nearest-even, pad lanes zero.
+ * bs_partial_or_null: the logits layer's BatchNorm-backward partials from the STORED dlogits, [bs_blocks][3][C] doubles, third row
+ * zero, C = 4 (fp32: z and dlog_out both at stride 4, <= 4 classes, 16-byte aligned) or 8 (bf16 z and bf16 dlog_out); needs mean /
+ * rstd and bs_blocks == the head's block count for (n, voxels).
+ * out8 (device, 4-byte aligned) = {loss, acc_all, acc_nonzero, n_nonzero, ce_term, dice_term, 0, 0}.
+ * One thread per voxel, grid-stride over the heads' workgroups of 256; fp64 partials per block, a one-workgroup finalise with a
+ * fixed tree; no atomics; the scratch needs no initialisation; the same arguments give the same bits.  dice_weight == 0: two
+ * launches (main, finalise); otherwise four at most (sums, finalise, gradient).  scratch: 8-byte aligned, >=
+ * ursn_loss_head_scratch_bytes(n, voxels, ncls) (0 for n outside [1, 65535], voxels outside [1, 2^31) or ncls outside [1, 8]).
+ * Null, misaligned, out-of-domain and too-small arguments are refused before any launch.  Enqueues only. */
+size_t ursn_loss_head_scratch_bytes(int32_t n, int64_t voxels, int32_t ncls);
+int ursn_loss_head(const ursn_vscores_desc* d, const float* label, const float* weight, const ursn_loss_desc* spec, void* dlog_out,
+                   int32_t out_cstride, int32_t out_dtype, double* bs_partial_or_null, int32_t bs_blocks, float* out8, void* scratch,
+                   size_t scratch_bytes, void* stream);
+
+/* ursn_accum_step with the loss head in place of the plan's head: forward() exactly as a step calls it, ursn_loss_head on conv2's
+ * operands into the handle's d(logits) tensor (with the BatchNorm-backward partials under the conditions the plan's head carries
+ * them), the unchanged backward; gradients are ADDED to the flat buffer and the metrics land where ursn_read_metrics reads them.
+ * Both plans; a training entry (refused while frozen unless ursn_bn_frozen_train is on); ends a pending ursn_forward_logits like
+ * every run call; never enters or replays a URSN_GRAPH graph.  Recorded as pass 6 "losshead" / "losssums" / "lossfinal" when
+ * profiling.  Enqueues only.  ursn_eval_loss: the same without dlogits and backward (forward-only: legal while frozen). */
+int ursn_accum_step_loss(ursn_net* net, const float* data, const float* label, const float* weight, int32_t n,
+                         const ursn_loss_desc* spec, void* stream);
+int ursn_eval_loss(ursn_net* net, const float* data, const float* label, const float* weight, int32_t n, const ursn_loss_desc* spec,
+                   void* stream);
+/* out2 = {ce_term, dice_term} of the last ursn_accum_step_loss / ursn_eval_loss on this handle.  Synchronises the stream. */
+int ursn_read_loss_terms(ursn_net* net, float* out2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

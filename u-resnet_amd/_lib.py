@@ -107,6 +107,11 @@ class ursn_crop_out(C.Structure):
                 ("weight", C.c_void_p), ("bg_weight", C.c_void_p), ("src", C.c_void_p), ("owned", C.c_void_p), ("cap", C.c_int64)]
 
 
+class ursn_loss_desc(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
+                ("ignore_label", C.c_int32)]
+
+
 class ursn_prof_rec(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("layer", C.c_char * 96), ("pass_", C.c_int32), ("ms", C.c_float),
                 ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int32), ("reserved_", C.c_int32)]
@@ -210,6 +215,12 @@ _SIGS = {
     "ursn_crop_write": (C.c_int, [C.POINTER(ursn_crop_desc), C.POINTER(ursn_crop_out), _P, C.c_size_t, _P]),
     "ursn_scores_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "ursn_conv_stats_scratch_bytes": (C.c_size_t, [C.POINTER(ursn_conv_desc)]),
+    "ursn_loss_head_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
+    "ursn_loss_head": (C.c_int, [C.POINTER(ursn_vscores_desc), _P, _P, C.POINTER(ursn_loss_desc), _P, C.c_int32, C.c_int32, _P,
+                                 C.c_int32, _P, _P, C.c_size_t, _P]),
+    "ursn_accum_step_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(ursn_loss_desc), _P]),
+    "ursn_eval_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(ursn_loss_desc), _P]),
+    "ursn_read_loss_terms": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -130,6 +130,17 @@ class ssnet_config(object):
     ANA_TILE_BATCH = 4
     TRAIN_CROP = []
     CROP_SEED = 0
+    # not in the reference, whose one objective is the weighted softmax cross-entropy of lib/ssnet.py:57-71.  All off by default: the
+    # steps then run the plan's head exactly as before.  Any key set = the train and test steps run the device loss head
+    # (losses.py holds the definition): LOSS_FOCAL_GAMMA 0 or >= 1 = the focal exponent on (1 - p_label); LOSS_LABEL_SMOOTHING in
+    # [0, 1) = the share of the target spread evenly over the classes; LOSS_DICE_WEIGHT >= 0 = the weight of the batch soft-Dice
+    # term (its sums run over the minibatch of ONE rank) with LOSS_DICE_EPS > 0 in numerator and denominator; LOSS_IGNORE_LABEL = a
+    # label whose voxels take no part in the loss (-1: none).  Report lines and scalars.jsonl then carry ce= and dice=
+    LOSS_FOCAL_GAMMA = 0.
+    LOSS_LABEL_SMOOTHING = 0.
+    LOSS_DICE_WEIGHT = 0.
+    LOSS_DICE_EPS = 1.
+    LOSS_IGNORE_LABEL = -1
 
     def __init__(self):
         pass
@@ -214,7 +225,26 @@ class ssnet_config(object):
             if key == 'ANA_TILE_BATCH' and value < 1:
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
+            if key == 'LOSS_FOCAL_GAMMA' and not (value == 0.0 or 1.0 <= value < float('inf')):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'LOSS_LABEL_SMOOTHING' and not 0.0 <= value < 1.0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'LOSS_DICE_WEIGHT' and not 0.0 <= value < float('inf'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'LOSS_DICE_EPS' and not 0.0 < value < float('inf'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
             setattr(self, key, value)
+
+    def loss_spec(self):
+        """The losses.LossSpec of the LOSS_* keys, or None while they all hold their defaults (the plan's head runs)."""
+        from .losses import LossSpec
+        spec = LossSpec(self.LOSS_FOCAL_GAMMA, self.LOSS_LABEL_SMOOTHING, self.LOSS_DICE_WEIGHT, self.LOSS_DICE_EPS,
+                        self.LOSS_IGNORE_LABEL)
+        return None if spec.neutral else spec
 
     def dump(self):
         """lib/config.py:68-76."""

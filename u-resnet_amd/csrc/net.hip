@@ -13,6 +13,7 @@
 #include "ursn_common.h"
 #include "net_bf16.h"
 #include "ext_loss.h"
+#include "loss_head.h"
 #include "bn_moving.h"
 
 int conv_dispatch(const ursn_conv_desc& d, ConvPass pass, const float* in, const float* w, float* out, int accumulate,
@@ -75,6 +76,8 @@ struct ursn_net {
   void* head_scratch = nullptr;
   void* cs_scratch = nullptr;   // ursn_infer_stats: per-span partials of the class statistics (ana_stats.hip)
   size_t cs_scratch_bytes = 0;
+  void* loss_scratch = nullptr;   // ursn_accum_step_loss / ursn_eval_loss: block partials and Dice coefficients (loss_head.hip)
+  size_t loss_scratch_bytes = 0;
   void* wg_scratch = nullptr;
   size_t wg_scratch_bytes = 0;
   float* dc_scratch = nullptr;   // packed weights (+ split-K slabs) of the deep-level kernel (conv_deep.hip), main stream only
@@ -388,6 +391,8 @@ int plan(ursn_net* n, Arena& A) {
   n->bnm.host.clear();
   for (const Layer& L : n->layers) n->bnm.host.push_back(BnmEntry{L.mean, L.rstd, L.cout, L.zcs, 0});
   bnm_plan(n->bnm, A);
+  n->loss_scratch_bytes = loss_head_scratch_bytes(c.max_batch, n->lvox[0]);   // after everything else: no earlier piece moves
+  n->loss_scratch = A.take(n->loss_scratch_bytes);
 
   n->sizes.n_params = poff;
   n->sizes.n_layers = (int64_t)n->layers.size();
@@ -633,6 +638,40 @@ int head(ursn_net* n, const float* data, const float* label, const float* weight
   ProfScope ps(n, s, n->conv2, 6, 0.0, 4.0 * N * n->lvox[0] * (2.0 * a.ncls + 3));
   URSN_TRY(launch_head(a, s));
   ps.done("head");
+  return 0;
+}
+
+// The loss head (loss_head.hip) in the place of head(): conv2's stored operands in, n->dlog and the metrics out, and the handle
+// state head() leaves behind (bs_layer / bs_blocks / bs_C) set under head()'s conditions.  Every launch is recorded on its own.
+// Two halves: the call is built and validated before the forward's launches, and run after them.
+int loss_head_net_prepare(ursn_net* n, const float* data, const float* label, const float* weight, int N, const ursn_loss_desc* spec,
+                          bool want_grad, LossHeadCall& c) {
+  Layer& L = n->layers[n->conv2];
+  memset(&c.d, 0, sizeof(c.d));
+  c.d.n = N; c.d.voxels = n->lvox[0]; c.d.ncls = n->cfg.num_class;
+  c.d.z = L.z; c.d.z_cstride = L.zcs; c.d.dtype = 0;
+  c.d.mean = L.mean; c.d.rstd = L.rstd; c.d.beta = n->params + L.b_off;
+  c.d.data = (n->cfg.cin == 1) ? data : nullptr;   // acc_nonzero needs one input channel, as in head()
+  c.label = label; c.weight = weight; c.spec = *spec;
+  c.out = want_grad ? n->dlog : nullptr; c.ocs = L.zcs; c.odt = 0;
+  c.out8 = n->metrics; c.scratch = n->loss_scratch; c.nstages = 0;
+  c.bs = nullptr; c.bs_blocks = 0;
+  static const bool fuse = ursn_env_on("URSN_HEAD_BN_BWD");
+  const bool carry = want_grad && fuse && n->bs_scratch && L.zcs == 4 && c.d.ncls <= 4 && head_blocks(N, n->lvox[0]) <= 16384;
+  if (carry) { c.bs = n->bs_scratch; c.bs_blocks = head_blocks(N, n->lvox[0]); }
+  return loss_head_prepare(c, n->loss_scratch_bytes);
+}
+int loss_head_net_run(ursn_net* n, const LossHeadCall& c, hipStream_t s) {
+  n->bs_layer = -1;
+  if (c.bs) { n->bs_layer = n->conv2; n->bs_blocks = c.bs_blocks; n->bs_C = 4; }
+  for (int i = 0; i < c.nstages; ++i) {
+    ProfScope ps(n, s, n->conv2, 6, 0.0, 0.0);
+    const char* name = "";
+    double bytes = 0.0;
+    URSN_TRY(loss_head_stage(c, i, s, &name, &bytes));
+    if (ps.idx >= 0) n->prof[ps.idx].bytes = bytes;
+    ps.done(name);
+  }
   return 0;
 }
 
@@ -1474,6 +1513,64 @@ extern "C" int ursn_backward_logits(ursn_net* net, const float* data, const floa
                                      dinput_out, s));
     ps.done("dinput");
   }
+  return 0;
+}
+
+// ---- device loss head (loss_head.hip) ------------------------------------------------------------------------------------------
+// ursn_accum_step with loss_head_net in the place of head(); never a URSN_GRAPH graph (a captured graph holds the plan's head).
+extern "C" int ursn_accum_step_loss(ursn_net* net, const float* data, const float* label, const float* weight, int32_t n,
+                                    const ursn_loss_desc* spec, void* stream) {
+  URSN_TRY(check_call(net, data, n, "accum_step_loss"));
+  URSN_REQUIRE(net->cfg.trainable && net->grads, "accum_step_loss: net constructed with trainable=False");
+  URSN_REQUIRE(label, "accum_step_loss: input_label is null");
+  URSN_REQUIRE(!net->cfg.use_weight || weight, "Network configured to use loss pixel-weighting. Cannot run w/ input_weight=None");
+  URSN_TRY(loss_spec_check(spec));
+  hipStream_t s = (hipStream_t)stream;
+  const float* w = net->cfg.use_weight ? weight : nullptr;
+  // last_n / last_fwd describe a forward that RAN: they are set once nothing can refuse the call any more
+  if (net->bf) {
+    bool ran = false;
+    const int rc = bnet_step_loss(net->bf, data, label, w, n, spec, 0, s, &ran);
+    if (ran) { net->last_n = n; bnm_of(net).last_fwd = bnm_of(net).frozen ? 2 : 1; }
+    return rc;
+  }
+  LossHeadCall c;
+  URSN_TRY(loss_head_net_prepare(net, data, label, w, n, spec, true, c));
+  net->last_n = n;
+  bnm_of(net).last_fwd = bnm_of(net).frozen ? 2 : 1;
+  URSN_TRY(forward(net, data, n, s));
+  URSN_TRY(loss_head_net_run(net, c, s));
+  return backward(net, data, n, s);
+}
+
+extern "C" int ursn_eval_loss(ursn_net* net, const float* data, const float* label, const float* weight, int32_t n,
+                              const ursn_loss_desc* spec, void* stream) {
+  URSN_TRY(check_call(net, data, n));
+  URSN_REQUIRE(label, "eval_loss: input_label is null");
+  URSN_REQUIRE(!net->cfg.use_weight || weight, "Network configured to use loss pixel-weighting. Cannot run w/ input_weight=None");
+  URSN_TRY(loss_spec_check(spec));
+  hipStream_t s = (hipStream_t)stream;
+  const float* w = net->cfg.use_weight ? weight : nullptr;
+  if (net->bf) {
+    bool ran = false;
+    const int rc = bnet_step_loss(net->bf, data, label, w, n, spec, 1, s, &ran);
+    if (ran) net->last_n = n;
+    return rc;
+  }
+  LossHeadCall c;
+  URSN_TRY(loss_head_net_prepare(net, data, label, w, n, spec, false, c));
+  net->last_n = n;
+  URSN_TRY(forward(net, data, n, s));
+  return loss_head_net_run(net, c, s);
+}
+
+extern "C" int ursn_read_loss_terms(ursn_net* net, float* out2, void* stream) {
+  URSN_REQUIRE(net && out2, "read_loss_terms: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  float h[2];
+  URSN_HIP(hipMemcpyAsync(h, net->metrics + 4, sizeof(h), hipMemcpyDeviceToHost, s));
+  URSN_HIP(hipStreamSynchronize(s));
+  out2[0] = h[0]; out2[1] = h[1];
   return 0;
 }
 

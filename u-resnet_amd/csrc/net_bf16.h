@@ -26,6 +26,10 @@ int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N,
 // external loss boundary (ext_loss.hip): forward + logits_dense without the head; dlogits_pack + backward (+ conv0_input_grad)
 int bnet_forward_logits(ursn_bnet* n, const float* data, int N, float* logits_out, hipStream_t s);
 int bnet_backward_logits(ursn_bnet* n, const float* data, const float* dlogits, int N, float* dinput_out, hipStream_t s);
+// ursn_accum_step_loss (mode 0) / ursn_eval_loss (mode 1): bnet_step with the loss head (loss_head.hip) in the place of the head
+// *ran_forward: set once the call's arguments were accepted and the forward's launches begin
+int bnet_step_loss(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, const ursn_loss_desc* spec,
+                   int mode, hipStream_t s, bool* ran_forward);
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride);
 // per-launch HIP-event records (as ursn_profile_enable / ursn_profile_read of the fp32 plan) and the weight-gradient stream switch
 int bnet_profile_enable(ursn_bnet* n, int on);

@@ -21,6 +21,7 @@
 #include "bf16_pack.h"
 #include "net_bf16.h"
 #include "ext_loss.h"
+#include "loss_head.h"
 #include "bn_moving.h"
 
 namespace {
@@ -99,6 +100,8 @@ struct ursn_bnet {
   double* stats = nullptr; size_t stats_doubles = 0;
   void* bn_scratch = nullptr;
   void* head_scratch = nullptr;
+  void* loss_scratch = nullptr;   // ursn_accum_step_loss / ursn_eval_loss: block partials and Dice coefficients (loss_head.hip)
+  size_t loss_scratch_bytes = 0;
   void* cs_scratch = nullptr;   // ursn_infer_stats: per-span partials of the class statistics (ana_stats.hip)
   size_t cs_scratch_bytes = 0;
   void* wg_scratch = nullptr; size_t wg_bytes = 0;
@@ -394,6 +397,8 @@ int plan(ursn_bnet* n, Arena& A) {
   n->bnm.host.clear();
   for (const BLayer& L : n->layers) n->bnm.host.push_back(BnmEntry{L.mean, L.rstd, L.cout, L.kout, 0});
   bnm_plan(n->bnm, A);
+  n->loss_scratch_bytes = loss_head_scratch_bytes(c.max_batch, n->lvox[0]);   // after everything else: no earlier piece moves
+  n->loss_scratch = A.take(n->loss_scratch_bytes);
 
   n->sizes.n_params = poff;
   n->sizes.n_layers = (int64_t)n->layers.size();
@@ -1078,6 +1083,42 @@ int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* 
   }
   if (mode == 1) return head(n, data, label, w, N, nullptr, false, s);
   return head(n, data, label, nullptr, N, softmax_out, false, s, labels_out);
+}
+
+// bnet_step with the loss head in the place of head(): the handle state head() leaves behind set under head()'s conditions, every
+// launch recorded on its own
+int bnet_step_loss(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, const ursn_loss_desc* spec,
+                   int mode, hipStream_t s, bool* ran_forward) {
+  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  BLayer& L = n->layers[n->conv2];
+  const bool want_grad = mode == 0;
+  LossHeadCall c;
+  memset(&c.d, 0, sizeof(c.d));
+  c.d.n = N; c.d.voxels = n->lvox[0]; c.d.ncls = n->cfg.num_class;
+  c.d.z = L.z; c.d.z_cstride = L.kout; c.d.dtype = 1;
+  c.d.mean = L.mean; c.d.rstd = L.rstd; c.d.beta = n->beta_pad; c.d.data = data;
+  c.label = label; c.weight = weight; c.spec = *spec;
+  c.out = want_grad ? n->dlog : nullptr; c.ocs = 8; c.odt = 1;
+  c.out8 = n->metrics; c.scratch = n->loss_scratch; c.nstages = 0;
+  c.bs = nullptr; c.bs_blocks = 0;
+  static const bool fuse = ursn_env_on("URSN_BF16_HEAD_BN_BWD");
+  const bool carry = want_grad && fuse && n->bs_scratch && L.kout == 8 && bhead_blocks(N, n->lvox[0]) <= 16384;
+  if (carry) { c.bs = n->bs_scratch; c.bs_blocks = bhead_blocks(N, n->lvox[0]); }
+  URSN_TRY(loss_head_prepare(c, n->loss_scratch_bytes));   // refusals come before the forward's launches
+  if (ran_forward) *ran_forward = true;
+  URSN_TRY(forward(n, data, N, s));
+  n->bs_layer = -1;
+  if (carry) { n->bs_layer = n->conv2; n->bs_blocks = c.bs_blocks; }
+  for (int i = 0; i < c.nstages; ++i) {
+    const char* name = "";
+    double bytes = 0.0;
+    BProf ps(n, s, n->conv2, 6, 0.0, 0.0, "losshead");
+    URSN_TRY(loss_head_stage(c, i, s, &name, &bytes));
+    ps.fixed = name;
+    if (ps.idx >= 0) n->prof[ps.idx].bytes = bytes;
+  }
+  if (want_grad) return backward(n, N, s);
+  return 0;
 }
 
 // bnet_step's inference mode that stops before the dense head's softmax: forward, the dense head only for the accuracies

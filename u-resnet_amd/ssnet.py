@@ -894,7 +894,8 @@ class ssnet_base(object):
                                                             self._stream(None)))
         return fd
 
-    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None, make_weight=None, crop=None):
+    def accum_gradients_voxels(self, sess, voxels, fetch=True, normalize_weight=False, symmetry=None, make_weight=None, crop=None,
+                               loss=None):
         """``accum_gradients`` fed a VoxelBatch: same fetch-set, same return structure.  ``normalize_weight``: the expanded dense
         weight tensor is normalised per event on the device (``_normalize_fed_weight``), the same definition of the sum as the
         dense feed's; ``voxels.weight`` / ``bg_weight`` are not written and ``VoxelBatch.normalize_weights`` is not needed.
@@ -904,7 +905,8 @@ class ssnet_base(object):
         "tiling" below): ``(big_batch, boxes)`` with ``big_batch`` from ``upload_voxels`` and ``boxes`` a ``tiling.Boxes`` of the
         network's own size (``tiling.random_boxes``); ``voxels`` must then be None, the minibatch is one event per box, cut out of
         the resident large batch by ``ursn_crop_write`` and fed through the same expansion, so ``symmetry``, ``make_weight`` and
-        ``normalize_weight`` compose as they do for a fed batch.  None: the call is made exactly as without the keyword."""
+        ``normalize_weight`` compose as they do for a fed batch.  None: the call is made exactly as without the keyword.
+        ``loss``: as in ``accum_gradients``; it comes last, on the tensors the other keywords left."""
         if not self._trainable:
             raise RuntimeError('accum_gradients_voxels: constructed with trainable=False')
         if crop is not None:
@@ -924,8 +926,7 @@ class ssnet_base(object):
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
         w = fd.get('input_weight') if self._use_weight else None
-        _lib.check(_lib.load().ursn_accum_step(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
-                                               self._ptr(w), n, out if fetch else None, self._stream(sess)))
+        self._step_call(fd, w, n, out if fetch else None, sess, loss)
         self._bn_track(sess)
         self._last_feed = fd
         self._mark_consumed(fd)
@@ -934,7 +935,7 @@ class ssnet_base(object):
             return None, doc
         return [None, float(out[0]), float(out[1]), float(out[2])], doc
 
-    def run_test_voxels(self, sess, voxels, normalize_weight=False, make_weight=None, crop=None):
+    def run_test_voxels(self, sess, voxels, normalize_weight=False, make_weight=None, crop=None, loss=None):
         """``run_test`` fed a VoxelBatch (``normalize_weight`` / ``make_weight`` / ``crop`` as in ``accum_gradients_voxels``)."""
         if crop is not None:
             voxels = self._crop_source(voxels, crop, 'run_test_voxels')
@@ -953,8 +954,7 @@ class ssnet_base(object):
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
         w = fd.get('input_weight') if self._use_weight else None
-        _lib.check(_lib.load().ursn_eval(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
-                                         self._ptr(w), n, out, self._stream(sess)))
+        self._eval_call(fd, w, n, out, sess, loss)
         self._mark_consumed(fd)
         return [float(out[0]), float(out[1]), float(out[2])], ['loss', 'acc. all', 'acc. nonzero']
 
@@ -1326,7 +1326,7 @@ class ssnet_base(object):
         return [None]
 
     def accum_gradients(self, sess, input_data, input_label, input_weight=None, fetch=True, normalize_weight=False,
-                        symmetry=None, make_weight=None):
+                        symmetry=None, make_weight=None, loss=None):
         """``normalize_weight`` (not in the reference, whose driver normalises on the host, lib/ssnet_trainval.py:173): the fed
         weights are divided by their per-event sums on the device before the step (``_normalize_fed_weight``); ``input_weight``
         itself, host array or device tensor, is left as it is.  ``symmetry`` (not in the reference, whose users flip and
@@ -1335,7 +1335,11 @@ class ssnet_base(object):
         the call is made exactly as without the keyword.  ``make_weight`` (a weights.WeightSpec; not in the reference, which reads
         the weights as a stored product): ``input_weight`` must be None and no weight crosses PCIe; after the feed and the symmetry
         (over data and label only) ``ursn_make_weights`` makes the weights on the device from the label the step will see, before
-        the optional normalisation.  None: the call is made exactly as without the keyword."""
+        the optional normalisation.  None: the call is made exactly as without the keyword.  ``loss`` (a losses.LossSpec; not in the
+        reference, whose one objective is the weighted cross-entropy): the step runs the device loss head (``ursn_accum_step_loss``:
+        focal exponent, label smoothing, soft-Dice term) in the place of the plan's head, on the tensors every other keyword left;
+        same fetch-set, and ``last_loss_terms()`` then gives the two terms.  None: the call is made exactly as without the
+        keyword."""
         if not self._trainable:
             raise RuntimeError('accum_gradients: constructed with trainable=False')
         if make_weight is not None:
@@ -1353,8 +1357,7 @@ class ssnet_base(object):
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
         w = fd.get('input_weight') if self._use_weight else None
-        _lib.check(_lib.load().ursn_accum_step(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
-                                               self._ptr(w), n, out if fetch else None, self._stream(sess)))
+        self._step_call(fd, w, n, out if fetch else None, sess, loss)
         self._bn_track(sess)
         self._last_feed = fd  # keep device inputs alive until the stream has consumed them
         self._mark_consumed(fd)
@@ -1424,6 +1427,49 @@ class ssnet_base(object):
         if not fetch:
             return None, doc
         return [None, float(loss.detach().item())], doc
+
+    # ------------------------------------------------------------------------------------------
+    # device loss head (losses.py, loss_head.hip): the ``loss=`` keyword of the step and evaluation calls
+    # ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _loss_desc(loss):
+        from .losses import LossSpec
+        if not isinstance(loss, LossSpec):
+            raise TypeError('loss= takes a losses.LossSpec, got %r' % type(loss).__name__)
+        return _lib.ursn_loss_desc(loss.gamma, loss.smoothing, loss.dice_weight, loss.dice_eps, loss.ignore_label)
+
+    def _step_call(self, fd, w, n, out, sess, loss):
+        """The step of accum_gradients / accum_gradients_voxels: ``ursn_accum_step`` (loss None: today's call, argument for
+        argument) or ``ursn_accum_step_loss`` followed by the metrics read the plain call does itself."""
+        lib = _lib.load()
+        if loss is None:
+            _lib.check(lib.ursn_accum_step(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']), self._ptr(w), n, out,
+                                           self._stream(sess)))
+            return
+        d = self._loss_desc(loss)
+        _lib.check(lib.ursn_accum_step_loss(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']), self._ptr(w), n,
+                                            ctypes.byref(d), self._stream(sess)))
+        if out is not None:
+            _lib.check(lib.ursn_read_metrics(self._handle, out, self._stream(sess)))
+
+    def _eval_call(self, fd, w, n, out, sess, loss):
+        lib = _lib.load()
+        if loss is None:
+            _lib.check(lib.ursn_eval(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']), self._ptr(w), n, out,
+                                     self._stream(sess)))
+            return
+        d = self._loss_desc(loss)
+        _lib.check(lib.ursn_eval_loss(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']), self._ptr(w), n,
+                                      ctypes.byref(d), self._stream(sess)))
+        _lib.check(lib.ursn_read_metrics(self._handle, out, self._stream(sess)))
+
+    def last_loss_terms(self, sess=None):
+        """``(ce_term, dice_term)`` of the last step or evaluation that ran with ``loss=``: loss = ce_term + dice_weight * dice_term."""
+        if self._handle is None:
+            raise RuntimeError('last_loss_terms: no step has run')
+        out = (ctypes.c_float * 2)()
+        _lib.check(_lib.load().ursn_read_loss_terms(self._handle, out, self._stream(sess)))
+        return float(out[0]), float(out[1])
 
     def last_feed(self):
         """Device-resident tensors of the most recent accum_gradients / inference_labels call (valid until two more
@@ -1680,7 +1726,7 @@ class ssnet_base(object):
             host[at:at + v.size] = v
         self._bn_buf.copy_(torch.from_numpy(host))
 
-    def run_test(self, sess, input_data, input_label, input_weight=None, normalize_weight=False, make_weight=None):
+    def run_test(self, sess, input_data, input_label, input_weight=None, normalize_weight=False, make_weight=None, loss=None):
         if make_weight is not None:
             self._check_make_weight(make_weight, input_weight, 'run_test')
             fd = self._feed_for_made_weight(input_data, input_label)
@@ -1693,8 +1739,7 @@ class ssnet_base(object):
         self._ensure_handle(n)
         out = (ctypes.c_float * 3)()
         w = fd.get('input_weight') if self._use_weight else None
-        _lib.check(_lib.load().ursn_eval(self._handle, self._ptr(fd['input_data']), self._ptr(fd['input_label']),
-                                         self._ptr(w), n, out, self._stream(sess)))
+        self._eval_call(fd, w, n, out, sess, loss)
         return [float(out[0]), float(out[1]), float(out[2])], ['loss', 'acc. all', 'acc. nonzero']
 
     def inference(self, sess, input_data, input_label=None, as_numpy=True):

@@ -88,6 +88,7 @@ class ssnet_trainval(object):
         self._net = None
         self._writer_train = self._writer_test = None
         self._weight_spec = None
+        self._loss_terms = None
 
     def __del__(self):
         try:
@@ -311,6 +312,12 @@ class ssnet_trainval(object):
         codes = symmetry.group(c.AUGMENT, [int(x) for x in self._net._dims[:-1]])
         return {'symmetry': symmetry.draw(c.AUGMENT_SEED, self._iteration, minibatch, d.get_rank() if d is not None else 0, n, codes)}
 
+    def _loss_kw(self):
+        """Keyword of the accumulate and test calls.  Empty while the LOSS_* keys hold their defaults: those calls are then made
+        exactly as before.  Else the device loss head's spec (losses.LossSpec)."""
+        spec = self._cfg.loss_spec()
+        return {} if spec is None else {'loss': spec}
+
     def _crop_args(self, vb, minibatch):
         """The ``voxels`` argument and the extra keyword of the ``*_voxels`` calls.  With the default TRAIN_CROP [] the batch
         itself and nothing: those calls are then made exactly as before.  Else the large batch goes up once
@@ -327,7 +334,7 @@ class ssnet_trainval(object):
 
     def _run_test_voxels(self, test):
         voxels, crop = self._crop_args(test, -1)
-        return self._net.run_test_voxels(self._sess, voxels, **self._norm_kw(), **crop)
+        return self._net.run_test_voxels(self._sess, voxels, **self._norm_kw(), **crop, **self._loss_kw())
 
     def _step_lr(self):
         """The learning rate of the current iteration's optimiser step: what the step is given, the report line prints and the
@@ -344,6 +351,8 @@ class ssnet_trainval(object):
         c, net = self._cfg, self._net
         rows = []
         norm = self._norm_kw()
+        norm.update(self._loss_kw())   # the loss comes last in the calls: it sees the tensors every other keyword left
+        terms = []
         net.zero_gradients(self._sess)
         for minibatch in range(c.NUM_MINIBATCHES):
             if c.SPARSE_IO:
@@ -359,8 +368,11 @@ class ssnet_trainval(object):
             self._descr_metrics = doc[1:]
             if want_metrics:
                 rows.append(res[1:])
+                if 'loss' in norm:
+                    terms.append(net.last_loss_terms(self._sess))
             self._advance_main()
         self._last_minibatch = net.last_feed()
+        self._loss_terms = np.asarray(terms, np.float64).mean(axis=0) if terms else None   # (ce, dice), mean over the minibatches
         if optim.schedule_on(c):
             net.apply_gradients(self._sess, lr=self._step_lr())
         else:
@@ -404,6 +416,7 @@ class ssnet_trainval(object):
             tested = None
             if test is not None:
                 norm = self._norm_kw()
+                norm.update(self._loss_kw())
                 tested = (self._run_test_voxels(test) if self._cfg.SPARSE_IO
                           else self._net.run_test(self._sess, *test, **norm))
             if _is_rank0():
@@ -412,6 +425,8 @@ class ssnet_trainval(object):
                     plan.iteration, self._step_lr(), self.report_memory(), stamp))
                 sys.stdout.write('Train set: ')
                 self._report(train_mean, self._descr_metrics)
+                if self._loss_terms is not None:
+                    sys.stdout.write('Loss terms: ce=%.6g   dice=%.6g\n' % (self._loss_terms[0], self._loss_terms[1]))
                 if gstats is not None:
                     sys.stdout.write('Optimiser: gnorm=%.6g   nonfinite=%d   skipped=%d\n'
                                      % (gstats['global']['grad_norm'], gstats['global']['nonfinite'],
@@ -422,6 +437,11 @@ class ssnet_trainval(object):
         if plan.summary:
             last = self._last_minibatch   # already normalised, on the host or on the device: never again here
             summ = self._net.make_summary(self._sess, last['input_data'], last['input_label'], last.get('input_weight'))
+            lterms = self._loss_terms
+            if lterms is None and self._loss_kw():   # a summary without a report: the last minibatch's terms, still on the device
+                lterms = self._net.last_loss_terms(self._sess)
+            if lterms is not None:
+                summ['ce'], summ['dice'] = float(lterms[0]), float(lterms[1])
             if gstats is not None:
                 summ['gnorm'] = gstats['global']['grad_norm']
                 summ['lr'] = float(self._step_lr())
