@@ -873,6 +873,27 @@ int ursn_eval_loss(ursn_net* net, const float* data, const float* label, const f
 /* out2 = {ce_term, dice_term} of the last ursn_accum_step_loss / ursn_eval_loss on this handle.  Synchronises the stream. */
 int ursn_read_loss_terms(ursn_net* net, float* out2, void* stream);
 
+/* ---- work partition of an op-level conv call (conv_api.hip) ----------------------------------------------------------------------
+ * Appended function only: URSN_ABI_VERSION stays 9.
+ * The work split the family ursn_conv_plan names would take for this descriptor / pass (0 forward, 1 data gradient, 2 weight
+ * gradient), read from the plan function the family's launcher itself calls, under the environment switches of this process.
+ * Host logic only: no device access.  out = {workgroups of the main launch, sequential steps per workgroup along the marched or
+ * looped axis, partial results reduced afterwards (0: none), a family-specific word}:
+ *   dconv    {boxes * tiles * gsplit * cout blocks, chunk rounds per workgroup, split-K slabs (0: gsplit 1), SLAB flag}; SLAB 0: the
+ *            forward's statistics partials are workgroups * 128 doubles, written by the conv kernel itself
+ *   pconv    {workgroups (capped), 256-voxel steps of the first workgroup, rows of statistics partials (forward), voxels of the last step}
+ *   b3conv   {workgroups, planes per z segment, rows of statistics partials, z segments}
+ *   bcbconv  {workgroups, planes per z segment, rows of statistics partials per cout block, z segments}
+ *   bdconv   {workgroups, chunk rounds per workgroup, split-K slabs (0: gsplit 1), box voxels}
+ *   bconv    {workgroups, boxes a workgroup walks, rows of statistics partials per cout block, box voxels * 10 + stage buffers (1 or
+ *            2)} -- of the first non-empty parity class where a stride-2 pass runs one launch per class
+ *   bsconv   {workgroups, 32-channel chunks a workgroup contracts, rows of statistics partials per cout block, coarse box voxels}
+ *   b3wgrad  {workgroups = slabs written, planes per column, slabs the reduce kernel walks (after the fold), fold group (0: no fold)}
+ *   bdwgrad  {workgroups, boxes a workgroup walks, slabs per channel block, boxes}: the last slice is short when boxes % steps != 0
+ *   bwgrad   {workgroups, boxes a workgroup walks, slabs per channel block, box voxels}
+ * Every other family (their splits have no plan struct, or no switch moves them): returns non-zero, "not reported". */
+int ursn_conv_partition(const ursn_conv_desc* d, int32_t pass, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,10 @@ SWITCHES = [
     ("fp32", {"URSN_DISABLE_TILED": "1", "URSN_WGRAD_STREAM": "0"}),
     ("fp32", {"URSN_S2CONV_V2": "2", "URSN_HEAD_BN_BWD": "0"}),   # stride-2 gather kernel with 16-byte operand reads on every layer it can take; logits-layer BatchNorm-backward sums as a separate pass
     ("fp32", {"URSN_NORM_ON_LOAD": "2"}),   # normalise-on-load on the 16-channel layers too
+    # the production partitions of tests/_partitions.py that are legal together, through the plans' own scratch carving
+    ("bf16", {"URSN_B3_NZSEG": "1", "URSN_B3W_MINWG": "1", "URSN_SLAB_FOLD": "3", "URSN_BDWGRAD_WGS": "5", "URSN_BCONV_MINWG": "1",
+              "URSN_BWGRAD_MINWG": "1", "URSN_BCB_MINWG": "1", "URSN_BDCONV_MINWG": "1"}),   # whole-Z segments and columns, a short last fold group (16 slabs in threes), several boxes per bdwgrad workgroup, the larger boxes
+    ("fp32", {"URSN_DCONV_MINWG": "1", "URSN_PCONV_GRID": "2"}),   # dconv at gsplit 1 with its own statistics partials (levels 3-4), pconv on two workgroups
 ]
 
 

@@ -46,6 +46,7 @@ ROWS = [Row(*r) for r in [
     ("pconv2d", F, 2, 2, (16, 40), 32, 16, 1, 1, 0, 0, {}, ("pconv", "pconv", "pwgrad")),
     ("pconv2d_split", F, 2, 2, (12, 40), 16, 8, 1, 1, 0, 0, {"split": 8}, ("pconv", "pconv", "pwgrad")),
     ("pconv3d_s2", F, 3, 1, (8, 8, 12), 16, 32, 1, 2, 0, 5, {"acc": (1,)}, ("pconv", "pconv", "pwgrad")),
+    ("pconv3d_grid", F, 3, 2, (7, 9, 27), 16, 8, 1, 1, 0, 0, {}, ("pconv", "pconv", "pwgrad")),      # four workgroups by default (tests/_partitions.py caps them)
     ("dconv3d_odd", F, 3, 1, (5, 7, 9), 128, 64, 3, 1, 0, 0, {}, ("dconv", None, "dwgrad")),
     ("dconv3d_rag", F, 3, 1, (4, 6, 10), 192, 80, 3, 1, 0, 0, {}, ("dconv", None, "dwgrad")),
     ("dconv3d_n2", F, 3, 2, (6, 6, 6), 128, 256, 3, 1, 0, 0, {}, ("dconv", "dconv", "dwgrad")),
@@ -130,6 +131,7 @@ ROWS = [Row(*r) for r in [
     ("b3conv_16_16_zseg", B, 3, 1, (36, 9, 40), 16, 16, 3, 1, 0, 0, {}, ("b3conv", "b3conv", "b3wgrad")),
     ("b3conv_norm_odd", B, 3, 2, (9, 21, 37), 8, 8, 3, 1, 0, 0, {"norm": 1}, ("b3conv", None, "b3wgrad")),
     ("b3conv_norm_relu_odd", B, 3, 2, (11, 19, 35), 16, 16, 3, 1, 0, 0, {"norm": 1, "in_relu": 1}, ("b3conv", None, "b3wgrad")),
+    ("b3conv_norm_zseg", B, 3, 1, (37, 9, 33), 8, 8, 3, 1, 0, 0, {"norm": 1, "in_relu": 1}, ("b3conv", None, "b3wgrad")),      # Z >= 36: more than one z segment
     ("b3conv_pw_odd", B, 3, 2, (9, 21, 37), 16, 8, 3, 1, 0, 0, {"pw": 1}, (None, "b3conv", None)),
     ("b3conv_pw_split_zseg", B, 3, 1, (40, 10, 34), 16, 8, 3, 1, 0, 0, {"pw": 1, "split": 8, "acc": (0,)}, (None, "b3conv", None)),
     ("bcbconv_odd_cb", B, 3, 2, (9, 21, 37), 32, 32, 3, 1, 0, 0, {}, ("bcbconv", "bcbconv", "bwgrad")),
@@ -547,11 +549,13 @@ def test_a_store_behind_the_payload_is_reported(tag):
 
 # ---- the other op-level entry points --------------------------------------------------------------------------------------------
 V_BN = 4 * 6 * 10 * 3
+V_BN_BLOCKS = 5 * 7 * 9 * 11      # odd, and 4 (8 channels) to 28 (64 channels) blocks of the reduce kernels where V_BN gives 1 to 6
+BN_CASES = [(3, 0, False), (8, 1, False), (12, 1, False), (64, 0, True)]
 
 
-@pytest.mark.parametrize("C,relu,res", [(3, 0, False), (8, 1, False), (12, 1, False), (64, 0, True)])
-def test_bn_forward_backward_and_frozen_backward(C, relu, res):
-    lib, V = _lib.load(), V_BN
+@pytest.mark.parametrize("C,relu,res", BN_CASES)
+def test_bn_forward_backward_and_frozen_backward(C, relu, res, V=V_BN):
+    lib = _lib.load()
     rng = np.random.default_rng(C)
     z = _f32(rng.standard_normal((V, C)) * 2.0 + 0.5)
     beta = _f32(rng.standard_normal(C) * 0.3)
@@ -601,6 +605,11 @@ def test_bn_forward_backward_and_frozen_backward(C, relu, res):
     assert rel_err(bwd[0][0], dz) < 2e-5 and rel_err(bwd[0][1], dbeta) < 2e-5
     rstd = fwd[0][1][C:].astype(np.float64)
     assert rel_err(frz[0][0], rstd * g) < 2e-5 and rel_err(frz[0][1], g.sum(0)) < 2e-5
+
+
+@pytest.mark.parametrize("C,relu,res", BN_CASES)
+def test_bn_forward_backward_and_frozen_backward_on_several_blocks(C, relu, res):
+    test_bn_forward_backward_and_frozen_backward(C, relu, res, V=V_BN_BLOCKS)
 
 
 def _mask_bytes(y):
@@ -694,11 +703,15 @@ def _head_scratch_bytes(lib, n, pix, ncls):
     return int(msg.rsplit("<", 1)[1].strip(" )"))
 
 
-@pytest.mark.parametrize("ncls,use_w", [(3, True), (5, False)])
-def test_softmax_ce_head_outputs_guarded(ncls, use_w):
+HEAD_CASES = [(3, True), (5, False)]
+PIX_HEAD_BLOCKS = 1777      # 3 x 1777 voxels: six blocks of 1024, the last ragged (500: two)
+
+
+@pytest.mark.parametrize("ncls,use_w", HEAD_CASES)
+def test_softmax_ce_head_outputs_guarded(ncls, use_w, pix=500):
     lib = _lib.load()
     rng = np.random.default_rng(ncls)
-    n, pix = 3, 500
+    n = 3
     logits = _f32(rng.standard_normal((n, pix, ncls)) * 3)
     logits[0, :7] = 1.25
     data = _f32(rng.uniform(0, 1, (n, pix)) * (rng.uniform(0, 1, (n, pix)) > 0.6))
@@ -725,6 +738,11 @@ def test_softmax_ce_head_outputs_guarded(ncls, use_w):
     sm, dl, o3 = runs[0]
     assert abs(o3[0] - m["loss"]) / abs(m["loss"]) < 1e-5 and abs(o3[1] - m["acc_all"]) < 1e-6 and abs(o3[2] - m["acc_nonzero"]) < 1e-6
     assert rel_err(sm, m["softmax"]) < 1e-5 and rel_err(dl, m["dlogits"]) < 1e-5
+
+
+@pytest.mark.parametrize("ncls,use_w", HEAD_CASES)
+def test_softmax_ce_head_outputs_guarded_on_several_blocks(ncls, use_w):
+    test_softmax_ce_head_outputs_guarded(ncls, use_w, pix=PIX_HEAD_BLOCKS)
 
 
 def test_adam_buffers_guarded():

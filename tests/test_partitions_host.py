@@ -1,0 +1,122 @@
+"""Host half of the production-partition sets (tests/_partitions.py): on a CPU, in a child process per set (the
+switches are read once per process), every (row, pass) of the set still reaches the family tests/test_op_guards_gpu.ROWS names,
+ursn_conv_partition reports the required change against the default environment, and the scratch-size queries stay consistent.
+ursn_conv_partition reads the plan function the family's launcher calls (b3_plan, w3_plan, dc_plan, dw_plan, the box pickers)."""
+import functools
+import os
+import re
+
+import pytest
+
+import _partitions as P
+import test_op_guards_gpu as G
+
+
+@functools.lru_cache(maxsize=None)
+def default_report():
+    return P.host_report(None, {})
+
+
+@pytest.mark.parametrize("name", [s.name for s in P.SETS])
+def test_the_set_moves_its_rows_onto_the_production_branch(name):
+    s = P.BY_NAME[name]
+    dflt, got = default_report(), P.host_report(name, s.env)
+    moved = P.check_rows(s, dflt, got)
+    for tag, ps, _ in s.rows:
+        if (name, tag, ps) in P.AT_DEFAULT:
+            assert (tag, ps) not in moved, (name, tag, ps, "no longer at the default: drop it from AT_DEFAULT")
+        else:
+            assert (tag, ps) in moved, (name, tag, ps, "the set leaves the row on its default partition")
+    for ps in {ps for _, ps, _ in s.rows}:
+        assert any(p == ps for _, p in moved), (name, ps, "no row of this pass moves")
+    if s.extras:
+        P.check_caps(dflt, got)
+    print(name, "moved", moved)
+
+
+def test_the_default_environment_reports_the_small_shape_partitions():
+    """The premise: at the default thresholds the rows sit on the other side -- split-K slabs, one box per workgroup, short z
+    segments, no fold stage -- and the elementwise scratch grows with the voxel count."""
+    d = default_report()
+    assert d["dconv3d_n2/0"]["part"][3] == 1 and d["dconv3d_n2/0"]["part"][2] > 1
+    assert d["bdconv_rag_dp/2"]["part"][1] == 1
+    assert d["b3conv_16_16_zseg/0"]["part"][1] <= 16 and d["b3conv_16_16_zseg/0"]["part"][3] > 1
+    assert d["b3conv_odd/2"]["part"][3] == 0
+    assert d["pconv3d_grid/0"]["part"][0] == 4
+    for fam in ("bn", "bn_bf16"):
+        for C, (small, big) in d[fam].items():
+            assert 0 < small < big, (fam, C)
+
+
+def test_every_row_of_every_set_is_a_guarded_row_and_each_family_has_a_named_case():
+    need = {"dconv_gsplit1", "bdwgrad_one_slice", "bdwgrad_walk", "bdwgrad_walk_ragged", "b3_whole_z", "b3w_one_column", "fold_ragged",
+            "larger_box", "bcb_whole_z", "bd_box256", "pconv_capped"}
+    have = set()
+    for s in P.SETS:
+        assert s.rows and s.bench
+        for tag, ps, req in s.rows:
+            assert tag in G.BY_TAG and G.BY_TAG[tag].fams[ps] is not None and req in P.REQUIRE, (s.name, tag, ps, req)
+            have.add(req)
+    assert need <= have, need - have
+    # b3conv's whole-Z segment: every fused form the family has at op level (normalise-on-load, fused shortcut term, split, accumulate)
+    ex = [G.BY_TAG[t].ex for t, ps, _ in P.BY_NAME["b3_whole_z"].rows]
+    assert any(e.get("norm") for e in ex) and any(e.get("pw") and e.get("split") for e in ex) and any(1 in e.get("acc", (0, 1)) for e in ex)
+
+
+def test_every_numeric_switch_is_driven_or_listed_with_a_reason():
+    """Every number-valued or structured switch of DESIGN.md's A/B table is either in a set's environment or in NOT_DRIVEN with the
+    reason (extends tests/test_host.py::test_switch_table_matches_sources, which holds the table to the sources)."""
+    with open(os.path.join(P.ROOT, "DESIGN.md")) as f:
+        design = f.read()
+    section = design.split("### A/B switches", 1)[1].split("\n## ", 1)[0]
+    rows = "\n".join(l for l in section.splitlines() if l.startswith("|"))
+    numeric = set(re.findall(r'(URSN_[A-Z0-9_]+)=(?:n\b|p\b|"|\d+\|)', rows))
+    assert {"URSN_DCONV_MINWG", "URSN_BDWGRAD_WGS", "URSN_B3_NZSEG", "URSN_SLAB_FOLD", "URSN_EW_GRID", "URSN_BDCONV_FORM",
+            "URSN_BSCONV_NT", "URSN_PCONV_GRID"} <= numeric, sorted(numeric)
+    numeric |= {"URSN_BCONV_NBUF", "URSN_B3WGRAD_PAIR"}      # on / off in the table, partition-like in effect
+    drv = P.driven()
+    missing = sorted(n for n in numeric if n not in drv and n not in P.NOT_DRIVEN)
+    assert not missing, "neither in a set nor in NOT_DRIVEN: %s" % missing
+    stale = sorted(n for n in P.NOT_DRIVEN if n not in numeric)
+    assert not stale, "in NOT_DRIVEN but no numeric switch of the table: %s" % stale
+    both = sorted(n for n in P.NOT_DRIVEN if n in drv and n != "URSN_BCONV_MINWG")
+    assert not both, both
+    for n, why in P.NOT_DRIVEN.items():
+        assert len(why) > 10, n
+
+
+def test_families_without_a_plan_struct_are_not_reported():
+    import ctypes
+    from uresnet_amd import _lib
+    lib = _lib.load()
+    out = (ctypes.c_int64 * 4)()
+    for tag, ps in (("tconv3d_n2", 0), ("igemm3d_odd", 0), ("b0conv_odd", 0), ("bpw_odd", 0), ("bs2k8_n2", 0), ("tconv3d_n2", 2)):
+        d = G.build_desc(G.BY_TAG[tag], ps)
+        assert lib.ursn_conv_partition(ctypes.byref(d), ps, out) != 0 and b"not reported" in lib.ursn_last_error(), tag
+    assert lib.ursn_conv_partition(None, 0, out) != 0
+
+
+@pytest.mark.parametrize("src,query,launcher,plan", [
+    ("conv_deep.hip", "deep_conv_partition", "launch_deep_conv", "dc_plan("),
+    ("bf16_wgraddeep.hip", "bdwgrad_partition", "launch_bdwgrad", "dw_plan("),
+    ("bf16_conv3.hip", "b3conv_partition", "launch_b3conv", "b3_plan("),
+    ("bf16_wgrad3.hip", "b3wgrad_partition", "launch_b3wgrad", "w3_plan("),
+    ("bf16_wgrad3.hip", "b3wgrad_partition", "slab_fold", "slab_fold_group("),
+    ("bf16_convcb.hip", "bcbconv_partition", "launch_bcbconv", "cb_plan("),
+    ("bf16_convdeep.hip", "bdconv_partition", "launch_bdconv", "bd_plan("),
+    ("bf16_conv.hip", "bconv_partition", "launch_bconv", "bconv_plan("),
+    ("bf16_conv.hip", "bwgrad_partition", "launch_bwgrad", "bwgrad_plan("),
+    ("bf16_scatter.hip", "bsconv_partition", "launch_bsconv", "bs_plan("),
+    ("conv_pointwise.hip", "pointwise_conv_partition", "launch_pointwise_conv", "pconv_grid("),
+])
+def test_the_query_and_the_launcher_call_the_same_plan_function(src, query, launcher, plan):
+    """Source text only: the body of the family's partition query and the body of its launcher both call the one plan function."""
+    with open(os.path.join(P.ROOT, "u-resnet_amd", "csrc", src)) as f:
+        text = f.read()
+
+    def body(name):
+        m = re.search(r"^(?:static )?(?:int|bool) %s\([^;{]*\{" % re.escape(name), text, re.M)
+        assert m, (src, name)
+        return text[m.end():text.index("\n}\n", m.end())]
+
+    assert plan in body(query) and plan in body(launcher), (src, query, launcher, plan)

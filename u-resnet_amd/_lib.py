@@ -221,6 +221,7 @@ _SIGS = {
     "ursn_accum_step_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(ursn_loss_desc), _P]),
     "ursn_eval_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(ursn_loss_desc), _P]),
     "ursn_read_loss_terms": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
+    "ursn_conv_partition": (C.c_int, [C.POINTER(ursn_conv_desc), C.c_int32, C.POINTER(C.c_int64)]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -439,6 +439,15 @@ size_t bconv_stats_scratch_doubles(const GatherGeom& g) {
   return (size_t)p.ncob * p.gridx * 2 * 16 * p.cot;
 }
 
+// ursn_conv_partition, generic box kernel: {workgroups, boxes a workgroup walks, rows of statistics partials per cout block,
+// box voxels * 10 + stage buffers (1 | 2)}
+bool bconv_partition(const GatherGeom& g, int64_t out[4]) {
+  BPlan p;
+  if (!bconv_plan(g, p)) return false;
+  out[0] = (int64_t)p.gridx * p.ncob; out[1] = p.per; out[2] = p.gridx; out[3] = (int64_t)p.bq[0] * p.bq[1] * p.bq[2] * 10 + p.nbuf;
+  return true;
+}
+
 template <int VT, int COT>
 static int bconv_launch(const BPlan& p, const BConvArgs& a, hipStream_t s) {
   auto kern = bconv_kernel<VT, COT>;
@@ -839,6 +848,14 @@ size_t bwgrad_scratch_bytes(const GatherGeom& g) {   // 256 bytes (the zero piec
   BWPlan p;
   if (!bwgrad_plan(g, p)) return 0;
   return (size_t)p.nchunks * p.ncob * p.gridx * p.U * 16 * 16 * p.cot * sizeof(float) + 512;
+}
+
+// ursn_conv_partition, generic weight gradient: {workgroups, boxes a workgroup walks, slabs per channel block summed afterwards, box voxels}
+bool bwgrad_partition(const GatherGeom& g, int64_t out[4]) {
+  BWPlan p;
+  if (!bwgrad_plan(g, p)) return false;
+  out[0] = (int64_t)p.gridx * p.nchunks * p.ncob; out[1] = p.per; out[2] = p.gridx; out[3] = (int64_t)p.bq[0] * p.bq[1] * p.bq[2];
+  return true;
 }
 
 template <int MTW, int COT>

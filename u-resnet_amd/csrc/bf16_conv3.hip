@@ -569,6 +569,13 @@ bool b3conv_pw_ok(const GatherGeom& g) {
 }
 size_t b3conv_pack_elems() { return (size_t)B3<16, 16>::WPACK + 8; }
 int b3conv_grid_blocks(const GatherGeom& g) { return b3_plan(g).grid; }
+// ursn_conv_partition: {workgroups, planes per z segment, rows of statistics partials (one per workgroup), z segments}
+bool b3conv_partition(const GatherGeom& g, int64_t out[4]) {
+  if (!b3conv_ok(g)) return false;
+  const B3Plan p = b3_plan(g);
+  out[0] = p.grid; out[1] = p.zseg; out[2] = p.grid; out[3] = p.nzseg;
+  return true;
+}
 
 // Off unless URSN_BF16_FUSE_BN_BWD_REDUCE=1: measured at cfg5 (256^3 x 4) the five fused launches cost more than the five
 // bbn_bwd_reduce passes they replace -- 65.1 vs 67.0 img/s with the z / y loads inside the epilogue, 75.9 vs 80.0 with the

@@ -396,6 +396,13 @@ bool bcbconv_ok(const GatherGeom& g) {
 size_t bcbconv_pack_elems(const GatherGeom& g) { return (size_t)((g.Nn + 31) / 32) * 28 * (g.K / 16) * 512 + 8; }   // incl. a fused shortcut's fragments
 int bcbconv_grid_blocks(const GatherGeom& g) { return cb_plan(g).grid; }   // rows of the statistics partials PER cout block
 size_t bcbconv_stats_scratch_doubles(const GatherGeom& g) { const CBPlan p = cb_plan(g); return (size_t)p.grid * p.ncob * 64; }
+// ursn_conv_partition: {workgroups, planes per z segment, rows of statistics partials per cout block, z segments}
+bool bcbconv_partition(const GatherGeom& g, int64_t out[4]) {
+  if (!bcbconv_ok(g)) return false;
+  const CBPlan p = cb_plan(g);
+  out[0] = (int64_t)p.grid * p.ncob; out[1] = p.zseg; out[2] = p.grid; out[3] = p.nzseg;
+  return true;
+}
 
 template <int CI, bool STATS, bool PW>
 static int cb_launch(const CBPlan& p, const CBArgs& a, hipStream_t s) {

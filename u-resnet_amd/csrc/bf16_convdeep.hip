@@ -490,6 +490,15 @@ size_t bdconv_stats_scratch_doubles(const GatherGeom& g) {
   return p.gsplit > 1 ? (size_t)p.red_blocks * 2 * g.Nn : (size_t)p.tiles * p.ncob * 128;
 }
 
+// ursn_conv_partition: {workgroups, chunk rounds per workgroup, split-K slabs summed afterwards (0: none), box voxels (form 0: 256)}
+bool bdconv_partition(const GatherGeom& g, int64_t out[4]) {
+  BDPlan p;
+  if (!bdconv_ok(g) || !bd_plan(g, p)) return false;
+  out[0] = (int64_t)p.tiles * p.gsplit * p.ncob; out[1] = p.rounds; out[2] = p.gsplit > 1 ? p.gsplit : 0;
+  out[3] = (int64_t)p.bq[0] * p.bq[1] * p.bq[2];
+  return true;
+}
+
 template <int WK, int NT, bool STATS, bool SLAB>
 static int bd_launch(const BDPlan& p, const BDArgs& a, hipStream_t s) {
   auto kern = bdconv_kernel<WK, NT, STATS, SLAB>;

@@ -372,6 +372,13 @@ int bs_launch(const BSPlan& p, const BSArgs& a, hipStream_t s) {
 
 bool bsconv_ok(const GatherGeom* g, int cnt) { BSPlan p; return bs_plan(g, cnt, p); }
 int bsconv_grid_blocks(const GatherGeom* g, int cnt) { BSPlan p; return bs_plan(g, cnt, p) ? p.tiles : 0; }
+// ursn_conv_partition: {workgroups, 32-channel chunks a workgroup contracts, rows of statistics partials per cout block, coarse box voxels}
+bool bsconv_partition(const GatherGeom* g, int cnt, int64_t out[4]) {
+  BSPlan p;
+  if (!bs_plan(g, cnt, p)) return false;
+  out[0] = (int64_t)p.tiles * p.ncob; out[1] = p.nchunks; out[2] = p.tiles; out[3] = (int64_t)p.bq[0] * p.bq[1] * p.bq[2];
+  return true;
+}
 size_t bsconv_pack_elems(const GatherGeom* g, int cnt) {
   BSPlan p;
   return bs_plan(g, cnt, p) ? (size_t)p.ncob * 27 * p.nchunks * p.mt * 512 + 8 : 0;

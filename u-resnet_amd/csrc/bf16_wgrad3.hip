@@ -232,10 +232,14 @@ __global__ __launch_bounds__(256) void slab_fold_kernel(float* __restrict__ slab
   for (int k = k0 + 1; k < k1; ++k) acc += base[(size_t)k * per4 + i];
   base[(size_t)k0 * per4 + i] = acc;
 }
+static int slab_fold_group(int nslabs, size_t per) {   // slabs per group of the fold stage, 0: no fold stage
+  static const int group = ursn_env_int("URSN_SLAB_FOLD", 16);   // A/B: 0 | 1 = off
+  return (group < 2 || nslabs < 4 * group || (per & 3)) ? 0 : group;
+}
 static int slab_fold(float* slab, int& nslabs, int& stride, size_t per, hipStream_t s) {
   stride = 1;
-  static const int group = ursn_env_int("URSN_SLAB_FOLD", 16);   // A/B: 0 | 1 = off
-  if (group < 2 || nslabs < 4 * group || (per & 3)) return 0;
+  const int group = slab_fold_group(nslabs, per);
+  if (!group) return 0;
   const int ng = (nslabs + group - 1) / group;
   hipLaunchKernelGGL(slab_fold_kernel, dim3((unsigned)((per / 4 + 255) / 256), ng), dim3(256), 0, s, slab, nslabs, per / 4, group);
   URSN_HIP(hipGetLastError());
@@ -509,6 +513,16 @@ bool b3wgrad_scalar_ok(const GatherGeom& g) { return b3wgrad_ok(g) && w3_pair(g)
 size_t b3wgrad_scratch_bytes(const GatherGeom& g) {
   const int nt = g.K == 8 ? (w3_pair(g) ? WZ::NT : 15) : 27;
   return (size_t)w3_plan(g).grid * nt * 256 * sizeof(float) + 256;
+}
+
+// ursn_conv_partition: {workgroups = slabs written, planes per column, slabs the reduce kernel walks, slabs per fold group (0: no fold)}
+bool b3wgrad_partition(const GatherGeom& g, int64_t out[4]) {
+  if (!b3wgrad_ok(g)) return false;
+  const W3Plan p = w3_plan(g);
+  const int nt = g.K == 8 ? (w3_pair(g) ? WZ::NT : 15) : 27;
+  const int group = slab_fold_group(p.grid, (size_t)nt * 256);
+  out[0] = p.grid; out[1] = p.zseg; out[2] = group ? (p.grid + group - 1) / group : p.grid; out[3] = group;
+  return true;
 }
 
 template <int K, int NN, bool AFF>

@@ -260,6 +260,13 @@ bool dw_plan(const GatherGeom& g, DWPlan& p) {
 
 bool bdwgrad_ok(const GatherGeom& g) { DWPlan p; return dw_plan(g, p); }
 size_t bdwgrad_scratch_bytes(const GatherGeom& g) { DWPlan p; return dw_plan(g, p) ? p.scratch : 0; }
+// ursn_conv_partition: {workgroups, boxes a workgroup walks, slabs per channel block summed afterwards, boxes}
+bool bdwgrad_partition(const GatherGeom& g, int64_t out[4]) {
+  DWPlan p;
+  if (!dw_plan(g, p)) return false;
+  out[0] = (int64_t)p.nslices * p.ncib * p.ncob; out[1] = p.per; out[2] = p.nslices; out[3] = p.nboxes;
+  return true;
+}
 
 int launch_bdwgrad(const GatherGeom& g, const bf16_t* S, const bf16_t* C, float* dw, int Kw, int Nw, void* scratch, size_t scratch_bytes,
                    hipStream_t s) {

@@ -675,6 +675,54 @@ extern "C" int ursn_conv_plan(const ursn_conv_desc* d0, int32_t pass_, char* out
   return 0;
 }
 
+// the families' own plan functions, each the one its launcher calls
+bool deep_conv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]);
+bool pointwise_conv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]);
+bool b3conv_partition(const GatherGeom& g, int64_t out[4]);
+bool b3wgrad_partition(const GatherGeom& g, int64_t out[4]);
+bool bcbconv_partition(const GatherGeom& g, int64_t out[4]);
+bool bdconv_partition(const GatherGeom& g, int64_t out[4]);
+bool bdwgrad_partition(const GatherGeom& g, int64_t out[4]);
+bool bconv_partition(const GatherGeom& g, int64_t out[4]);
+bool bwgrad_partition(const GatherGeom& g, int64_t out[4]);
+bool bsconv_partition(const GatherGeom* g, int cnt, int64_t out[4]);
+
+// The work split the family ursn_conv_plan names takes for this descriptor / pass: host logic only, no device access.
+extern "C" int ursn_conv_partition(const ursn_conv_desc* d0, int32_t pass_, int64_t out[4]) {
+  URSN_REQUIRE(d0 && out && pass_ >= 0 && pass_ <= 2, "conv_partition: bad argument");
+  char name[32];
+  URSN_TRY(ursn_conv_plan(d0, pass_, name, sizeof(name)));
+  const ConvPass pass = (ConvPass)pass_;
+  auto is = [&](const char* f) { return strcmp(name, f) == 0; };
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  bool ok = false;
+  if (d0->dtype == 1) {
+    ursn_conv_desc d = *d0;
+    if (d.cin == 1) { d.cin = 8; d.in_cstride = 8; }
+    GatherGeom g[8];
+    const int n = build_geoms(d, pass, g);
+    URSN_REQUIRE(n >= 1, "conv_partition: bad descriptor");
+    int first = 0;
+    while (first < n - 1 && g[first].ntaps == 0) ++first;
+    if (is("b3conv")) ok = b3conv_partition(g[first], out);
+    else if (is("bcbconv")) ok = bcbconv_partition(g[first], out);
+    else if (is("bdconv")) ok = bdconv_partition(g[first], out);
+    else if (is("bconv")) ok = bconv_partition(g[first], out);
+    else if (is("bsconv")) ok = bsconv_partition(g, n, out);
+    else if (is("b3wgrad")) ok = b3wgrad_partition(g[0], out);
+    else if (is("bdwgrad")) ok = bdwgrad_partition(g[0], out);
+    else if (is("bwgrad")) ok = bwgrad_partition(g[0], out);
+  } else {
+    if (is("dconv")) ok = deep_conv_partition(*d0, pass, out);
+    else if (is("pconv")) ok = pointwise_conv_partition(*d0, pass, out);
+  }
+  if (!ok) {
+    ursn_set_error("conv_partition: the partition of family %s is not reported", name);
+    return 4;
+  }
+  return 0;
+}
+
 extern "C" size_t ursn_conv_wgrad_scratch_bytes(const ursn_conv_desc* d) {
   if (!d) return 0;
   GatherGeom g[8];

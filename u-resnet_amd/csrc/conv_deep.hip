@@ -414,6 +414,17 @@ size_t deep_conv_stats_scratch_doubles(const ursn_conv_desc& d) {
   return p.gsplit > 1 ? (size_t)p.red_blocks * 2 * p.Nn : (size_t)p.boxes * p.tpb * p.ncob * 128;
 }
 
+// ursn_conv_partition: {workgroups, chunk rounds per workgroup, split-K slabs summed afterwards (0: none), SLAB flag}
+bool deep_conv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]) {
+  DCPlan p;
+  if (!dc_plan(d, pass, p)) return false;
+  out[0] = (int64_t)p.boxes * p.tpb * p.gsplit * p.ncob;
+  out[1] = p.rounds;
+  out[2] = p.gsplit > 1 ? p.gsplit : 0;
+  out[3] = p.gsplit > 1 ? 1 : 0;
+  return true;
+}
+
 template <int NTAP, bool STATS, bool SLAB>
 static int dc_launch(const DCPlan& p, const DCArgs& a, hipStream_t s) {
   auto kern = dconv_kernel<NTAP, STATS, SLAB>;

@@ -319,6 +319,24 @@ static int pconv_grid_cap() {   // workgroups of the forward / data-gradient ker
   return cap < 1 ? 1 : cap;
 }
 
+static int pconv_grid(int64_t nvox) {
+  const int cap = pconv_grid_cap();
+  int64_t blocks = cdiv64(nvox, 256 * 4);
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+// ursn_conv_partition: {workgroups, 256-voxel steps of the first workgroup, rows of statistics partials written, voxels of the last step}
+bool pointwise_conv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]) {
+  int lo[3], sm[3];
+  int64_t nvox;
+  if (!pw_geometry(d, lo, sm, nvox)) return false;
+  const int grid = pconv_grid(nvox);
+  out[0] = grid; out[1] = cdiv64(nvox, (int64_t)grid * 256); out[2] = pass == PASS_FWD ? grid : 0;
+  out[3] = nvox - (cdiv64(nvox, 256) - 1) * 256;
+  return true;
+}
+
 size_t pointwise_stats_scratch_doubles(const ursn_conv_desc& d) {
   if (!pointwise_conv_supported(d, PASS_FWD, 0)) return 0;
   return (size_t)pconv_grid_cap() * 2 * d.cout;
@@ -352,11 +370,7 @@ int launch_pointwise_conv(const ursn_conv_desc& d, ConvPass pass, const float* i
     else { URSN_REQUIRE(d.x2, "pointwise conv: split input without x2"); a.in2 = d.x2; a.in2_cs = i2; }
   }
   const int ck = flip ? d.cout : d.cin, cp = flip ? d.cin : d.cout;
-  const int cap = pconv_grid_cap();
-  int64_t blocks = cdiv64(a.nvox, 256 * 4);
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  const int grid = (int)blocks;
+  const int grid = pconv_grid(a.nvox);
   ursn_note_kernel(flip ? "pconv_dgrad" : "pconv");
   int rc = 3;
   if (ck == 8 && cp == 16) rc = pconv_launch<8, 16>(a, flip, grid, s);
