@@ -894,6 +894,59 @@ int ursn_read_loss_terms(ursn_net* net, float* out2, void* stream);
  * Every other family (their splits have no plan struct, or no switch moves them): returns non-zero, "not reported". */
 int ursn_conv_partition(const ursn_conv_desc* d, int32_t pass, int64_t out[4]);
 
+/* ---- voxel clusters: connected components of a voxel list (cluster.hip) -----------------------------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * The step every consumer takes after the per-voxel class: touching voxels become track and shower clusters, small fragments are
+ * dropped.  Done on the sorted per-event lists themselves (ursn_voxel_batch's offsets / index, row-major in `spatial`: the network's
+ * shape, or `big` of a tiled event), so time and scratch scale with the list and never with the volume.
+ *
+ * An entry PARTICIPATES when its index lies in [0, prod(spatial)) and bit cls[j] of class_mask is set (a class >= 32 never does).
+ * Two participating entries of ONE event are joined when their coordinates differ by at most 1 on every axis and in at most A axes:
+ * 3-D connectivity 6 | 18 | 26 is A = 1 | 2 | 3, 2-D connectivity 4 | 8 is A = 1 | 2; with same_class they must also have equal
+ * class.  Adjacency is decided on coordinates: linear indices that differ by 1 across a row end, or by one row across a plane end,
+ * are not neighbours.  Clusters are the connected components of that relation with at least min_size entries, numbered per event
+ * from 0 in the order of their lowest list position (scipy.ndimage.label's numbering for a raster-ordered list).  Every other entry
+ * gets cluster -1.  Events without entries are legal; entries of different events never join.
+ * Per-cluster table (optional): first = the cluster's lowest list position counted from its event's first entry (a list position,
+ * not a voxel index), size = its entry count, cls = the class of `first`.
+ *
+ * Method: union-find over list positions.  Neighbours are found by binary searches confined to the event's range of the list and
+ * the consecutive entries of the neighbouring row; links are made with 32-bit integer atomicMin and sizes summed with 32-bit integer
+ * atomicAdd in global memory.  The outputs do not depend on arrival order: every link points from a higher position to a lower one,
+ * so a component's representative is its lowest list position whatever order the merges land in, and sizes are integer sums.  No
+ * float atomics.  Every device loop is bounded (parent pointers only decrease, each loop carries a trip cap taken from the list
+ * length); a thread that exceeds one sets *status non-zero and leaves -- the outputs are then not valid.  The ids are formed in a
+ * later launch than the merges.  Seven launches; enqueues only, never synchronises; the scratch needs no initialisation; the same
+ * arguments give the same bits.  Null, misaligned, out-of-domain and too-small arguments are refused with a message before any
+ * launch; m_total = 0 launches one kernel that writes count, table_offsets and status and reads no list. */
+typedef struct ursn_cluster_desc {      /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* shape the indices are row-major in, prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int64_t m_total;                      /* list entries, < 2^31; positions at or beyond it are never read or written */
+  const int64_t* offsets;               /* [n+1] as in ursn_voxel_batch */
+  const int32_t* index;                 /* [m_total] strictly increasing per event */
+  const uint8_t* cls;                   /* [m_total] class of each entry (pred, ana, or a true label) */
+  int32_t connectivity;                 /* 3-D: 6 | 18 | 26;  2-D: 4 | 8 */
+  uint32_t class_mask;                  /* bit k: entries of class k take part; all others get cluster -1 */
+  int32_t same_class;                   /* 1: only entries of equal class join;  0: any two participating entries */
+  int32_t min_size;                     /* >= 1: components with fewer entries are dropped (cluster -1) and not numbered */
+} ursn_cluster_desc;
+
+typedef struct ursn_cluster_out {       /* DEVICE pointers */
+  int32_t* cluster;                     /* [m_total] event-local id 0..K_e-1, or -1 */
+  int32_t* count;                       /* [n] K_e */
+  int32_t* first; int32_t* size; uint8_t* cls;   /* optional per-cluster table, [cap] each, events back to back in id order */
+  int64_t* table_offsets;               /* [n+1], needed iff a table array is given; true counts whatever cap is */
+  int64_t cap;                          /* table rows at or beyond cap are never written */
+  int32_t* status;                      /* [1] 0, or non-zero if a bounded device loop ran out */
+} ursn_cluster_out;
+
+/* Bytes of scratch for a list of m_total entries: 8-byte aligned, at least 8; 0 for n outside [1, 65535] or m_total outside
+ * [0, 2^31).  Host logic only. */
+size_t ursn_cluster_scratch_bytes(int32_t n, int64_t m_total);
+int ursn_cluster_voxels(const ursn_cluster_desc* d, const ursn_cluster_out* out, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,17 @@ class ursn_crop_out(C.Structure):
                 ("weight", C.c_void_p), ("bg_weight", C.c_void_p), ("src", C.c_void_p), ("owned", C.c_void_p), ("cap", C.c_int64)]
 
 
+class ursn_cluster_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("m_total", C.c_int64),
+                ("offsets", C.c_void_p), ("index", C.c_void_p), ("cls", C.c_void_p), ("connectivity", C.c_int32),
+                ("class_mask", C.c_uint32), ("same_class", C.c_int32), ("min_size", C.c_int32)]
+
+
+class ursn_cluster_out(C.Structure):
+    _fields_ = [("cluster", C.c_void_p), ("count", C.c_void_p), ("first", C.c_void_p), ("size", C.c_void_p), ("cls", C.c_void_p),
+                ("table_offsets", C.c_void_p), ("cap", C.c_int64), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -222,6 +233,8 @@ _SIGS = {
     "ursn_eval_loss": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(ursn_loss_desc), _P]),
     "ursn_read_loss_terms": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
     "ursn_conv_partition": (C.c_int, [C.POINTER(ursn_conv_desc), C.c_int32, C.POINTER(C.c_int64)]),
+    "ursn_cluster_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "ursn_cluster_voxels": (C.c_int, [C.POINTER(ursn_cluster_desc), C.POINTER(ursn_cluster_out), _P, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -141,6 +141,18 @@ class ssnet_config(object):
     LOSS_DICE_WEIGHT = 0.
     LOSS_DICE_EPS = 1.
     LOSS_IGNORE_LABEL = -1
+    # not in the reference, whose users group the predicted voxels into objects on the host.  ANA_CLUSTER 'pred' | 'ana' (with
+    # TRAIN False) = ana_step labels the connected components of the argmax class / the ana label at the event's listed voxels on
+    # the device (ssnet_base.set_clustering; clusters.py holds the definition): batch mode appends a fourth record per event, the
+    # cluster id (-1: none) of every voxel of the set, and the interactive result's per-event dicts gain cluster / clusters.  Needs
+    # SPARSE_IO with SPARSE_SCORES or ANA_TILE (tiled: clusters cross tile borders); refused together with ANA_CSV.
+    # CLUSTER_CONNECTIVITY 0 = 26 in 3-D and 8 in 2-D, else 6 | 18 | 26 | 4 | 8; CLUSTER_CLASSES [] = every class but 0;
+    # CLUSTER_MIN_SIZE = components with fewer voxels get no id.  '' = off.  Ignored with TRAIN, like every ANA_* key; refused
+    # together with ANA_TTA (cluster the averaged result with ssnet_base.cluster_voxels instead)
+    ANA_CLUSTER = ''
+    CLUSTER_CONNECTIVITY = 0
+    CLUSTER_CLASSES = []
+    CLUSTER_MIN_SIZE = 1
 
     def __init__(self):
         pass
@@ -237,7 +249,28 @@ class ssnet_config(object):
             if key == 'LOSS_DICE_EPS' and not 0.0 < value < float('inf'):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
+            if key == 'ANA_CLUSTER' and value not in ('', 'pred', 'ana'):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CLUSTER_CONNECTIVITY' and value not in (0, 4, 8, 6, 18, 26):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CLUSTER_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value)
+                                                 and len(set(value)) == len(value)):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CLUSTER_MIN_SIZE' and value < 1:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
             setattr(self, key, value)
+
+    def cluster_spec(self):
+        """The clusters.ClusterSpec of the CLUSTER_* keys, or None while ANA_CLUSTER is off."""
+        if not self.ANA_CLUSTER:
+            return None
+        from .clusters import ClusterSpec
+        return ClusterSpec(self.CLUSTER_CONNECTIVITY or None, self.CLUSTER_CLASSES or None, True, self.CLUSTER_MIN_SIZE,
+                           self.ANA_CLUSTER)
 
     def loss_spec(self):
         """The losses.LossSpec of the LOSS_* keys, or None while they all hold their defaults (the plan's head runs)."""

@@ -1010,8 +1010,9 @@ class ssnet_base(object):
         import torch
         self._require_single_channel('inference_voxel_scores')
         want = tuple(want)
-        if not want or any(w not in ('scores', 'pred', 'ana') for w in want):
-            raise ValueError("inference_voxel_scores: want = %r, expected a non-empty subset of ('scores', 'pred', 'ana')" % (want,))
+        spec = self._cluster_wanted(want)
+        if not want or any(w not in ('scores', 'pred', 'ana') for w in want if spec is None or w != 'cluster'):
+            raise ValueError("inference_voxel_scores: want = %r, expected a non-empty subset of %r" % (want, self._want_names()))
         if 'ana' in want and self._num_class < 3:
             raise ValueError('inference_voxel_scores: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
         fd = self._feed_voxels(voxels, with_label=with_labels, with_weight=False)
@@ -1022,7 +1023,8 @@ class ssnet_base(object):
         M = int(off[-1])
         kinds = {'scores': ((max(M, 1), self._num_class), torch.float32), 'pred': ((max(M, 1),), torch.uint8),
                  'ana': ((max(M, 1),), torch.uint8)}
-        dev = {w: torch.empty(kinds[w][0], dtype=kinds[w][1], device=self._device) for w in want}
+        made = [w for w in want if w != 'cluster'] + ([spec.on] if spec is not None and spec.on not in want else [])
+        dev = {w: torch.empty(kinds[w][0], dtype=kinds[w][1], device=self._device) for w in made}
         acc = (ctypes.c_float * 2)()
         _lib.check(_lib.load().ursn_infer_voxels(self._handle, self._ptr(fd['input_data']), self._ptr(fd.get('input_label')), n,
                                                  ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_index), M, self._ptr(dev.get('scores')),
@@ -1030,16 +1032,135 @@ class ssnet_base(object):
                                                  acc if with_labels else None, self._stream(sess)))
         self._last_feed = fd
         self._mark_consumed(fd)
+        pending = None
+        if spec is not None:                       # behind the gather head, on the list it read
+            pending = self._enqueue_clusters(sess, d_offsets, d_index, dev[spec.on], n, M, self._dims[:-1], spec)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self._device))
         slot.consumed[turn] = done                 # the gather head has read offsets / index: the list buffer is free again
         res = {'index': [voxels.index[off[i]:off[i + 1]].copy() for i in range(n)]}
         for w in want:
+            if w == 'cluster':
+                continue
             host = dev[w][:M].cpu().numpy()
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
+        if pending is not None:
+            res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
+
+    # ------------------------------------------------------------------------------------------
+    # voxel clusters (not in the reference, whose users label the dense volume on the host; definition and numpy statement:
+    # clusters.py, device passes: csrc/cluster.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_clustering(self, spec):
+        """A ``clusters.ClusterSpec`` makes ``'cluster'`` a legal member of ``want`` in ``inference_voxel_scores`` and
+        ``inference_tiled_voxel_scores`` (their defaults do not change); None takes it away again.  With it wanted the class array
+        ``spec.on`` is made on the device even when it is not itself wanted, the cluster passes are enqueued behind the gather head
+        (tiled: behind the last scatter, on the stitched list in the large shape) and the result gains ``cluster`` (int32 [m_i] per
+        event, -1 = no cluster) and ``clusters`` (per event a dict of ``first`` / ``size`` / ``cls``)."""
+        from .clusters import ClusterSpec
+        if spec is not None:
+            if not isinstance(spec, ClusterSpec):
+                raise ValueError('set_clustering: spec = %r, expected a clusters.ClusterSpec or None' % (spec,))
+            spec.axes(len(self._dims) - 1)
+            if spec.on == 'ana' and self._num_class < 3:
+                raise ValueError('set_clustering: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
+        self._cluster_spec = spec
+
+    def _cluster_wanted(self, want):
+        """The spec when ``'cluster'`` is wanted and one is set, else None (``'cluster'`` is then an unknown name like any other)."""
+        spec = getattr(self, '_cluster_spec', None)
+        return spec if spec is not None and 'cluster' in want else None
+
+    def _want_names(self):
+        """The legal members of ``want`` of the voxel-score calls: ``'cluster'`` only while a spec is set."""
+        return ('scores', 'pred', 'ana') + (('cluster',) if getattr(self, '_cluster_spec', None) is not None else ())
+
+    def _enqueue_clusters(self, sess, d_offsets, d_index, d_cls, n, M, shape, spec):
+        """``ursn_cluster_voxels`` on device lists (raw pointers or tensors); enqueues only.  Returns what ``_fetch_clusters`` reads."""
+        import torch
+        lib = _lib.load()
+        shape = [int(s) for s in shape]
+        conn, _ = spec.axes(len(shape))
+        need = int(lib.ursn_cluster_scratch_bytes(n, M))
+        if need == 0:
+            raise ValueError('clusters: %d events with %d list entries are out of domain' % (n, M))
+        scratch = getattr(self, '_cluster_scratch_buf', None)
+        if scratch is None or scratch.numel() * 8 < need:
+            scratch = self._cluster_scratch_buf = torch.empty((need + 7) // 8, dtype=torch.int64, device=self._device)
+        cap = max(M, 1)
+        ints = torch.empty(3 * cap + n + 1, dtype=torch.int32, device=self._device)    # cluster | first | size | count | status
+        tcls = torch.empty(cap, dtype=torch.uint8, device=self._device)
+        toff = torch.empty(n + 1, dtype=torch.int64, device=self._device)
+        ptr = lambda x: x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_desc()
+        d.ndim, d.n, d.m_total = len(shape), n, M
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.cls = ptr(d_offsets), ptr(d_index), ptr(d_cls)
+        d.connectivity, d.class_mask, d.same_class, d.min_size = conn, spec.class_mask(), int(spec.same_class), spec.min_size
+        o = _lib.ursn_cluster_out()
+        base = ints.data_ptr()
+        o.cluster, o.first, o.size, o.count, o.status = base, base + 4 * cap, base + 8 * cap, base + 12 * cap, base + 12 * cap + 4 * n
+        o.cls, o.table_offsets, o.cap = tcls.data_ptr(), toff.data_ptr(), M
+        _lib.check(lib.ursn_cluster_voxels(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), scratch.numel() * 8,
+                                           self._stream(sess)))
+        return ints, tcls, toff, cap, n, M
+
+    @staticmethod
+    def _fetch_clusters(pending, off):
+        """The [M]-sized ids and the per-cluster table as per-event lists; raises when a bounded device loop ran out."""
+        ints, tcls, toff, cap, n, M = pending
+        toff = toff.cpu().numpy()
+        total = int(toff[-1])
+        small = ints[3 * cap:].cpu().numpy()
+        if int(small[n]) != 0:
+            raise _lib.UrsnError('cluster_voxels: a bounded device loop ran out (status %d); the ids are not valid' % int(small[n]))
+        assert 0 <= total <= M and np.array_equal(np.diff(toff), small[:n]), 'cluster_voxels: table offsets and counts disagree'
+        cluster = ints[:M].cpu().numpy()
+        first, size = ints[cap:cap + total].cpu().numpy(), ints[2 * cap:2 * cap + total].cpu().numpy()
+        cls = tcls[:total].cpu().numpy()
+        per_event = [cluster[off[i]:off[i + 1]].copy() for i in range(n)]
+        tables = [{'first': first[toff[i]:toff[i + 1]].copy(), 'size': size[toff[i]:toff[i + 1]].copy(),
+                   'cls': cls[toff[i]:toff[i + 1]].copy()} for i in range(n)]
+        return per_event, tables
+
+    def cluster_voxels(self, sess, voxels_or_lists, cls, spec, shape=None):
+        """Clusters of any per-event index lists and classes: ``voxels_or_lists`` is a VoxelBatch or a list of sorted per-event
+        index arrays, ``cls`` the classes as one flat array or per-event arrays (the ``pred`` / ``ana`` lists of
+        ``inference_voxel_scores_tta``, or true labels for a comparison against truth), ``shape`` the spatial shape the indices are
+        row-major in (None: the network's).  Returns ``{'cluster': [...], 'clusters': [...]}`` as ``set_clustering`` describes."""
+        import torch
+        from .clusters import ClusterSpec
+        if not isinstance(spec, ClusterSpec):
+            raise ValueError('cluster_voxels: spec = %r, expected a clusters.ClusterSpec' % (spec,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        spec.axes(len(shape))
+        if any(s < 1 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_voxels: shape = %r, expected extents >= 1 with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_voxels: %d events outside [1, 65535]' % n)
+        if isinstance(cls, (list, tuple)):
+            cls = np.concatenate([np.asarray(c).reshape(-1) for c in cls]) if len(cls) else np.zeros(0, np.uint8)
+        cls = np.asarray(cls).reshape(-1)
+        if cls.size != M or index.size != M:
+            raise ValueError('cluster_voxels: %d list entries, %d indices, %d classes' % (M, index.size, cls.size))
+        if M and (cls.min() < 0 or cls.max() > 255 or not np.array_equal(cls, cls.astype(np.uint8))):
+            raise ValueError('cluster_voxels: classes must be integers in [0, 255]')
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        d_off, d_index, d_cls = up(off, np.int64), up(index, np.int32), up(cls, np.uint8)
+        pending = self._enqueue_clusters(sess, d_off, d_index, d_cls, n, M, shape, spec)
+        cluster, tables = self._fetch_clusters(pending, off)
+        return {'cluster': cluster, 'clusters': tables}
 
     # ------------------------------------------------------------------------------------------
     # tiling: volumes larger than the network (not in the reference, whose events have the network's size; boxes, their
@@ -1220,9 +1341,10 @@ class ssnet_base(object):
         from . import tiling
         self._require_single_channel('inference_tiled_voxel_scores')
         want = tuple(want)
-        if not want or any(w not in ('scores', 'pred', 'ana') for w in want):
-            raise ValueError("inference_tiled_voxel_scores: want = %r, expected a non-empty subset of ('scores', 'pred', 'ana')"
-                             % (want,))
+        spec = self._cluster_wanted(want)
+        if not want or any(w not in ('scores', 'pred', 'ana') for w in want if spec is None or w != 'cluster'):
+            raise ValueError("inference_tiled_voxel_scores: want = %r, expected a non-empty subset of %r"
+                             % (want, self._want_names()))
         if 'ana' in want and self._num_class < 3:
             raise ValueError('inference_tiled_voxel_scores: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
         if tile_batch is not None and int(tile_batch) < 1:
@@ -1244,7 +1366,8 @@ class ssnet_base(object):
         host_counts = counts.cpu().numpy()
         keep = np.flatnonzero(host_counts[1] > 0)
         kinds = {'scores': ((max(M, 1), C), torch.float32), 'pred': ((max(M, 1),), torch.uint8), 'ana': ((max(M, 1),), torch.uint8)}
-        out = {w: torch.zeros(kinds[w][0], dtype=kinds[w][1], device=self._device) for w in want}
+        made = [w for w in want if w != 'cluster'] + ([spec.on] if spec is not None and spec.on not in want else [])
+        out = {w: torch.zeros(kinds[w][0], dtype=kinds[w][1], device=self._device) for w in made}
         forwards = 0
         if keep.size:
             run = boxes.select(keep)
@@ -1257,7 +1380,7 @@ class ssnet_base(object):
             bufs = {'offsets': torch.empty(tb + 1, dtype=torch.int64, device=self._device), 'index': i32(cap),
                     'value': torch.empty(max(cap, 1), dtype=torch.float32, device=self._device), 'src': i32(cap),
                     'owned': torch.empty(max(cap, 1), dtype=torch.uint8, device=self._device)}
-            rows = {w: torch.empty((max(cap, 1),) + kinds[w][0][1:], dtype=kinds[w][1], device=self._device) for w in want}
+            rows = {w: torch.empty((max(cap, 1),) + kinds[w][0][1:], dtype=kinds[w][1], device=self._device) for w in made}
             o = _lib.ursn_crop_out()
             for name, t in bufs.items():
                 setattr(o, name, t.data_ptr())
@@ -1283,10 +1406,17 @@ class ssnet_base(object):
                 self._mark_consumed(fd)
                 forwards += 1
         off = big_batch.offsets
+        pending = None
+        if spec is not None:                       # behind the last scatter, on the stitched list in the large shape
+            pending = self._enqueue_clusters(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], out[spec.on], n, M, big, spec)
         res = {'index': [big_batch.index[off[i]:off[i + 1]].copy() for i in range(n)]}
         for w in want:
+            if w == 'cluster':
+                continue
             host = out[w][:M].cpu().numpy()
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
+        if pending is not None:
+            res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

@@ -163,6 +163,18 @@ class ssnet_trainval(object):
             if not cfg.TRAIN and (cfg.ANA_CSV or cfg.ANA_TTA):
                 raise ValueError('ANA_TILE cannot be combined with ANA_CSV or ANA_TTA: a tiled analysis returns the scores at the '
                                  'listed voxels of the large event')
+        self._cluster_spec = None
+        if cfg.ANA_CLUSTER and not cfg.TRAIN:
+            if cfg.ANA_CSV:
+                raise ValueError('ANA_CLUSTER cannot be combined with ANA_CSV: the clusters are formed at the listed voxels of a '
+                                 'voxel-list result, the per-class statistics run over every voxel')
+            if not (cfg.SPARSE_IO and (cfg.SPARSE_SCORES or cfg.ANA_TILE)):
+                raise ValueError('ANA_CLUSTER needs SPARSE_IO True with SPARSE_SCORES True or ANA_TILE: the clusters are formed on '
+                                 'the voxel lists those results hold')
+            if cfg.ANA_TTA and not cfg.ANA_TILE:
+                raise ValueError('ANA_CLUSTER cannot be combined with ANA_TTA in the driver: cluster the averaged result with '
+                                 'ssnet_base.cluster_voxels')
+            self._cluster_spec = cfg.cluster_spec()
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -194,6 +206,8 @@ class ssnet_trainval(object):
                             precision=cfg.PRECISION, **extra)
         self._sess = HipSession()
         self._skipped_reported = 0
+        if self._cluster_spec is not None:   # default off: never called
+            self._net.set_clustering(self._cluster_spec)
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -522,9 +536,11 @@ class ssnet_trainval(object):
         """SPARSE_IO + SPARSE_SCORES: the output side is a voxel list too (``inference_voxel_scores``), nothing dense is built on
         the host or copied in either direction.  Records per event: ``np.save(index)``, ``np.save(class)`` -- byte for byte those of
         ``_ana_step_voxels`` (the label rule ends in ``* (data > 1.0)``, so the voxel set lies inside the event's list) -- then
-        ``np.save(scores[ana != 0])``, the class scores of the voxels in the set, in set order.  Interactive mode returns
+        ``np.save(scores[ana != 0])``, the class scores of the voxels in the set, in set order; with ANA_CLUSTER a fourth,
+        ``np.save(cluster[ana != 0])``, their cluster ids (and ``cluster`` / ``clusters`` in the per-event dicts).  Interactive mode returns
         ``entries`` / ``acc_all`` / ``acc_nonzero`` and ``voxels``, the per-event list of index / value / label / scores / pred."""
-        want = ('scores',) + (('ana',) if self._output else ()) + (() if batch_mode else ('pred',))
+        clustered = getattr(self, '_cluster_spec', None) is not None
+        want = ('scores',) + (('ana',) if self._output else ()) + (() if batch_mode else ('pred',)) + (('cluster',) if clustered else ())
         r = self._net.inference_voxel_scores(self._sess, vb, with_labels=True, want=want)
         acc_all, acc_nonzero = r['acc_all'], r['acc_nonzero']
         if self._output:
@@ -534,6 +550,8 @@ class ssnet_trainval(object):
                 np.save(self._output, r['index'][i][keep])
                 np.save(self._output, r['ana'][i][keep])
                 np.save(self._output, r['scores'][i][keep])
+                if clustered:
+                    np.save(self._output, r['cluster'][i][keep])
             self._output.flush()
         result = None
         if not batch_mode:
@@ -541,6 +559,9 @@ class ssnet_trainval(object):
             events = [{'index': r['index'][i], 'value': vb.value[off[i]:off[i + 1]].copy(),
                        'label': vb.label[off[i]:off[i + 1]].copy(), 'scores': r['scores'][i], 'pred': r['pred'][i]}
                       for i in range(vb.n)]
+            if clustered:
+                for i, ev in enumerate(events):
+                    ev['cluster'], ev['clusters'] = r['cluster'][i], r['clusters'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
         self._advance_main()
         return result
@@ -551,7 +572,8 @@ class ssnet_trainval(object):
         indices in the large shape, plus ``tiles`` = (run, total).  Only the listed voxels have scores: ``acc_nonzero`` (over
         data > 0, which all lie in the list) is exact, ``acc_all`` is None."""
         c = self._cfg
-        want = ('scores', 'pred') + (('ana',) if self._output else ())
+        clustered = getattr(self, '_cluster_spec', None) is not None
+        want = ('scores', 'pred') + (('ana',) if self._output else ()) + (('cluster',) if clustered else ())
         r = self._net.inference_tiled_voxel_scores(self._sess, vb, c.ANA_TILE, halo=c.ANA_TILE_HALO, tile_batch=c.ANA_TILE_BATCH,
                                                    want=want)
         lit = vb.value > 0
@@ -564,6 +586,8 @@ class ssnet_trainval(object):
                 np.save(self._output, r['index'][i][keep])
                 np.save(self._output, r['ana'][i][keep])
                 np.save(self._output, r['scores'][i][keep])
+                if clustered:
+                    np.save(self._output, r['cluster'][i][keep])
             self._output.flush()
         result = None
         if not batch_mode:
@@ -571,6 +595,9 @@ class ssnet_trainval(object):
             events = [{'index': r['index'][i], 'value': vb.value[off[i]:off[i + 1]].copy(),
                        'label': vb.label[off[i]:off[i + 1]].copy(), 'scores': r['scores'][i], 'pred': r['pred'][i]}
                       for i in range(vb.n)]
+            if clustered:
+                for i, ev in enumerate(events):
+                    ev['cluster'], ev['clusters'] = r['cluster'][i], r['clusters'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
         self._advance_main()
