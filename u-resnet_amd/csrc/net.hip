@@ -15,6 +15,8 @@
 #include "ext_loss.h"
 #include "loss_head.h"
 #include "bn_moving.h"
+#include "prof_log.h"
+#include "topology.h"
 
 int conv_dispatch(const ursn_conv_desc& d, ConvPass pass, const float* in, const float* w, float* out, int accumulate,
                   hipStream_t s);
@@ -30,12 +32,8 @@ struct Act {       // activation tensor view (+ gradient view with identical lay
   int flag = -1;   // index into ursn_net::ginit (gradient-initialised state shared between views)
 };
 
-struct Layer {
-  std::string name;
-  int kind = 0;  // 0 conv, 1 deconv
-  int k = 3, stride = 1, cin = 0, cout = 0, lin = 0, lout = 0;
-  int relu = 0;  // activation_fn of the slim layer call (conv0 / deconv / conv1: ReLU; all others None)
-  int64_t w_off = 0, b_off = 0, w_n = 0;
+struct Layer : TopoLayer {   // the topology row + what the fp32 plan adds to it
+  Layer(const TopoLayer& row) : TopoLayer(row) {}
   ursn_conv_desc desc;
   float *z = nullptr, *dz = nullptr, *mean = nullptr, *rstd = nullptr;
   float* coef = nullptr;   // [6][zcs]: BatchNorm-backward apply coefficients for the data-gradient kernel (ursn_conv_desc.vdz_coef)
@@ -43,9 +41,8 @@ struct Layer {
                 // multiple of 4), pad lanes stay 0
 };
 
-struct Unit {
-  std::string scope;
-  int sc = -1, c1 = -1, c2 = -1;  // layer indices
+struct Unit : TopoUnit {
+  Unit(const TopoUnit& row) : TopoUnit(row) {}
   Act in, a1, out;
   Act in2;   // C > 0: the unit input is the never-materialised concat [in | in2] (decoder, narrow levels)
   bool a1_virtual = false;   // a1 = BN(z1) is never written: conv2 and its weight gradient normalise z1 while staging
@@ -54,18 +51,13 @@ struct Unit {
 
 }  // namespace
 
-struct ursn_net {
+struct ursn_net : TopoShape {   // nlev / ldim / lvox / deconv / cat_names / conv0..2: the table's, assigned by plan()
   ursn_bnet* bf = nullptr;   // act_dtype == 1: the bf16 mixed-precision plan (net_bf16.hip) executes the fetch-sets
   ursn_config cfg;
   ursn_sizes sizes;
-  int nlev = 0;
-  int ldim[8][3];        // spatial dims per level (3 entries, leading 1 for 2-D)
-  int64_t lvox[8];       // voxels per image per level
   std::vector<Layer> layers;
   std::vector<Unit> units;           // encoder units then decoder units, execution order
-  std::vector<int> deconv;           // layer index per decoder step
   std::vector<Act> deconv_in, deconv_out, cat;  // per decoder step
-  int conv0 = -1, conv1 = -1, conv2 = -1;
   Act a_data, a_conv0, a_conv1, a_pre1;  // a_pre1: input of conv1 (last decoder unit output)
   std::vector<int> ginit;
   float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
@@ -96,12 +88,7 @@ struct ursn_net {
   // (0 none ran, 1 pending, 2 consumed by a backward, 3 overwritten by another run call, 4 parameters changed by apply_adam)
   int pend_state = 0, pend_n = 0;
   const float* pend_data = nullptr;
-  // optional per-launch timing with HIP events on the launch stream (bench.py roofline leg)
-  bool profile = false;
-  struct ProfRec { int layer; int pass; const char* kernel; double flops; double bytes; hipEvent_t e0, e1; long l0; int launches; };
-  std::vector<ProfRec> prof;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
+  ProfLog prof;   // optional per-launch timing (prof_log.h)
   // weight gradients run on a second stream: they only feed the optimiser, so they overlap the HBM-bound
   // BN-backward passes and the low-occupancy deep-level kernels of the main chain (URSN_WGRAD_STREAM=0 disables)
   hipStream_t s2 = nullptr;
@@ -118,7 +105,6 @@ struct ursn_net {
   std::vector<hipEvent_t> fwd_pool;   // forward: fork / join events of the side-stream shortcut convs
   size_t fwd_used = 0;
   hipEvent_t s2_done = nullptr;
-  std::vector<std::pair<std::string, std::string>> cat_names;   // per decoder step: producers of [first | second] channel halves
   std::map<std::string, Act> named;       // debug lookup: activations
   std::map<std::string, int> named_z;     // layer name -> layer index
   BnmState bnm;                           // BatchNorm moving statistics (bn_moving.hip); the bf16 plan keeps its own
@@ -151,64 +137,38 @@ Act sub_act(const Act& full, int c0, int C) {
   return a;  // same cs, same flag
 }
 
-int add_layer(ursn_net* n, Arena& A, const std::string& name, int kind, int k, int s, int ci, int co, int lin, int lout,
-              int64_t& poff, int relu = 0) {
-  Layer L;
-  L.name = "UResNet/" + name;
-  L.relu = relu;
-  L.kind = kind; L.k = k; L.stride = s; L.cin = ci; L.cout = co; L.lin = lin; L.lout = lout;
-  int64_t taps = 1;
-  for (int j = 0; j < n->cfg.ndim; ++j) taps *= k;
-  L.w_n = taps * ci * co;
-  L.w_off = poff; poff += L.w_n;
-  L.b_off = poff; poff += co;
+// carves the tensors of layer li (its row came from the topology table) and fills its conv descriptor
+void carve_layer(ursn_net* n, Arena& A, int li) {
+  Layer& L = n->layers[li];
   memset(&L.desc, 0, sizeof(L.desc));
   L.desc.ndim = n->cfg.ndim;
   L.desc.n = n->cfg.max_batch;
-  for (int j = 0; j < n->cfg.ndim; ++j) L.desc.in_sp[j] = n->ldim[lin][3 - n->cfg.ndim + j];
-  L.desc.cin = ci; L.desc.cout = co; L.desc.k = k; L.desc.stride = s; L.desc.transposed = kind;
-  L.zcs = (co + 3) & ~3;
+  for (int j = 0; j < n->cfg.ndim; ++j) L.desc.in_sp[j] = n->ldim[L.lin][3 - n->cfg.ndim + j];
+  L.desc.cin = L.cin; L.desc.cout = L.cout; L.desc.k = L.k; L.desc.stride = L.stride; L.desc.transposed = L.kind;
+  L.zcs = (L.cout + 3) & ~3;
   L.desc.out_cstride = L.zcs;
-  int64_t e = (int64_t)n->cfg.max_batch * n->lvox[lout] * L.zcs;
+  int64_t e = (int64_t)n->cfg.max_batch * n->lvox[L.lout] * L.zcs;
   L.z = A.floats(e);
   L.dz = n->cfg.trainable ? A.floats(e) : nullptr;
   L.mean = A.floats(L.zcs);   // padded like z: pad entries stay 0 (a BN over the padded channel count yields dz = 0 there)
   L.rstd = A.floats(L.zcs);
   L.coef = n->cfg.trainable ? A.floats(6 * L.zcs) : nullptr;
-  n->layers.push_back(L);
-  n->named_z[L.name] = (int)n->layers.size() - 1;
-  return (int)n->layers.size() - 1;
+  n->named_z[L.name] = li;
 }
 
-// Builds the whole plan; with A.base == nullptr only sizes are computed.
+// Builds the whole plan; with A.base == nullptr only sizes are computed.  The shape comes from the topology table (topology.h):
+// the walk below carves the arena in the table's order and decides what is this plan's own.
 int plan(ursn_net* n, Arena& A) {
   const ursn_config& c = n->cfg;
-  URSN_REQUIRE(c.ndim == 2 || c.ndim == 3, "len(dims) must be 3 (H,W,C) or 4 (H,W,D,C)");
-  // the decoder scopes are the reference's literal 'resnet_module%d' % (step + 5) (lib/uresnet.py:100): with more than 5
-  // strides they collide with the encoder's names (TensorFlow raises on the duplicate variable scope as well)
-  URSN_REQUIRE(c.num_strides >= 1 && c.num_strides <= 5, "num_strides %d out of range [1,5]", c.num_strides);
-  URSN_REQUIRE(c.cin >= 1, "input channels (dims[-1]) must be >= 1, got %d", c.cin);
-  URSN_REQUIRE(c.base_filters >= 1, "base_num_outputs must be >= 1, got %d", c.base_filters);
-  URSN_REQUIRE(c.num_class >= 1 && c.num_class <= 8, "num_class %d out of range [1,8] (the head's 8-channel logits piece)", c.num_class);
-  URSN_REQUIRE(c.max_batch >= 1, "max_batch must be >= 1, got %d", c.max_batch);
+  Topology T;
+  URSN_TRY(topology_build(c, T));
+  static_cast<TopoShape&>(*n) = T;
   const int ns = c.num_strides;
-  n->nlev = ns + 1;
-  for (int l = 0; l <= ns; ++l) {
-    n->lvox[l] = 1;
-    for (int j = 0; j < 3; ++j) {
-      int lead = 3 - c.ndim;
-      if (j < lead) { n->ldim[l][j] = 1; continue; }
-      int s0 = c.spatial[j - lead];
-      URSN_REQUIRE(s0 > 0 && s0 % (1 << ns) == 0, "spatial size %d not divisible by 2^%d (deconv/skip shapes would differ)", s0, ns);
-      n->ldim[l][j] = s0 >> l;
-      n->lvox[l] *= n->ldim[l][j];
-    }
-  }
   const bool tr = c.trainable != 0;
   const int F = c.base_filters;
-  int64_t poff = 0;
-  n->layers.clear(); n->units.clear(); n->deconv.clear(); n->cat.clear(); n->deconv_in.clear(); n->deconv_out.clear();
-  n->ginit.clear(); n->named.clear(); n->named_z.clear(); n->cat_names.clear();
+  n->layers.assign(T.layers.begin(), T.layers.end());
+  n->units.clear(); n->cat.clear(); n->deconv_in.clear(); n->deconv_out.clear();
+  n->ginit.clear(); n->named.clear(); n->named_z.clear();
 
   // concat buffers first (decoder step i lives at level ns-1-i with F*2^(ns-i) channels).  Where a half is narrower
   // than a 64-byte line (<= 8 channels) and the tiled / pointwise kernels take the two halves as separate tensors,
@@ -243,19 +203,17 @@ int plan(ursn_net* n, Arena& A) {
   n->a_data = Act();
   n->a_data.C = c.cin; n->a_data.cs = c.cin; n->a_data.lvl = 0;
 
-  n->conv0 = add_layer(n, A, "conv0", 0, 3, 1, c.cin, F, 0, 0, poff, 1);
+  carve_layer(n, A, n->conv0);
   n->a_conv0 = fmap_view(0);
-  n->named["UResNet/conv0"] = n->a_conv0;
+  n->named[n->layers[n->conv0].name] = n->a_conv0;
 
-  auto add_unit = [&](const std::string& scope, const Act& in, int co, int s, int lout, const Act* out_view,
-                      const Act* in2 = nullptr) {
-    Unit u;
-    u.scope = "UResNet/" + scope;
+  auto add_unit = [&](const TopoUnit& row, const Act& in, const Act* out_view, const Act* in2 = nullptr) {
+    Unit u(row);
+    const int co = u.co, lout = u.lout;
     u.in = in;
     if (in2) u.in2 = *in2;
-    const int cin = in.C + (in2 ? in2->C : 0);
-    if (!(cin == co && s == 1)) u.sc = add_layer(n, A, scope + "/shortcut", 0, 1, s, cin, co, in.lvl, lout, poff);
-    u.c1 = add_layer(n, A, scope + "/resnet_conv1", 0, 3, s, cin, co, in.lvl, lout, poff);
+    if (u.sc >= 0) carve_layer(n, A, u.sc);
+    carve_layer(n, A, u.c1);
     {  // normalise-on-load (URSN_NORM_ON_LOAD=0 turns it off, =2 extends it to 16 channels): resnet_conv1's BatchNorm has no
        // activation, so where conv2 (forward + weight gradient) runs on the tiled kernels they apply it while staging and a1
        // is never written.  Rounds 1-2 measured it neutral (-0.7 ms of bn_act passes, +0.3..0.5 ms in the conv kernels) and
@@ -275,7 +233,7 @@ int plan(ursn_net* n, Arena& A) {
                      !igemm_conv_supported(d2p, PASS_FWD) && (!tr || tiled_wgrad_supported(d2));
     }
     u.a1 = make_act(n, A, lout, co, tr, u.a1_virtual);
-    u.c2 = add_layer(n, A, scope + "/resnet_conv2", 0, 3, 1, co, co, lout, lout, poff);
+    carve_layer(n, A, u.c2);
     u.out = out_view ? *out_view : make_act(n, A, lout, co, tr);
     if (tr && bn_mask_ok(co) && ursn_env_on("URSN_RELU_MASK"))
       u.jmask = (unsigned long long*)A.take(bn_mask_words((int64_t)c.max_batch * n->lvox[lout], co) * sizeof(unsigned long long));
@@ -286,44 +244,27 @@ int plan(ursn_net* n, Arena& A) {
   };
 
   Act net = n->a_conv0;
-  std::vector<std::string> skip_name(ns + 1);   // producer of the encoder feature map at each level
-  skip_name[0] = "UResNet/conv0";
-  for (int step = 0; step < ns; ++step) {
-    char sc[64];
-    int co = net.C * 2;
-    snprintf(sc, sizeof(sc), "resnet_module%d/module1", step);
-    Act u1 = add_unit(sc, net, co, 2, step + 1, nullptr);
-    snprintf(sc, sizeof(sc), "resnet_module%d/module2", step);
-    if (step + 1 < ns) {
-      Act view = fmap_view(step + 1);
-      net = add_unit(sc, u1, co, 1, step + 1, &view);
+  for (const TopoUnit& row : T.units) {
+    if (row.src == TOPO_SRC_CONCAT) {   // decoder step i: the transposed conv, then the unit on [deconv_i | skip]
+      const int i = row.src_step, li = n->deconv[i], co = n->layers[li].cout;
+      carve_layer(n, A, li);
+      n->deconv_in.push_back(net);
+      Act dout = split[i] ? make_act(n, A, row.lin, co, tr) : sub_act(n->cat[i], 0, co);
+      n->deconv_out.push_back(dout);
+      n->named[n->layers[li].name] = dout;
+      net = split[i] ? add_unit(row, dout, nullptr, &lone_fmap[i]) : add_unit(row, n->cat[i], nullptr);
+    } else if (row.skip_of >= 0) {      // the encoder's feature map of this level is written into its concat buffer
+      Act view = fmap_view(row.lout);
+      net = add_unit(row, net, &view);
     } else {
-      net = add_unit(sc, u1, co, 1, step + 1, nullptr);
+      net = add_unit(row, net, nullptr);
     }
-    skip_name[step + 1] = std::string("UResNet/") + sc;
-  }
-  for (int i = 0; i < ns; ++i) {
-    char sc[64];
-    int co = net.C / 2;
-    int lvl = ns - 1 - i;
-    snprintf(sc, sizeof(sc), "deconv%d", i);
-    int li = add_layer(n, A, sc, 1, 3, 2, net.C, co, net.lvl, lvl, poff, 1);
-    n->deconv.push_back(li);
-    n->deconv_in.push_back(net);
-    Act dout = split[i] ? make_act(n, A, lvl, co, tr) : sub_act(n->cat[i], 0, co);
-    n->deconv_out.push_back(dout);
-    n->named[n->layers[li].name] = dout;
-    n->cat_names.push_back({n->layers[li].name, skip_name[lvl]});   // tf.concat([deconv_i, skip]) (lib/uresnet.py:81)
-    snprintf(sc, sizeof(sc), "resnet_module%d/module1", i + 5);
-    Act u1 = split[i] ? add_unit(sc, dout, co, 1, lvl, nullptr, &lone_fmap[i]) : add_unit(sc, n->cat[i], co, 1, lvl, nullptr);
-    snprintf(sc, sizeof(sc), "resnet_module%d/module2", i + 5);
-    net = add_unit(sc, u1, co, 1, lvl, nullptr);
   }
   n->a_pre1 = net;
-  n->conv1 = add_layer(n, A, "conv1", 0, 3, 1, net.C, F, 0, 0, poff, 1);
+  carve_layer(n, A, n->conv1);
   n->a_conv1 = make_act(n, A, 0, F, tr);
-  n->named["UResNet/conv1"] = n->a_conv1;
-  n->conv2 = add_layer(n, A, "conv2", 0, 3, 1, F, c.num_class, 0, 0, poff);
+  n->named[n->layers[n->conv1].name] = n->a_conv1;
+  carve_layer(n, A, n->conv2);
 
   const int64_t V0 = (int64_t)c.max_batch * n->lvox[0];
   n->dlog = tr ? A.floats(V0 * n->layers[n->conv2].zcs) : nullptr;   // channel stride = conv2's padded stride
@@ -394,7 +335,7 @@ int plan(ursn_net* n, Arena& A) {
   n->loss_scratch_bytes = loss_head_scratch_bytes(c.max_batch, n->lvox[0]);   // after everything else: no earlier piece moves
   n->loss_scratch = A.take(n->loss_scratch_bytes);
 
-  n->sizes.n_params = poff;
+  n->sizes.n_params = n->n_params;
   n->sizes.n_layers = (int64_t)n->layers.size();
   n->sizes.n_tensors = 2 * (int64_t)n->layers.size();
   n->sizes.workspace_bytes = (int64_t)((A.off + 255) & ~(size_t)255);
@@ -403,32 +344,25 @@ int plan(ursn_net* n, Arena& A) {
 
 // ---- profiling ------------------------------------------------------------------------------
 extern "C" const char* ursn_last_kernel_name();
-hipEvent_t prof_event(ursn_net* n) {
-  if (n->ev_used == n->ev_pool.size()) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    n->ev_pool.push_back(e);
-  }
-  return n->ev_pool[n->ev_used++];
-}
 struct ProfScope {
   ursn_net* n; hipStream_t s; int idx = -1; bool range = false;
   ProfScope(ursn_net* n_, hipStream_t s_, int layer, int pass, double flops, double bytes) : n(n_), s(s_) {
     if (ursn_roctx_on()) { ursn_roctx_push(n->layers[layer].name.c_str(), pass); range = true; }
-    if (!n->profile || n->prof.size() > 200000) return;
-    ursn_net::ProfRec r{layer, pass, "", flops, bytes, prof_event(n), prof_event(n), ursn_kernel_launch_count(), 1};
+    if (!n->prof.on || n->prof.recs.size() > 200000) return;
+    ProfRec r{layer, pass, "", flops, bytes, n->prof.event(), n->prof.event(), ursn_kernel_launch_count(), 1};
     if (!r.e0 || !r.e1) return;
     hipEventRecord(r.e0, s);
-    n->prof.push_back(r);
-    idx = (int)n->prof.size() - 1;
+    n->prof.recs.push_back(r);
+    idx = (int)n->prof.recs.size() - 1;
   }
   ~ProfScope() { if (range) ursn_roctx_pop(); }
   void done(const char* kernel) {
     if (idx < 0) return;
-    n->prof[idx].kernel = kernel;
-    long nl = ursn_kernel_launch_count() - n->prof[idx].l0;
-    n->prof[idx].launches = nl > 0 ? (int)nl : 1;   // elementwise scopes do not note their kernels: one launch
-    hipEventRecord(n->prof[idx].e1, s);
+    ProfRec& r = n->prof.recs[idx];
+    r.kernel = kernel;
+    long nl = ursn_kernel_launch_count() - r.l0;
+    r.launches = nl > 0 ? (int)nl : 1;   // elementwise scopes do not note their kernels: one launch
+    hipEventRecord(r.e1, s);
   }
 };
 double layer_macs(const ursn_net* n, const Layer& L, int N) {
@@ -641,16 +575,25 @@ int head(ursn_net* n, const float* data, const float* label, const float* weight
   return 0;
 }
 
+// conv2's stored operands (z / mean / rstd / beta) of a batch of N as the voxel-score kernels read them; callers add only
+// data / offsets / index
+ursn_vscores_desc logits_view(const ursn_net* n, int N) {
+  const Layer& L = n->layers[n->conv2];
+  ursn_vscores_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
+  d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
+  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->params + L.b_off;
+  return d;
+}
+
 // The loss head (loss_head.hip) in the place of head(): conv2's stored operands in, n->dlog and the metrics out, and the handle
 // state head() leaves behind (bs_layer / bs_blocks / bs_C) set under head()'s conditions.  Every launch is recorded on its own.
 // Two halves: the call is built and validated before the forward's launches, and run after them.
 int loss_head_net_prepare(ursn_net* n, const float* data, const float* label, const float* weight, int N, const ursn_loss_desc* spec,
                           bool want_grad, LossHeadCall& c) {
   Layer& L = n->layers[n->conv2];
-  memset(&c.d, 0, sizeof(c.d));
-  c.d.n = N; c.d.voxels = n->lvox[0]; c.d.ncls = n->cfg.num_class;
-  c.d.z = L.z; c.d.z_cstride = L.zcs; c.d.dtype = 0;
-  c.d.mean = L.mean; c.d.rstd = L.rstd; c.d.beta = n->params + L.b_off;
+  c.d = logits_view(n, N);
   c.d.data = (n->cfg.cin == 1) ? data : nullptr;   // acc_nonzero needs one input channel, as in head()
   c.label = label; c.weight = weight; c.spec = *spec;
   c.out = want_grad ? n->dlog : nullptr; c.ocs = L.zcs; c.odt = 0;
@@ -669,7 +612,7 @@ int loss_head_net_run(ursn_net* n, const LossHeadCall& c, hipStream_t s) {
     const char* name = "";
     double bytes = 0.0;
     URSN_TRY(loss_head_stage(c, i, s, &name, &bytes));
-    if (ps.idx >= 0) n->prof[ps.idx].bytes = bytes;
+    if (ps.idx >= 0) n->prof.recs[ps.idx].bytes = bytes;
     ps.done(name);
   }
   return 0;
@@ -993,13 +936,10 @@ extern "C" int ursn_query(const ursn_config* cfg, ursn_sizes* out) {
 // the topology recorded by _build against.
 extern "C" int ursn_query_layer(const ursn_config* cfg, int64_t index, ursn_layer_info* out) {
   URSN_REQUIRE(cfg && out, "query_layer: null argument");
-  if (cfg->act_dtype == 1) return bnet_layer(cfg, index, out, nullptr);
-  ursn_net tmp;
-  tmp.cfg = *cfg;
-  Arena A;
-  URSN_TRY(plan(&tmp, A));
-  URSN_REQUIRE(index >= 0 && index < (int64_t)tmp.layers.size(), "query_layer: index %lld out of range", (long long)index);
-  const Layer& L = tmp.layers[index];
+  Topology T;
+  URSN_TRY(topology_build(*cfg, T));
+  URSN_REQUIRE(index >= 0 && index < (int64_t)T.layers.size(), "query_layer: index %lld out of range", (long long)index);
+  const TopoLayer& L = T.layers[index];
   memset(out, 0, sizeof(*out));
   snprintf(out->name, sizeof(out->name), "%s", L.name.c_str());
   out->transposed = L.kind; out->k = L.k; out->stride = L.stride; out->cin = L.cin; out->cout = L.cout; out->relu = L.relu;
@@ -1009,14 +949,13 @@ extern "C" int ursn_query_layer(const ursn_config* cfg, int64_t index, ursn_laye
 
 extern "C" int ursn_query_concat(const ursn_config* cfg, int32_t step, char* first, char* second, size_t cap) {
   URSN_REQUIRE(cfg && first && second && cap > 0, "query_concat: null argument");
-  ursn_net tmp;
-  tmp.cfg = *cfg;
-  tmp.cfg.act_dtype = 0;   // same topology and scope names in both precisions
-  Arena A;
-  URSN_TRY(plan(&tmp, A));
-  URSN_REQUIRE(step >= 0 && step < (int)tmp.cat_names.size(), "query_concat: step %d out of range", step);
-  snprintf(first, cap, "%s", tmp.cat_names[step].first.c_str());
-  snprintf(second, cap, "%s", tmp.cat_names[step].second.c_str());
+  ursn_config c = *cfg;
+  c.act_dtype = 0;   // same topology and scope names in both precisions: the wider domain answers
+  Topology T;
+  URSN_TRY(topology_build(c, T));
+  URSN_REQUIRE(step >= 0 && step < (int)T.cat_names.size(), "query_concat: step %d out of range", step);
+  snprintf(first, cap, "%s", T.cat_names[step].first.c_str());
+  snprintf(second, cap, "%s", T.cat_names[step].second.c_str());
   return 0;
 }
 
@@ -1097,7 +1036,6 @@ extern "C" int ursn_destroy(ursn_net* net) {
   if (net->s2_done) (void)hipEventDestroy(net->s2_done);
   for (hipEvent_t e : net->sync_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : net->fwd_pool) (void)hipEventDestroy(e);
-  for (hipEvent_t e : net->ev_pool) (void)hipEventDestroy(e);
   delete net;
   return 0;
 }
@@ -1110,21 +1048,9 @@ extern "C" int ursn_get_sizes(const ursn_net* net, ursn_sizes* out) {
 
 extern "C" int ursn_param(const ursn_net* net, int64_t index, ursn_param_info* out) {
   URSN_REQUIRE(net && out, "param: null argument");
-  if (net->bf) return bnet_param(net->bf, index, out);
-  URSN_REQUIRE(index >= 0 && index < net->sizes.n_tensors, "param: index %lld out of range", (long long)index);
-  const Layer& L = net->layers[index / 2];
-  memset(out, 0, sizeof(*out));
-  if (index % 2 == 0) {
-    snprintf(out->name, sizeof(out->name), "%s/weights", L.name.c_str());
-    out->offset = L.w_off; out->nelem = L.w_n; out->rank = net->cfg.ndim + 2;
-    for (int j = 0; j < net->cfg.ndim; ++j) out->shape[j] = L.k;
-    out->shape[net->cfg.ndim] = L.kind ? L.cout : L.cin;
-    out->shape[net->cfg.ndim + 1] = L.kind ? L.cin : L.cout;
-  } else {
-    snprintf(out->name, sizeof(out->name), "%s/BatchNorm/beta", L.name.c_str());
-    out->offset = L.b_off; out->nelem = L.cout; out->rank = 1; out->shape[0] = L.cout;
-  }
-  return 0;
+  Topology T;   // the same tensors in both precisions
+  URSN_TRY(topology_build(net->cfg, T));
+  return topology_param(T, index, out);
 }
 
 extern "C" int ursn_zero_grad(ursn_net* net, void* stream) {
@@ -1158,7 +1084,7 @@ extern "C" int ursn_accum_step(ursn_net* net, const float* data, const float* la
   // URSN_GRAPH=1: when the batch holds <= 2^20 voxels, 2: always.  Never while profiling (events per launch).
   static const int gmode = ursn_env_int("URSN_GRAPH", 0);
   // a frozen step neither enters nor replays a graph: a captured graph holds the launches of the mode it was captured in
-  bool geligible = gmode > 0 && !frozen_step && !net->profile && !net->graph_broken && !ursn_roctx_on() &&
+  bool geligible = gmode > 0 && !frozen_step && !net->prof.on && !net->graph_broken && !ursn_roctx_on() &&
                    (gmode > 1 || (int64_t)n * net->lvox[0] <= ((int64_t)1 << 20));
   auto run_on = [&](hipStream_t rs) -> int {
     URSN_TRY(forward(net, data, n, rs));
@@ -1241,12 +1167,14 @@ extern "C" int ursn_apply_adam(ursn_net* net, float lr, void* stream) {
 // ---- guarded optimiser step (opt_guard.hip) ---------------------------------------------------------------------------------
 namespace {
 // (offset, nelem, decay flag = rank > 1) of every trainable tensor in ursn_param order
-int opt_param_table(const ursn_net* net, std::vector<int64_t>& off, std::vector<int64_t>& nel, std::vector<int32_t>& dec) {
-  const int64_t nt = net->sizes.n_tensors;
+int opt_param_table(const ursn_config& cfg, std::vector<int64_t>& off, std::vector<int64_t>& nel, std::vector<int32_t>& dec) {
+  Topology T;
+  URSN_TRY(topology_build(cfg, T));
+  const int64_t nt = 2 * (int64_t)T.layers.size();
   off.resize(nt); nel.resize(nt); dec.resize(nt);
   ursn_param_info info;
   for (int64_t i = 0; i < nt; ++i) {
-    URSN_TRY(ursn_param(net, i, &info));
+    URSN_TRY(topology_param(T, i, &info));
     off[i] = info.offset; nel[i] = info.nelem; dec[i] = info.rank > 1;
   }
   return 0;
@@ -1255,14 +1183,11 @@ int opt_param_table(const ursn_net* net, std::vector<int64_t>& off, std::vector<
 
 extern "C" int ursn_opt_state_bytes(const ursn_config* cfg, int64_t* out) {
   URSN_REQUIRE(cfg && out, "opt_state_bytes: null argument");
-  ursn_net tmp;
-  tmp.cfg = *cfg;
-  tmp.cfg.act_dtype = 0;            // same tensors and element counts in both precisions
-  Arena A;
-  URSN_TRY(plan(&tmp, A));
+  ursn_config c = *cfg;
+  c.act_dtype = 0;                  // same tensors and element counts in both precisions
   std::vector<int64_t> off, nel;
   std::vector<int32_t> dec;
-  URSN_TRY(opt_param_table(&tmp, off, nel, dec));
+  URSN_TRY(opt_param_table(c, off, nel, dec));
   const size_t bytes = ursn_opt_state_size(nel.data(), (int32_t)nel.size());
   URSN_REQUIRE(bytes > 0, "opt_state_bytes: the parameter list is out of the optimiser state's domain");
   *out = (int64_t)bytes;
@@ -1275,7 +1200,7 @@ extern "C" int ursn_opt_attach(ursn_net* net, void* state, size_t bytes) {
   URSN_REQUIRE(net->grads, "opt_attach: net is not trainable");
   std::vector<int64_t> off, nel;
   std::vector<int32_t> dec;
-  URSN_TRY(opt_param_table(net, off, nel, dec));
+  URSN_TRY(opt_param_table(net->cfg, off, nel, dec));
   URSN_TRY(ursn_opt_state_init(state, bytes, off.data(), nel.data(), dec.data(), (int32_t)nel.size()));
   int64_t lay[6];
   URSN_TRY(ursn_opt_state_layout(nel.data(), (int32_t)nel.size(), lay));
@@ -1386,11 +1311,7 @@ extern "C" int ursn_infer_voxels(ursn_net* net, const float* data, const float* 
     URSN_TRY(forward(net, data, n, s));
     if (dense_head) URSN_TRY(head(net, data, label, nullptr, n, nullptr, false, s));
     const Layer& L = net->layers[net->conv2];
-    ursn_vscores_desc d;
-    memset(&d, 0, sizeof(d));
-    d.n = n; d.voxels = net->lvox[0]; d.ncls = net->cfg.num_class;
-    d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
-    d.mean = L.mean; d.rstd = L.rstd; d.beta = net->params + L.b_off;
+    ursn_vscores_desc d = logits_view(net, n);
     d.data = data; d.offsets = offsets; d.index = index;
     if (m_total > 0) {
       ProfScope ps(net, s, net->conv2, 6, 0.0, (double)m_total * (4.0 * L.zcs + 4.0 + 4.0 * d.ncls + 6.0));
@@ -1425,11 +1346,7 @@ extern "C" int ursn_infer_stats(ursn_net* net, const float* data, const float* l
     URSN_TRY(forward(net, data, n, s));
     if (dense_head) URSN_TRY(head(net, data, label, nullptr, n, softmax_out, false, s, labels_out));
     const Layer& L = net->layers[net->conv2];
-    ursn_vscores_desc d;
-    memset(&d, 0, sizeof(d));
-    d.n = n; d.voxels = net->lvox[0]; d.ncls = net->cfg.num_class;
-    d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
-    d.mean = L.mean; d.rstd = L.rstd; d.beta = net->params + L.b_off;
+    ursn_vscores_desc d = logits_view(net, n);
     d.data = net->cfg.cin == 1 ? data : nullptr;
     ProfScope ps(net, s, net->conv2, 6, 0.0, (double)n * net->lvox[0] * (4.0 * L.zcs + 4.0 + (d.data ? 4.0 : 0.0)));
     URSN_TRY(launch_cstats(&d, label, stats, net->cs_scratch, net->cs_scratch_bytes, s));
@@ -1455,11 +1372,7 @@ extern "C" int ursn_forward_logits(ursn_net* net, const float* data, int32_t n, 
   } else {
     URSN_TRY(forward(net, data, n, s));
     const Layer& L = net->layers[net->conv2];
-    ursn_vscores_desc d;
-    memset(&d, 0, sizeof(d));
-    d.n = n; d.voxels = net->lvox[0]; d.ncls = net->cfg.num_class;
-    d.z = L.z; d.z_cstride = L.zcs; d.dtype = 0;
-    d.mean = L.mean; d.rstd = L.rstd; d.beta = net->params + L.b_off;
+    ursn_vscores_desc d = logits_view(net, n);
     ProfScope ps(net, s, net->conv2, 6, 0.0, (double)n * net->lvox[0] * 4.0 * (L.zcs + d.ncls));
     URSN_TRY(launch_logits_dense(&d, logits_out, s));
     ps.done("logits");
@@ -1577,14 +1490,11 @@ extern "C" int ursn_read_loss_terms(ursn_net* net, float* out2, void* stream) {
 // ---- BatchNorm moving statistics (bn_moving.hip) ----------------------------------------------------------------------------
 extern "C" int ursn_bn_moving_size(const ursn_config* cfg, int64_t* out) {
   URSN_REQUIRE(cfg && out, "bn_moving_size: null argument");
-  ursn_sizes sz;
-  URSN_TRY(ursn_query(cfg, &sz));   // the chosen plan's own checks of the configuration
-  ursn_net tmp;
-  tmp.cfg = *cfg;
-  tmp.cfg.act_dtype = 0;            // same layers and widths in both precisions
-  Arena A;
-  URSN_TRY(plan(&tmp, A));
-  *out = tmp.bnm.total;
+  URSN_REQUIRE(cfg->act_dtype == 0 || cfg->act_dtype == 1, "query: act_dtype %d not in {0 fp32, 1 bf16}", cfg->act_dtype);
+  Topology T;
+  URSN_TRY(topology_build(*cfg, T));   // with the chosen plan's own checks of the configuration
+  *out = 0;
+  for (const TopoLayer& L : T.layers) *out += 2 * (int64_t)L.cout;   // [moving_mean[C] | moving_variance[C]] per layer
   return 0;
 }
 
@@ -1652,16 +1562,9 @@ extern "C" int ursn_tensor(const ursn_net* net, const char* name, float** ptr, i
   URSN_REQUIRE(net && name && ptr && voxels && channels && cstride, "tensor: null argument");
   if (net->bf) return bnet_tensor(net->bf, name, (void**)ptr, voxels, channels, cstride);
   std::string s(name);
-  bool want_z = false, want_g = false, want_dz = false, want_mean = false, want_rstd = false;
-  auto strip = [&](const char* suf, bool& f) {
-    size_t L = strlen(suf);
-    if (s.size() > L && s.compare(s.size() - L, L, suf) == 0) { f = true; s = s.substr(0, s.size() - L); }
-  };
-  strip(":dz", want_dz);
-  strip(":z", want_z);
-  strip(":grad", want_g);
-  strip(":mean", want_mean);
-  strip(":rstd", want_rstd);
+  const unsigned kinds = tensor_name_kinds(s, false);   // no second gradient tensors here: ":grad2" stays in the name
+  const bool want_z = kinds & TK_Z, want_g = kinds & TK_GRAD, want_dz = kinds & TK_DZ;
+  const bool want_mean = kinds & TK_MEAN, want_rstd = kinds & TK_RSTD;
   if (want_g && s == "logits") {   // d loss / d logits as the head wrote it (input of conv2's BatchNorm backward)
     URSN_REQUIRE(net->dlog, "tensor: net is not trainable");
     const Layer& L = net->layers[net->conv2];
@@ -1692,32 +1595,15 @@ extern "C" int ursn_tensor(const ursn_net* net, const char* name, float** ptr, i
 // ---- profiling C-ABI --------------------------------------------------------------------------
 extern "C" int ursn_profile_enable(ursn_net* net, int32_t on) {
   URSN_REQUIRE(net, "null handle");
-  if (net->bf) return bnet_profile_enable(net->bf, on);
-  net->profile = on != 0;
-  net->prof.clear();
-  net->ev_used = 0;
+  (net->bf ? *bnet_prof(net->bf) : net->prof).enable(on != 0);
   return 0;
 }
 
 extern "C" int ursn_profile_read(ursn_net* net, ursn_prof_rec* out, int64_t max_recs, int64_t* n_out) {
   URSN_REQUIRE(net && n_out, "null argument");
-  if (net->bf) return bnet_profile_read(net->bf, out, max_recs, n_out);
-  int64_t cnt = 0;
-  for (size_t i = 0; i < net->prof.size() && (!out || cnt < max_recs); ++i) {   // out == NULL: only counts, all of them
-    const ursn_net::ProfRec& r = net->prof[i];
-    float ms = 0.f;
-    if (hipEventSynchronize(r.e1) != hipSuccess || hipEventElapsedTime(&ms, r.e0, r.e1) != hipSuccess) continue;
-    if (out) {
-      ursn_prof_rec& o = out[cnt];
-      memset(&o, 0, sizeof(o));
-      snprintf(o.kernel, sizeof(o.kernel), "%s", r.kernel);
-      snprintf(o.layer, sizeof(o.layer), "%s", net->layers[r.layer].name.c_str());
-      o.pass = r.pass; o.ms = ms; o.flops = r.flops; o.bytes = r.bytes; o.launches = r.launches;
-    }
-    ++cnt;
-  }
-  *n_out = cnt;
-  if (out) { net->prof.clear(); net->ev_used = 0; }
+  Topology T;   // the same layer names in both precisions
+  URSN_TRY(topology_build(net->cfg, T));
+  (net->bf ? *bnet_prof(net->bf) : net->prof).read([&](int li) { return T.layers[li].name.c_str(); }, out, max_recs, n_out);
   return 0;
 }
 

@@ -4,7 +4,6 @@
 
 struct ursn_bnet;
 int bnet_query(const ursn_config* cfg, ursn_sizes* out);
-int bnet_layer(const ursn_config* cfg, int64_t index, ursn_layer_info* out, int* n_layers);
 int bnet_create(const ursn_config* cfg, float* params, float* grads, void* workspace, size_t workspace_bytes, ursn_bnet** out);
 void bnet_destroy(ursn_bnet* n);
 const ursn_sizes* bnet_sizes(const ursn_bnet* n);
@@ -12,7 +11,6 @@ float* bnet_metrics(ursn_bnet* n);
 struct BnmState;
 BnmState* bnet_bnm(ursn_bnet* n);   // BatchNorm moving statistics of the plan (bn_moving.h)
 int bnet_bn_update(ursn_bnet* n, double momentum, hipStream_t s);   // ursn_bn_update's launch, recorded when profiling
-int bnet_param(const ursn_bnet* n, int64_t index, ursn_param_info* out);
 // mode 0: forward + loss + backward (gradients accumulate); 1: forward + loss; 2: forward + softmax / ana labels
 int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, int mode, float* softmax_out,
               float* labels_out, hipStream_t s);
@@ -31,7 +29,7 @@ int bnet_backward_logits(ursn_bnet* n, const float* data, const float* dlogits, 
 int bnet_step_loss(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, const ursn_loss_desc* spec,
                    int mode, hipStream_t s, bool* ran_forward);
 int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxels, int32_t* channels, int32_t* cstride);
-// per-launch HIP-event records (as ursn_profile_enable / ursn_profile_read of the fp32 plan) and the weight-gradient stream switch
-int bnet_profile_enable(ursn_bnet* n, int on);
-int bnet_profile_read(ursn_bnet* n, ursn_prof_rec* out, int64_t max_recs, int64_t* n_out);
+// the plan's per-launch HIP-event log (prof_log.h; ursn_profile_enable / ursn_profile_read) and the weight-gradient stream switch
+struct ProfLog;
+ProfLog* bnet_prof(ursn_bnet* n);
 int bnet_set_wgrad_overlap(ursn_bnet* n, int on);

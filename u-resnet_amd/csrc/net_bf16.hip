@@ -23,6 +23,8 @@
 #include "ext_loss.h"
 #include "loss_head.h"
 #include "bn_moving.h"
+#include "prof_log.h"
+#include "topology.h"
 
 namespace {
 
@@ -36,11 +38,9 @@ struct BAct {              // activation view + its gradient view (same layout)
   const float* in_f32 = nullptr;   // the network input, read as one fp32 channel per voxel by conv0's kernels (set per call)
 };
 
-struct BLayer {
-  std::string name;
-  int kind = 0, k = 3, stride = 1, cin = 0, cout = 0, lin = 0, lout = 0;   // real channel counts (parameter tensor)
+struct BLayer : TopoLayer {   // the topology row (real channel counts: the parameter tensor) + what the bf16 plan adds to it
+  BLayer(const TopoLayer& row) : TopoLayer(row) {}
   int kin = 0, kout = 0;                                                   // channel counts in memory (multiples of 8)
-  int64_t w_off = 0, b_off = 0, w_n = 0;
   ursn_conv_desc desc;                                                     // memory-view channels
   bf16_t *z = nullptr, *dz = nullptr;
   float *mean = nullptr, *rstd = nullptr;
@@ -51,34 +51,28 @@ struct BLayer {
   std::vector<int> vcs;   // input channel strides of the views the layer runs on (compact kin first): the packs are sized over all
 };
 
-struct BUnit {
-  int sc = -1, c1 = -1, c2 = -1;
+struct BUnit : TopoUnit {
+  BUnit(const TopoUnit& row) : TopoUnit(row) {}
   BAct in, a1, out;
   unsigned char* jmask = nullptr;   // relu mask of the join (one byte per 16-byte piece): both BatchNorm-backward passes read it instead of out
 };
 
+// forward() installs the network's packing context: every entry point that runs it holds one of these
+struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } };
+
 }  // namespace
 
-struct BProfRec { int layer, pass; const char* kernel; double flops, bytes; hipEvent_t e0, e1; long l0; int launches; };
-
-struct ursn_bnet {
-  bool profile = false, s2_on = true;
-  std::vector<BProfRec> prof;
-  std::vector<hipEvent_t> pev;
-  size_t pev_used = 0;
+struct ursn_bnet : TopoShape {   // nlev / ldim / lvox / deconv / conv0..2: the table's, assigned by plan()
+  bool s2_on = true;
+  ProfLog prof;   // optional per-launch timing (prof_log.h)
   // BatchNorm-backward reductions taken in the epilogue of the data gradient that completed the layer's output gradient
   double* bs_scratch = nullptr;
   int bs_layer = -1, bs_blocks = 0;
   ursn_config cfg;
   ursn_sizes sizes;
-  int nlev = 0;
-  int ldim[8][3];
-  int64_t lvox[8];
   std::vector<BLayer> layers;
   std::vector<BUnit> units;
-  std::vector<int> deconv;
   std::vector<BAct> deconv_in, deconv_out, cat;
-  int conv0 = -1, conv1 = -1, conv2 = -1;
   BAct a_data, a_conv0, a_conv1, a_pre1;
   // F = 8: conv0's activation lives in its own contiguous tensor; the level-0 concat voxel (16 channels) is written whole
   // when the last transposed conv's BatchNorm runs (its half from z, the skip half recomputed from conv0's z): 16-byte
@@ -136,29 +130,20 @@ BAct sub_act(const BAct& full, int c0, int C) {
 }
 int pad8(int c) { return (c + 7) & ~7; }
 
-int add_layer(ursn_bnet* n, Arena& A, const std::string& name, int kind, int k, int s, int ci, int co, int lin, int lout,
-              int64_t& poff) {
-  BLayer L;
-  L.name = "UResNet/" + name;
-  L.kind = kind; L.k = k; L.stride = s; L.cin = ci; L.cout = co; L.lin = lin; L.lout = lout;
-  L.kin = pad8(ci); L.kout = pad8(co);
-  int64_t taps = 1;
-  for (int j = 0; j < n->cfg.ndim; ++j) taps *= k;
-  L.w_n = taps * ci * co;
-  L.w_off = poff; poff += L.w_n;
-  L.b_off = poff; poff += co;
+// carves the tensors of layer li (its row came from the topology table) and fills its conv descriptor
+void carve_layer(ursn_bnet* n, Arena& A, int li) {
+  BLayer& L = n->layers[li];
+  L.kin = pad8(L.cin); L.kout = pad8(L.cout);
   memset(&L.desc, 0, sizeof(L.desc));
   L.desc.ndim = n->cfg.ndim;
   L.desc.n = n->cfg.max_batch;
-  for (int j = 0; j < n->cfg.ndim; ++j) L.desc.in_sp[j] = n->ldim[lin][3 - n->cfg.ndim + j];
-  L.desc.cin = L.kin; L.desc.cout = L.kout; L.desc.k = k; L.desc.stride = s; L.desc.transposed = kind; L.desc.dtype = 1;
-  const size_t bytes = (size_t)n->cfg.max_batch * n->lvox[lout] * L.kout * sizeof(bf16_t);
+  for (int j = 0; j < n->cfg.ndim; ++j) L.desc.in_sp[j] = n->ldim[L.lin][3 - n->cfg.ndim + j];
+  L.desc.cin = L.kin; L.desc.cout = L.kout; L.desc.k = L.k; L.desc.stride = L.stride; L.desc.transposed = L.kind; L.desc.dtype = 1;
+  const size_t bytes = (size_t)n->cfg.max_batch * n->lvox[L.lout] * L.kout * sizeof(bf16_t);
   L.z = (bf16_t*)A.take(bytes);
   L.dz = n->cfg.trainable ? (bf16_t*)A.take(bytes) : nullptr;
   L.mean = (float*)A.take(L.kout * sizeof(float));
   L.rstd = (float*)A.take(L.kout * sizeof(float));
-  n->layers.push_back(L);
-  return (int)n->layers.size() - 1;
 }
 
 // geometry of one pass of a layer with the weight strides of the STORED (unpadded) parameter tensor
@@ -188,35 +173,20 @@ void real_extents(const BLayer& L, ConvPass pass, int& Kw, int& Nw) {
 
 int plan(ursn_bnet* n, Arena& A) {
   const ursn_config& c = n->cfg;
-  URSN_REQUIRE(c.ndim == 2 || c.ndim == 3, "len(dims) must be 3 (H,W,C) or 4 (H,W,D,C)");
-  URSN_REQUIRE(c.num_strides >= 1 && c.num_strides <= 5, "num_strides %d out of range [1,5]", c.num_strides);
-  URSN_REQUIRE(c.cin == 1, "bf16 path: one input channel (the reference's data), got %d", c.cin);
-  URSN_REQUIRE(c.base_filters >= 8 && c.base_filters % 8 == 0, "bf16 path: base_num_outputs must be a multiple of 8, got %d", c.base_filters);
-  URSN_REQUIRE(c.num_class >= 1 && c.num_class <= 8, "num_class %d out of range [1,8] (the head's 8-channel logits piece)", c.num_class);
-  URSN_REQUIRE(c.max_batch >= 1, "max_batch must be >= 1, got %d", c.max_batch);
+  Topology T;
+  URSN_TRY(topology_build(c, T));   // with this plan's own refusals (one input channel, a base width that is a multiple of 8)
+  static_cast<TopoShape&>(*n) = T;
   const int ns = c.num_strides, F = c.base_filters;
   const bool tr = c.trainable != 0;
-  n->nlev = ns + 1;
-  for (int l = 0; l <= ns; ++l) {
-    n->lvox[l] = 1;
-    for (int j = 0; j < 3; ++j) {
-      const int lead = 3 - c.ndim;
-      if (j < lead) { n->ldim[l][j] = 1; continue; }
-      const int s0 = c.spatial[j - lead];
-      URSN_REQUIRE(s0 > 0 && s0 % (1 << ns) == 0, "spatial size %d not divisible by 2^%d (deconv/skip shapes would differ)", s0, ns);
-      n->ldim[l][j] = s0 >> l;
-      n->lvox[l] *= n->ldim[l][j];
-    }
-  }
-  int64_t poff = 0;
-  n->layers.clear(); n->units.clear(); n->deconv.clear(); n->cat.clear(); n->deconv_in.clear(); n->deconv_out.clear();
+  n->layers.assign(T.layers.begin(), T.layers.end());
+  n->units.clear(); n->cat.clear(); n->deconv_in.clear(); n->deconv_out.clear();
   n->ginit.clear(); n->named.clear();
   n->cat.resize(ns);
   for (int i = 0; i < ns; ++i) n->cat[i] = make_act(n, A, ns - 1 - i, 2 * (F << (ns - 1 - i)), tr);
   auto fmap_view = [&](int lvl) { const BAct& full = n->cat[ns - 1 - lvl]; return sub_act(full, full.C / 2, full.C / 2); };
 
   n->a_data = make_act(n, A, 0, 8, false);
-  n->conv0 = add_layer(n, A, "conv0", 0, 3, 1, c.cin, F, 0, 0, poff);
+  carve_layer(n, A, n->conv0);
   {
     GatherGeom g[8];
     const BLayer& L0 = n->layers[n->conv0];
@@ -245,12 +215,13 @@ int plan(ursn_bnet* n, Arena& A) {
     if (tr && (layer_geoms(n, L, PASS_WGRAD, c.max_batch, L.kin, L.kout, g) != 1 || !b3wgrad_ok(g[0]))) return false;
     return true;
   };
-  auto add_unit = [&](const std::string& scope, const BAct& in, int co, int s, int lout, const BAct* out_view) {
-    BUnit u;
+  auto add_unit = [&](const TopoUnit& row, const BAct& in, const BAct* out_view) {
+    BUnit u(row);
+    const int co = u.co, lout = u.lout;
     u.in = in;
-    if (!(in.C == co && s == 1)) u.sc = add_layer(n, A, scope + "/shortcut", 0, 1, s, in.C, co, in.lvl, lout, poff);
-    u.c1 = add_layer(n, A, scope + "/resnet_conv1", 0, 3, s, in.C, co, in.lvl, lout, poff);
-    u.c2 = add_layer(n, A, scope + "/resnet_conv2", 0, 3, 1, co, co, lout, lout, poff);
+    if (u.sc >= 0) carve_layer(n, A, u.sc);
+    carve_layer(n, A, u.c1);
+    carve_layer(n, A, u.c2);
     const bool virt = virtual_ok(n->layers[u.c2]);   // resnet_conv1's BatchNorm output feeds resnet_conv2 only
     u.a1 = make_act(n, A, lout, co, tr, !virt);
     if (virt) { u.a1.aff_layer = u.c1; u.a1.aff_relu = 0; }
@@ -258,42 +229,35 @@ int plan(ursn_bnet* n, Arena& A) {
     if (tr && ursn_env_on("URSN_BF16_RELU_MASK"))
       u.jmask = (unsigned char*)A.take((size_t)c.max_batch * n->lvox[lout] * (pad8(co) / 8) + 256);
     n->units.push_back(u);
-    n->named["UResNet/" + scope] = u.out;
+    n->named[u.scope] = u.out;
     n->named[n->layers[u.c1].name] = u.a1;
     return u.out;
   };
-  n->named["UResNet/conv0"] = n->a_conv0;
+  n->named[n->layers[n->conv0].name] = n->a_conv0;
   BAct net = n->a_conv0;
-  char sc[64];
-  for (int step = 0; step < ns; ++step) {
-    const int co = net.C * 2;
-    snprintf(sc, sizeof(sc), "resnet_module%d/module1", step);
-    BAct u1 = add_unit(sc, net, co, 2, step + 1, nullptr);
-    snprintf(sc, sizeof(sc), "resnet_module%d/module2", step);
-    if (step + 1 < ns) { BAct view = fmap_view(step + 1); net = add_unit(sc, u1, co, 1, step + 1, &view); }
-    else net = add_unit(sc, u1, co, 1, step + 1, nullptr);
-  }
-  for (int i = 0; i < ns; ++i) {
-    const int co = net.C / 2, lvl = ns - 1 - i;
-    snprintf(sc, sizeof(sc), "deconv%d", i);
-    const int li = add_layer(n, A, sc, 1, 3, 2, net.C, co, net.lvl, lvl, poff);
-    n->deconv.push_back(li);
-    n->deconv_in.push_back(net);
-    n->deconv_out.push_back(sub_act(n->cat[i], 0, co));
-    n->named[n->layers[li].name] = n->deconv_out.back();
-    snprintf(sc, sizeof(sc), "resnet_module%d/module1", i + 5);
-    BAct u1 = add_unit(sc, n->cat[i], co, 1, lvl, nullptr);
-    snprintf(sc, sizeof(sc), "resnet_module%d/module2", i + 5);
-    net = add_unit(sc, u1, co, 1, lvl, nullptr);
+  for (const TopoUnit& row : T.units) {
+    if (row.src == TOPO_SRC_CONCAT) {   // decoder step i: the transposed conv writes the first half of the concat buffer
+      const int i = row.src_step, li = n->deconv[i];
+      carve_layer(n, A, li);
+      n->deconv_in.push_back(net);
+      n->deconv_out.push_back(sub_act(n->cat[i], 0, n->layers[li].cout));
+      n->named[n->layers[li].name] = n->deconv_out.back();
+      net = add_unit(row, n->cat[i], nullptr);
+    } else if (row.skip_of >= 0) {      // the encoder's feature map of this level is the second half of its concat buffer
+      BAct view = fmap_view(row.lout);
+      net = add_unit(row, net, &view);
+    } else {
+      net = add_unit(row, net, nullptr);
+    }
   }
   n->a_pre1 = net;
-  n->conv1 = add_layer(n, A, "conv1", 0, 3, 1, net.C, F, 0, 0, poff);
-  n->conv2 = add_layer(n, A, "conv2", 0, 3, 1, F, c.num_class, 0, 0, poff);
+  carve_layer(n, A, n->conv1);
+  carve_layer(n, A, n->conv2);
   {
     const bool virt = virtual_ok(n->layers[n->conv2]);   // conv1's activation feeds conv2 only (lib/uresnet.py:84-100)
     n->a_conv1 = make_act(n, A, 0, F, tr, !virt);
     if (virt) { n->a_conv1.aff_layer = n->conv1; n->a_conv1.aff_relu = 1; }
-    n->named["UResNet/conv1"] = n->a_conv1;
+    n->named[n->layers[n->conv1].name] = n->a_conv1;
   }
 
   const int64_t V0 = (int64_t)c.max_batch * n->lvox[0];
@@ -400,7 +364,7 @@ int plan(ursn_bnet* n, Arena& A) {
   n->loss_scratch_bytes = loss_head_scratch_bytes(c.max_batch, n->lvox[0]);   // after everything else: no earlier piece moves
   n->loss_scratch = A.take(n->loss_scratch_bytes);
 
-  n->sizes.n_params = poff;
+  n->sizes.n_params = n->n_params;
   n->sizes.n_layers = (int64_t)n->layers.size();
   n->sizes.n_tensors = 2 * (int64_t)n->layers.size();
   n->sizes.workspace_bytes = (int64_t)((A.off + 255) & ~(size_t)255);
@@ -410,30 +374,22 @@ int plan(ursn_bnet* n, Arena& A) {
 // ---- forward -------------------------------------------------------------------------------------------------------------
 // ---- per-launch event records (bench.py --breakdown / --layers, roofline of the dominant kernel) ------------------------
 extern "C" const char* ursn_last_kernel_name();
-hipEvent_t bprof_event(ursn_bnet* n) {
-  if (n->pev_used == n->pev.size()) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    n->pev.push_back(e);
-  }
-  return n->pev[n->pev_used++];
-}
 struct BProf {   // RAII: the conv paths return from several places
   ursn_bnet* n; hipStream_t s; int idx = -1; const char* fixed; bool range = false;
   BProf(ursn_bnet* n_, hipStream_t s_, int layer, int pass, double flops, double bytes, const char* name = nullptr)
       : n(n_), s(s_), fixed(name) {
     if (ursn_roctx_on()) { ursn_roctx_push(n->layers[layer].name.c_str(), pass); range = true; }
-    if (!n->profile || n->prof.size() > 200000) return;
-    BProfRec r{layer, pass, "", flops, bytes, bprof_event(n), bprof_event(n), ursn_kernel_launch_count(), 1};
+    if (!n->prof.on || n->prof.recs.size() > 200000) return;
+    ProfRec r{layer, pass, "", flops, bytes, n->prof.event(), n->prof.event(), ursn_kernel_launch_count(), 1};
     if (!r.e0 || !r.e1) return;
     hipEventRecord(r.e0, s);
-    n->prof.push_back(r);
-    idx = (int)n->prof.size() - 1;
+    n->prof.recs.push_back(r);
+    idx = (int)n->prof.recs.size() - 1;
   }
   ~BProf() {
     if (range) ursn_roctx_pop();
     if (idx < 0) return;
-    BProfRec& r = n->prof[idx];
+    ProfRec& r = n->prof.recs[idx];
     r.kernel = fixed ? fixed : ursn_last_kernel_name();
     const long nl = ursn_kernel_launch_count() - r.l0;
     r.launches = nl > 0 ? (int)nl : 1;
@@ -960,23 +916,6 @@ int bnet_query(const ursn_config* cfg, ursn_sizes* out) {
   return 0;
 }
 
-int bnet_layer(const ursn_config* cfg, int64_t index, ursn_layer_info* out, int* n_layers) {
-  ursn_bnet tmp;
-  tmp.cfg = *cfg;
-  Arena A;
-  URSN_TRY(plan(&tmp, A));
-  if (n_layers) *n_layers = (int)tmp.layers.size();
-  if (!out) return 0;
-  URSN_REQUIRE(index >= 0 && index < (int64_t)tmp.layers.size(), "query_layer: index %lld out of range", (long long)index);
-  const BLayer& L = tmp.layers[index];
-  memset(out, 0, sizeof(*out));
-  snprintf(out->name, sizeof(out->name), "%s", L.name.c_str());
-  out->transposed = L.kind; out->k = L.k; out->stride = L.stride; out->cin = L.cin; out->cout = L.cout;
-  out->relu = (L.kind == 1 || L.name == "UResNet/conv0" || L.name == "UResNet/conv1") ? 1 : 0;
-  out->w_offset = L.w_off; out->beta_offset = L.b_off;
-  return 0;
-}
-
 int bnet_create(const ursn_config* cfg, float* params, float* grads, void* workspace, size_t workspace_bytes, ursn_bnet** out) {
   ursn_bnet* n = new ursn_bnet();
   n->cfg = *cfg;
@@ -1011,35 +950,9 @@ void bnet_destroy(ursn_bnet* n) {
   if (n->s2) { (void)hipStreamSynchronize(n->s2); (void)hipStreamDestroy(n->s2); }
   if (n->s2_done) (void)hipEventDestroy(n->s2_done);
   for (hipEvent_t e : n->evs) (void)hipEventDestroy(e);
-  for (hipEvent_t e : n->pev) (void)hipEventDestroy(e);
   delete n;
 }
 
-int bnet_profile_enable(ursn_bnet* n, int on) {
-  n->profile = on != 0;
-  n->prof.clear();
-  n->pev_used = 0;
-  return 0;
-}
-int bnet_profile_read(ursn_bnet* n, ursn_prof_rec* out, int64_t max_recs, int64_t* n_out) {
-  int64_t cnt = 0;
-  for (size_t i = 0; i < n->prof.size() && (!out || cnt < max_recs); ++i) {   // out == NULL: only counts, all of them
-    const BProfRec& r = n->prof[i];
-    float ms = 0.f;
-    if (hipEventSynchronize(r.e1) != hipSuccess || hipEventElapsedTime(&ms, r.e0, r.e1) != hipSuccess) continue;
-    if (out) {
-      ursn_prof_rec& o = out[cnt];
-      memset(&o, 0, sizeof(o));
-      snprintf(o.kernel, sizeof(o.kernel), "%s", r.kernel);
-      snprintf(o.layer, sizeof(o.layer), "%s", n->layers[r.layer].name.c_str());
-      o.pass = r.pass; o.ms = ms; o.flops = r.flops; o.bytes = r.bytes; o.launches = r.launches;
-    }
-    ++cnt;
-  }
-  *n_out = cnt;
-  if (out) { n->prof.clear(); n->pev_used = 0; }
-  return 0;
-}
 int bnet_set_wgrad_overlap(ursn_bnet* n, int on) {
   if (n->s2) (void)hipStreamSynchronize(n->s2);
   n->s2_on = on != 0;
@@ -1049,32 +962,30 @@ int bnet_set_wgrad_overlap(ursn_bnet* n, int on) {
 const ursn_sizes* bnet_sizes(const ursn_bnet* n) { return &n->sizes; }
 float* bnet_metrics(ursn_bnet* n) { return n->metrics; }
 BnmState* bnet_bnm(ursn_bnet* n) { return &n->bnm; }
+ProfLog* bnet_prof(ursn_bnet* n) { return &n->prof; }
 int bnet_bn_update(ursn_bnet* n, double momentum, hipStream_t s) {
   BProf ps(n, s, n->conv0, 7, 0.0, 4.0 * (3.0 * (double)n->bnm.total), "bn_moving_update");
   return bnm_launch_update(n->bnm, momentum, s);
 }
 
-int bnet_param(const ursn_bnet* n, int64_t index, ursn_param_info* out) {
-  URSN_REQUIRE(index >= 0 && index < n->sizes.n_tensors, "param: index %lld out of range", (long long)index);
-  const BLayer& L = n->layers[index / 2];
-  memset(out, 0, sizeof(*out));
-  if (index % 2 == 0) {
-    snprintf(out->name, sizeof(out->name), "%s/weights", L.name.c_str());
-    out->offset = L.w_off; out->nelem = L.w_n; out->rank = n->cfg.ndim + 2;
-    for (int j = 0; j < n->cfg.ndim; ++j) out->shape[j] = L.k;
-    out->shape[n->cfg.ndim] = L.kind ? L.cout : L.cin;
-    out->shape[n->cfg.ndim + 1] = L.kind ? L.cin : L.cout;
-  } else {
-    snprintf(out->name, sizeof(out->name), "%s/BatchNorm/beta", L.name.c_str());
-    out->offset = L.b_off; out->nelem = L.cout; out->rank = 1; out->shape[0] = L.cout;
-  }
-  return 0;
+namespace {
+// conv2's stored operands (z / mean / rstd, the padded beta) of a batch of N as the voxel-score kernels read them; callers add
+// only data / offsets / index
+ursn_vscores_desc logits_view(const ursn_bnet* n, int N) {
+  const BLayer& L = n->layers[n->conv2];
+  ursn_vscores_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
+  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
+  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  return d;
 }
+}  // namespace
 
 int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, int mode, float* softmax_out,
               float* labels_out, hipStream_t s) {
   // mode 0: accumulate gradients (forward + loss + backward); 1: evaluate (forward + loss); 2: inference
-  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;   // forward() installs the network's packing context
+  PackScope pack_scope;
   URSN_TRY(forward(n, data, N, s));
   const float* w = n->cfg.use_weight ? weight : nullptr;
   if (mode == 0) {
@@ -1089,14 +1000,12 @@ int bnet_step(ursn_bnet* n, const float* data, const float* label, const float* 
 // launch recorded on its own
 int bnet_step_loss(ursn_bnet* n, const float* data, const float* label, const float* weight, int N, const ursn_loss_desc* spec,
                    int mode, hipStream_t s, bool* ran_forward) {
-  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  PackScope pack_scope;
   BLayer& L = n->layers[n->conv2];
   const bool want_grad = mode == 0;
   LossHeadCall c;
-  memset(&c.d, 0, sizeof(c.d));
-  c.d.n = N; c.d.voxels = n->lvox[0]; c.d.ncls = n->cfg.num_class;
-  c.d.z = L.z; c.d.z_cstride = L.kout; c.d.dtype = 1;
-  c.d.mean = L.mean; c.d.rstd = L.rstd; c.d.beta = n->beta_pad; c.d.data = data;
+  c.d = logits_view(n, N);
+  c.d.data = data;
   c.label = label; c.weight = weight; c.spec = *spec;
   c.out = want_grad ? n->dlog : nullptr; c.ocs = 8; c.odt = 1;
   c.out8 = n->metrics; c.scratch = n->loss_scratch; c.nstages = 0;
@@ -1115,7 +1024,7 @@ int bnet_step_loss(ursn_bnet* n, const float* data, const float* label, const fl
     BProf ps(n, s, n->conv2, 6, 0.0, 0.0, "losshead");
     URSN_TRY(loss_head_stage(c, i, s, &name, &bytes));
     ps.fixed = name;
-    if (ps.idx >= 0) n->prof[ps.idx].bytes = bytes;
+    if (ps.idx >= 0) n->prof.recs[ps.idx].bytes = bytes;
   }
   if (want_grad) return backward(n, N, s);
   return 0;
@@ -1125,15 +1034,10 @@ int bnet_step_loss(ursn_bnet* n, const float* data, const float* label, const fl
 // (label != nullptr, no softmax / label volume), then the gather head on conv2's z / mean / rstd and the padded beta
 int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N, const int64_t* offsets, const int32_t* index,
                       int64_t m_total, float* scores_out, uint8_t* pred_out, uint8_t* ana_out, hipStream_t s) {
-  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  PackScope pack_scope;
   URSN_TRY(forward(n, data, N, s));
   if (label) URSN_TRY(head(n, data, label, nullptr, N, nullptr, false, s));
-  const BLayer& L = n->layers[n->conv2];
-  ursn_vscores_desc d;
-  memset(&d, 0, sizeof(d));
-  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
-  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
-  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  ursn_vscores_desc d = logits_view(n, N);
   d.data = data; d.offsets = offsets; d.index = index;
   if (m_total == 0) return 0;
   BProf ps(n, s, n->conv2, 6, 0.0, (double)m_total * (16.0 + 4.0 + 4.0 * d.ncls + 6.0), "vscores");
@@ -1144,15 +1048,10 @@ int bnet_infer_voxels(ursn_bnet* n, const float* data, const float* label, int N
 // class statistics (ana_stats.hip) on conv2's z / mean / rstd and the padded beta
 int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N, bool dense_head, float* labels_out,
                      float* softmax_out, const ursn_class_stats_out* stats, hipStream_t s) {
-  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  PackScope pack_scope;
   URSN_TRY(forward(n, data, N, s));
   if (dense_head) URSN_TRY(head(n, data, label, nullptr, N, softmax_out, false, s, labels_out));
-  const BLayer& L = n->layers[n->conv2];
-  ursn_vscores_desc d;
-  memset(&d, 0, sizeof(d));
-  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
-  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
-  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  ursn_vscores_desc d = logits_view(n, N);
   d.data = data;
   BProf ps(n, s, n->conv2, 6, 0.0, (double)N * n->lvox[0] * (16.0 + 4.0 + 4.0), "cstats");
   return launch_cstats(&d, label, stats, n->cs_scratch, n->cs_scratch_bytes, s);
@@ -1160,14 +1059,9 @@ int bnet_infer_stats(ursn_bnet* n, const float* data, const float* label, int N,
 
 // ursn_forward_logits: the forward of a step, then conv2's z / mean / rstd and the padded beta as dense fp32 logits; no head
 int bnet_forward_logits(ursn_bnet* n, const float* data, int N, float* logits_out, hipStream_t s) {
-  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  PackScope pack_scope;
   URSN_TRY(forward(n, data, N, s));
-  const BLayer& L = n->layers[n->conv2];
-  ursn_vscores_desc d;
-  memset(&d, 0, sizeof(d));
-  d.n = N; d.voxels = n->lvox[0]; d.ncls = n->cfg.num_class;
-  d.z = L.z; d.z_cstride = L.kout; d.dtype = 1;
-  d.mean = L.mean; d.rstd = L.rstd; d.beta = n->beta_pad;
+  ursn_vscores_desc d = logits_view(n, N);
   BProf ps(n, s, n->conv2, 6, 0.0, (double)N * n->lvox[0] * (16.0 + 4.0 * d.ncls), "logits");
   return launch_logits_dense(&d, logits_out, s);
 }
@@ -1175,7 +1069,7 @@ int bnet_forward_logits(ursn_bnet* n, const float* data, int N, float* logits_ou
 // ursn_backward_logits: the caller's d-logits rounded into n->dlog with the partials bhead_kernel would have carried, then the
 // unchanged backward().  The weight packs of the data gradients are those the pending forward's replay filled (same parameters).
 int bnet_backward_logits(ursn_bnet* n, const float* data, const float* dlogits, int N, float* dinput_out, hipStream_t s) {
-  struct PackScope { ~PackScope() { bpack_set_ctx(nullptr); } } pack_scope;
+  PackScope pack_scope;
   static const bool prepack = ursn_env_on("URSN_BF16_PREPACK");
   if (prepack && n->pack.d_jobs && n->pack_N == N) bpack_set_ctx(&n->pack);
   n->a_data.in_f32 = n->scalar_in ? data : nullptr;
@@ -1207,17 +1101,9 @@ int bnet_tensor(const ursn_bnet* n, const char* name, void** ptr, int64_t* voxel
   // output; at F = 8 the level-0 concat gradient lives in two 8-channel tensors: UResNet/deconv<last>:grad and
   // UResNet/conv0:grad2 (the skip's share; UResNet/conv0:grad is the encoder's share)
   std::string s(name);
-  bool want_z = false, want_dz = false, want_g = false, want_g2 = false, want_mean = false, want_rstd = false;
-  auto strip = [&](const char* suf, bool& f) {
-    const size_t L = strlen(suf);
-    if (s.size() > L && s.compare(s.size() - L, L, suf) == 0) { f = true; s = s.substr(0, s.size() - L); }
-  };
-  strip(":dz", want_dz);
-  strip(":z", want_z);
-  strip(":grad2", want_g2);
-  strip(":grad", want_g);
-  strip(":mean", want_mean);
-  strip(":rstd", want_rstd);
+  const unsigned kinds = tensor_name_kinds(s, true);
+  const bool want_z = kinds & TK_Z, want_dz = kinds & TK_DZ, want_g = kinds & TK_GRAD, want_g2 = kinds & TK_GRAD2;
+  const bool want_mean = kinds & TK_MEAN, want_rstd = kinds & TK_RSTD;
   const int ns = n->cfg.num_strides;
   if (want_g && s == "logits") {
     URSN_REQUIRE(n->dlog, "tensor: net is not trainable");
