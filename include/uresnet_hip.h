@@ -947,6 +947,71 @@ typedef struct ursn_cluster_out {       /* DEVICE pointers */
 size_t ursn_cluster_scratch_bytes(int32_t n, int64_t m_total);
 int ursn_cluster_voxels(const ursn_cluster_desc* d, const ursn_cluster_out* out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- per-cluster object records: moments, principal axis, end points (cluster_features.hip) -------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * What a consumer takes from a cluster: its charge, position, direction, extent and its two ends, each a reduction over the
+ * cluster's members.  Input: the lists ursn_cluster_voxels read, the ids and table_offsets it wrote, and optionally the value list.
+ * The members of table row r = table_offsets[e] + id are the entries j of event e with cluster[j] == id; coordinates x[0..2] are the
+ * row-major coordinates of index[j] in `spatial` (2-D: x[2] = 0).  uresnet_amd/clusters.py (cluster_features_numpy) states every
+ * field operation by operation; the device gives the same bits.
+ *
+ * int64 table, URSN_CLFEAT_I columns per row:
+ *   [0] n            members
+ *   [1] charge       sum of rint((double)value * 2^16); a member with |value| >= 2^15 or a non-finite value adds nothing and sets
+ *                    bit 0 of flags; no value list: 0
+ *   [2..4] s         coordinate sums            [5..7] lo, [8..10] hi   bounding box
+ *   [11..13] m       anchor floor((2 s + n) / (2 n)): the centroid rounded to a voxel
+ *   [14..16] d       sum (x - m)                [17..22] dd   sum (x_a - m_a)(x_b - m_b) for ab = 00, 11, 22, 01, 02, 12
+ *   [23] flags       [24] end_lo, [25] end_hi   list positions (global across the batch) of the members with the smallest / largest
+ *                    projection on the axis, the lower position among equals in both
+ * With every extent <= 32768 and m_total < 2^31: |s|, |d| < 2^46, |dd| < 2^61, |charge| <= 2^62.
+ * fp64 table, URSN_CLFEAT_R columns per row (every value one correctly rounded operation after another, never contracted):
+ *   [0..2] centroid  s / n
+ *   [3..8] cov       dd[ab] / n - (d[a] / n) * (d[b] / n), same order as dd; |d / n| <= 0.5 by the anchor, so nothing cancels
+ *   [9..11] eval     eigenvalues of cov, descending: cyclic Jacobi, a fixed 8 sweeps over (0,1), (0,2), (1,2), Rutishauser's rotation
+ *   [12..14] axis    unit eigenvector of eval[0], its component of largest magnitude positive
+ *   [15] length      t_hi - t_lo      [16] t_lo, [17] t_hi   the extreme projections: fp32 values, stored widened
+ * where a member's projection is t = (axis[0] (x0 - m0) + axis[1] (x1 - m1)) + axis[2] (x2 - m2) in fp64, rounded once to fp32.
+ *
+ * Method: per-entry passes accumulate with 64-bit INTEGER atomics (add / min / max, agent scope) and nothing else, so no result
+ * depends on arrival order; the end-point search packs (order-preserving code of the fp32 projection) << 32 | position into one
+ * 64-bit atomic min, and the same code with the complemented position into one atomic max.  Equal-id lanes next to each other in a
+ * wave are combined first, then the runs of a workgroup in an LDS table: one global atomic per field and distinct row of a workgroup
+ * (URSN_CLFEAT_WAVE=0: one per field and entry; same bits).  Per-cluster passes stride up to the count they read from
+ * table_offsets[n].  Seven launches; enqueues only, never synchronises; the scratch needs no
+ * initialisation; every device loop is bounded.  Skipped: entries with cluster == -1 and entries whose row is >= cap.  An entry
+ * with an id whose index lies outside [0, prod(spatial)), whose id lies outside its event's rows, or a row without members sets
+ * *status non-zero (none can come from ursn_cluster_voxels) and is skipped.  Rows at or beyond cap are never written.  Null,
+ * misaligned, out-of-domain and too-small arguments are refused with a message before any launch; m_total = 0 or no clusters
+ * still writes *status. */
+#define URSN_CLFEAT_I 26   /* int64 columns:  208 bytes per row */
+#define URSN_CLFEAT_R 18   /* fp64 columns:   144 bytes per row */
+
+typedef struct ursn_cluster_feat_desc { /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t reserved;                     /* 0 */
+  int64_t m_total;                      /* list entries, < 2^31 */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] */
+  const float* value;                   /* [m_total], or null: charge = 0 */
+  const int32_t* cluster;               /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets;         /* [n+1] as ursn_cluster_voxels wrote it */
+} ursn_cluster_feat_desc;
+
+typedef struct ursn_cluster_feat_out {  /* DEVICE pointers */
+  int64_t* itab;                        /* [cap][URSN_CLFEAT_I] */
+  double* rtab;                         /* [cap][URSN_CLFEAT_R] */
+  int64_t cap;                          /* rows at or beyond cap are never written */
+  int32_t* status;                      /* [1] 0, or non-zero: an entry or a row was inconsistent */
+} ursn_cluster_feat_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535], m_total outside [0, 2^31) or cap < 0.  Host logic only. */
+size_t ursn_cluster_features_scratch_bytes(int32_t n, int64_t m_total, int64_t cap);
+int ursn_cluster_features(const ursn_cluster_feat_desc* d, const ursn_cluster_feat_out* out, void* scratch, size_t scratch_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

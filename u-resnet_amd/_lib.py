@@ -118,6 +118,19 @@ class ursn_cluster_out(C.Structure):
                 ("table_offsets", C.c_void_p), ("cap", C.c_int64), ("status", C.c_void_p)]
 
 
+CLFEAT_I, CLFEAT_R = 26, 18       # URSN_CLFEAT_I / URSN_CLFEAT_R: columns of the int64 / fp64 object tables
+
+
+class ursn_cluster_feat_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("reserved", C.c_int32), ("m_total", C.c_int64),
+                ("offsets", C.c_void_p), ("index", C.c_void_p), ("value", C.c_void_p), ("cluster", C.c_void_p),
+                ("table_offsets", C.c_void_p)]
+
+
+class ursn_cluster_feat_out(C.Structure):
+    _fields_ = [("itab", C.c_void_p), ("rtab", C.c_void_p), ("cap", C.c_int64), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -235,6 +248,8 @@ _SIGS = {
     "ursn_conv_partition": (C.c_int, [C.POINTER(ursn_conv_desc), C.c_int32, C.POINTER(C.c_int64)]),
     "ursn_cluster_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "ursn_cluster_voxels": (C.c_int, [C.POINTER(ursn_cluster_desc), C.POINTER(ursn_cluster_out), _P, C.c_size_t, _P]),
+    "ursn_cluster_features_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "ursn_cluster_features": (C.c_int, [C.POINTER(ursn_cluster_feat_desc), C.POINTER(ursn_cluster_feat_out), _P, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

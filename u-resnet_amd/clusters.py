@@ -95,3 +95,169 @@ def cluster_numpy(index, cls, spatial, spec):
     ids[first] = np.arange(first.size)
     cluster = np.where(root >= 0, ids[np.maximum(root, 0)], -1).astype(np.int32) if m else np.zeros(0, np.int32)
     return cluster, first.astype(np.int32), sizes[first].astype(np.int32), cls[first].astype(np.uint8)
+
+
+# ---- per-cluster object records (csrc/cluster_features.hip does it on the device; this is the statement) --------------------------
+FIX_SHIFT = 16                      # charge is summed in fixed point: rint(value * 2^16) as an integer
+FIX_LIMIT = 2.0 ** 15               # |value| at or beyond it (or not finite): no charge, bit 0 of flags
+MAX_EXTENT = 32768
+JACOBI_SWEEPS = 8
+JACOBI_PAIRS = ((0, 1), (0, 2), (1, 2))
+PAIRS = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))       # the order of dd and cov
+_PAIR_AT = {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (1, 0): 3, (0, 2): 4, (2, 0): 4, (1, 2): 5, (2, 1): 5}
+
+
+def jacobi_eigen3(cov):
+    """Eigenvalues and the leading eigenvector of the symmetric 3 x 3 matrix ``cov`` (six fp64 numbers in the order of PAIRS) by
+    cyclic Jacobi on a FIXED schedule: JACOBI_SWEEPS sweeps over the pairs (0,1), (0,2), (1,2); nothing is tested for convergence.
+    Every line below is one fp64 operation rounded on its own; the device kernel follows it operation for operation.
+
+    The matrix is held as its six elements a[00, 11, 22, 01, 02, 12], the vectors as v[row][column], the identity at the start.
+    One rotation of the pair (p, q), with r the third index, is skipped when a_pq == 0 exactly (either sign of zero); otherwise
+        theta = (a_qq - a_pp) / (2 * a_pq)
+        t     = sign(theta) / (|theta| + sqrt(theta * theta + 1))        sign(theta) = +1 for theta >= 0, else -1
+        c     = 1 / sqrt(t * t + 1)
+        s     = t * c
+        tau   = s / (1 + c)
+        h     = t * a_pq
+    and then, in this order, every right-hand side reading the values from BEFORE the rotation,
+        a_pp = a_pp - h
+        a_qq = a_qq + h
+        a_pq = 0
+        a_rp = a_rp - s * (a_rq + tau * a_rp)
+        a_rq = a_rq + s * (a_rp - tau * a_rq)
+        for k = 0, 1, 2:   v_kp = v_kp - s * (v_kq + tau * v_kp)
+                           v_kq = v_kq + s * (v_kp - tau * v_kq)
+    (a theta too large to square gives t = 0, c = 1, s = 0: the element is dropped and nothing else moves).
+    ``eval`` = the diagonal in descending order, ties keeping the lower column first; ``axis`` = the column of the first, negated as
+    a whole (unary minus) when its component of largest magnitude -- the lowest axis among equals -- is negative."""
+    a = [np.float64(x) for x in cov]
+    one, two, zero = np.float64(1.0), np.float64(2.0), np.float64(0.0)
+    v = [[one if i == k else zero for i in range(3)] for k in range(3)]
+    for p, q in JACOBI_PAIRS * JACOBI_SWEEPS:
+        with np.errstate(over='ignore'):                       # theta may overflow by design: t = 0 then
+            r = 3 - p - q
+            pq, rp, rq = _PAIR_AT[(p, q)], _PAIR_AT[(r, p)], _PAIR_AT[(r, q)]
+            apq = a[pq]
+            if apq == zero:
+                continue
+            theta = (a[q] - a[p]) / (two * apq)
+            root = np.sqrt(theta * theta + one)
+            t = (one if theta >= zero else -one) / (np.abs(theta) + root)
+            c = one / np.sqrt(t * t + one)
+            s = t * c
+            tau = s / (one + c)
+            h = t * apq
+            a[p] = a[p] - h
+            a[q] = a[q] + h
+            a[pq] = zero
+            g, f = a[rp], a[rq]
+            a[rp] = g - s * (f + tau * g)
+            a[rq] = f + s * (g - tau * f)
+            for k in range(3):
+                g, f = v[k][p], v[k][q]
+                v[k][p] = g - s * (f + tau * g)
+                v[k][q] = f + s * (g - tau * f)
+    order = sorted(range(3), key=lambda i: -a[i])              # stable: equal values keep the lower column first
+    ev = np.array([a[i] for i in order], np.float64)
+    ax = [v[k][order[0]] for k in range(3)]
+    big = 0
+    for k in (1, 2):
+        if np.abs(ax[k]) > np.abs(ax[big]):
+            big = k
+    if ax[big] < zero:
+        ax = [-x for x in ax]
+    return ev, np.array(ax, np.float64)
+
+
+def cluster_features_numpy(offsets, index, value, cluster, table_offsets, spatial):
+    """The statement of the per-cluster object records: for every cluster (global row = ``table_offsets[event]`` + event-local id)
+    the reductions over its members, the entries j of that event with ``cluster[j] == id``.  Slow on purpose: Python integers
+    wherever 64 bits could overflow, scalar fp64 operations in one fixed order, one member at a time.
+
+    Coordinates x are those of ``np.unravel_index(index, spatial)``; in 2-D the third coordinate is 0.  Integers, exact:
+    ``n`` members, ``lo`` / ``hi`` [3] bounding box, ``s`` [3] coordinate sums, ``charge`` = sum of rint(float64(value) * 2^16) (a
+    member with |value| >= 2^15 or a value that is not finite adds nothing and sets bit 0 of ``flags``; no values: 0), anchor
+    ``m`` = floor((2 s + n) / (2 n)) (the centroid rounded to a voxel), ``d`` [3] = sum (x - m), ``dd`` [6] = sum (x_a - m_a)(x_b -
+    m_b) over PAIRS.  Bounds, with every extent <= 32768 and fewer than 2^31 entries: |s| < 2^15 * 2^31 = 2^46 and 2 s + n < 2^48;
+    |x - m| < 2^15, so |d| < 2^46 and |dd| < 2^30 * 2^31 = 2^61; |rint(value * 2^16)| <= 2^31, so |charge| <= 2^62: all inside
+    int64.  fp64, one rounded operation each: ``centroid`` = s / n; ``cov[ab]`` = dd[ab] / n - (d[a] / n) * (d[b] / n), where the
+    anchor keeps |d / n| <= 0.5, so nothing cancels; ``eval`` / ``axis`` = ``jacobi_eigen3(cov)``.  Ends: for every member
+    t = (axis[0] * (x_0 - m_0) + axis[1] * (x_1 - m_1)) + axis[2] * (x_2 - m_2) in fp64, rounded once to fp32 (a zero of either
+    sign counts as +0); ``end_lo`` / ``end_hi`` = the list position, global across the batch, of the smallest / largest fp32 t,
+    the LOWER position among equals in both; ``t_lo`` / ``t_hi`` those fp32 values; ``length`` = float64(t_hi) - float64(t_lo).
+
+    Returns a dict of arrays with one row per cluster: int64 ``n, charge, s, lo, hi, m, d, dd, flags, end_lo, end_hi``; float64
+    ``centroid, cov, eval, axis, length``; float32 ``t_lo, t_hi``."""
+    offsets = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    table_offsets = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    index = np.asarray(index, np.int64).reshape(-1)
+    cluster = np.asarray(cluster, np.int64).reshape(-1)
+    spatial = tuple(int(s) for s in spatial)
+    nev, ndim = len(offsets) - 1, len(spatial)
+    if ndim not in (2, 3) or any(not 1 <= s <= MAX_EXTENT for s in spatial):
+        raise ValueError('cluster_features_numpy: spatial = %r, expected 2 or 3 extents in [1, %d]' % (spatial, MAX_EXTENT))
+    if len(table_offsets) != nev + 1 or index.size != cluster.size or (nev >= 0 and offsets[-1] != index.size):
+        raise ValueError('cluster_features_numpy: offsets, table_offsets and the lists disagree')
+    if value is not None:
+        value = np.asarray(value, np.float32).reshape(-1)
+        if value.size != index.size:
+            raise ValueError('cluster_features_numpy: %d values for %d entries' % (value.size, index.size))
+    K = table_offsets[-1]
+    rows = [None] * K
+    for e in range(nev):
+        members = [[] for _ in range(table_offsets[e + 1] - table_offsets[e])]
+        for j in range(offsets[e], offsets[e + 1]):
+            if cluster[j] >= 0:
+                members[int(cluster[j])].append(j)
+        for i, mem in enumerate(members):
+            rows[table_offsets[e] + i] = mem
+    out = {k: np.zeros((K,) + shp, dt) for k, shp, dt in (
+        ('n', (), np.int64), ('charge', (), np.int64), ('s', (3,), np.int64), ('lo', (3,), np.int64), ('hi', (3,), np.int64),
+        ('m', (3,), np.int64), ('d', (3,), np.int64), ('dd', (6,), np.int64), ('flags', (), np.int64), ('end_lo', (), np.int64),
+        ('end_hi', (), np.int64), ('centroid', (3,), np.float64), ('cov', (6,), np.float64), ('eval', (3,), np.float64),
+        ('axis', (3,), np.float64), ('length', (), np.float64), ('t_lo', (), np.float32), ('t_hi', (), np.float32))}
+    for row, mem in enumerate(rows):
+        if not mem:
+            raise ValueError('cluster_features_numpy: cluster row %d has no member' % row)
+        xs = []
+        for j in mem:
+            c = np.unravel_index(int(index[j]), spatial)
+            xs.append(tuple(int(c[a]) if a < ndim else 0 for a in range(3)))
+        n = len(mem)
+        s = [sum(x[a] for x in xs) for a in range(3)]
+        charge, flags = 0, 0
+        if value is not None:
+            for j in mem:
+                val = np.float64(value[j])
+                if not np.isfinite(val) or abs(val) >= FIX_LIMIT:
+                    flags |= 1
+                else:
+                    charge += int(np.rint(val * np.float64(2.0 ** FIX_SHIFT)))
+        m = [(2 * s[a] + n) // (2 * n) for a in range(3)]
+        d = [sum(x[a] - m[a] for x in xs) for a in range(3)]
+        dd = [sum((x[a] - m[a]) * (x[b] - m[b]) for x in xs) for a, b in PAIRS]
+        fn = np.float64(n)
+        mean = [np.float64(d[a]) / fn for a in range(3)]
+        cov = [np.float64(dd[k]) / fn - mean[a] * mean[b] for k, (a, b) in enumerate(PAIRS)]
+        ev, ax = jacobi_eigen3(cov)
+        best_lo = best_hi = None
+        for j, x in zip(mem, xs):
+            t = (ax[0] * np.float64(x[0] - m[0]) + ax[1] * np.float64(x[1] - m[1])) + ax[2] * np.float64(x[2] - m[2])
+            t = np.float32(t)
+            if t == np.float32(0.0):
+                t = np.float32(0.0)
+            if best_lo is None or t < best_lo[0]:            # members come in list order: strict comparisons keep the lower position
+                best_lo = (t, j)
+            if best_hi is None or t > best_hi[0]:
+                best_hi = (t, j)
+        out['n'][row], out['charge'][row], out['flags'][row] = n, charge, flags
+        out['s'][row], out['m'][row], out['d'][row], out['dd'][row] = s, m, d, dd
+        out['lo'][row] = [min(x[a] for x in xs) for a in range(3)]
+        out['hi'][row] = [max(x[a] for x in xs) for a in range(3)]
+        out['centroid'][row] = [np.float64(s[a]) / fn for a in range(3)]
+        out['cov'][row], out['eval'][row], out['axis'][row] = cov, ev, ax
+        out['end_lo'][row], out['end_hi'][row] = best_lo[1], best_hi[1]
+        out['t_lo'][row], out['t_hi'][row] = best_lo[0], best_hi[0]
+        out['length'][row] = np.float64(best_hi[0]) - np.float64(best_lo[0])
+    return out

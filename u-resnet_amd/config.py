@@ -153,6 +153,11 @@ class ssnet_config(object):
     CLUSTER_CONNECTIVITY = 0
     CLUSTER_CLASSES = []
     CLUSTER_MIN_SIZE = 1
+    # ANA_OBJECTS '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per cluster: the object record the device reduces from
+    # the cluster's members (ssnet_base.set_cluster_features; clusters.cluster_features_numpy holds the definition): entry, id,
+    # class, size, charge, centroid, eigenvalues and principal axis of the covariance, length, and the two end points.  '' = off.
+    # Refused without ANA_CLUSTER; ignored with TRAIN, like every ANA_* key
+    ANA_OBJECTS = ''
 
     def __init__(self):
         pass

@@ -195,6 +195,32 @@ def ana_csv_row(entry, stats, i):
     return row + '\n'
 
 
+def objects_csv_header():
+    """The header line of the ANA_OBJECTS file: one row per cluster."""
+    cols = ['entry', 'cluster', 'class', 'size', 'charge']
+    for name in ('centroid', 'eval', 'axis'):
+        cols += ['%s_%d' % (name, a) for a in range(3)]
+    cols.append('length')
+    for name in ('end_lo', 'end_hi'):
+        cols += ['%s_%d' % (name, a) for a in range(3)]
+    return ','.join(cols) + '\n'
+
+
+def objects_csv_row(entry, k, objects, index, start, shape):
+    """Cluster ``k`` of one event's ``objects`` record as a CSV row.  ``index`` is the event's index list, ``start`` the list position
+    of its first entry (``end_lo`` / ``end_hi`` count from the start of the batch), ``shape`` the shape the indices are row-major in.
+    The charge is the fixed-point sum divided by 2^16; floats are written with 17 significant digits and read back to the same bits."""
+    o = objects
+    row = '%d,%d,%d,%d,%.17g' % (entry, k, o['cls'][k], o['size'][k], float(int(o['charge'][k])) / 65536.0)
+    for name in ('centroid', 'eval', 'axis'):
+        row += ''.join(',%.17g' % x for x in o[name][k])
+    row += ',%.17g' % o['length'][k]
+    for name in ('end_lo', 'end_hi'):
+        c = np.unravel_index(int(index[int(o[name][k]) - int(start)]), tuple(int(s) for s in shape))
+        row += ''.join(',%d' % (int(c[a]) if a < len(c) else 0) for a in range(3))
+    return row + '\n'
+
+
 class ssnet_base(object):
 
     def __init__(self, dims, num_class):
@@ -865,6 +891,7 @@ class ssnet_base(object):
         slot.consumed[i] = done                    # the list buffer is free once the expansion has read it
         # inference_voxel_scores reads offsets / index again after the forward pass and moves `consumed` behind its own launch
         self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
+        self._fed_value = base + at['value']       # the same buffer: read by the object-record passes under the same `consumed`
         return fd
 
     def _expand_voxel_list(self, b, with_label, with_weight, symmetry=None):
@@ -1035,6 +1062,9 @@ class ssnet_base(object):
         pending = None
         if spec is not None:                       # behind the gather head, on the list it read
             pending = self._enqueue_clusters(sess, d_offsets, d_index, dev[spec.on], n, M, self._dims[:-1], spec)
+        objects = None
+        if pending is not None and getattr(self, '_cluster_features_on', False):   # behind the cluster passes, same lists
+            objects = self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self._device))
         slot.consumed[turn] = done                 # the gather head has read offsets / index: the list buffer is free again
@@ -1046,6 +1076,8 @@ class ssnet_base(object):
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
         if pending is not None:
             res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
+        if objects is not None:
+            res['objects'] = self._fetch_cluster_features(objects, res['clusters'])
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1161,6 +1193,114 @@ class ssnet_base(object):
         pending = self._enqueue_clusters(sess, d_off, d_index, d_cls, n, M, shape, spec)
         cluster, tables = self._fetch_clusters(pending, off)
         return {'cluster': cluster, 'clusters': tables}
+
+    # ------------------------------------------------------------------------------------------
+    # per-cluster object records (definition and numpy statement: clusters.cluster_features_numpy, device passes:
+    # csrc/cluster_features.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_features(self, on):
+        """While on, and a cluster spec is set, and ``'cluster'`` is wanted, ``inference_voxel_scores`` and
+        ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_features`` behind the cluster passes (tiled: on the stitched list in
+        the large shape), with the batch's own resident value list, and the result gains ``objects``: per event a dict of arrays with
+        one row per cluster (the fields of ``clusters.cluster_features_numpy`` plus ``first`` / ``size`` / ``cls`` of the cluster
+        table).  The legal members of ``want`` do not change; never called, the results have the keys they had."""
+        if type(on) is not bool:
+            raise ValueError('set_cluster_features: on = %r, expected a bool' % (on,))
+        self._cluster_features_on = on
+
+    def _enqueue_cluster_features(self, sess, d_offsets, d_index, d_value, pending, shape):
+        """``ursn_cluster_features`` behind ``_enqueue_clusters`` (its ids and table offsets stay on the device); enqueues only."""
+        import torch
+        lib = _lib.load()
+        ints, _, toff, _, n, M = pending
+        shape = [int(s) for s in shape]
+        cap = M
+        need = int(lib.ursn_cluster_features_scratch_bytes(n, M, cap))
+        if need == 0:
+            raise ValueError('cluster_features: %d events with %d list entries are out of domain' % (n, M))
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=self._device)
+        itab = torch.empty((max(cap, 1), _lib.CLFEAT_I), dtype=torch.int64, device=self._device)
+        rtab = torch.empty((max(cap, 1), _lib.CLFEAT_R), dtype=torch.float64, device=self._device)
+        status = torch.empty(1, dtype=torch.int32, device=self._device)
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_feat_desc()
+        d.ndim, d.n, d.m_total = len(shape), n, M
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.value, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ptr(d_value), ints.data_ptr(), \
+            toff.data_ptr()
+        o = _lib.ursn_cluster_feat_out()
+        o.itab, o.rtab, o.cap, o.status = itab.data_ptr(), rtab.data_ptr(), cap, status.data_ptr()
+        _lib.check(lib.ursn_cluster_features(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, itab, rtab, status):
+            t.record_stream(cur)
+        return itab, rtab, status
+
+    @staticmethod
+    def _fetch_cluster_features(objects, tables):
+        """The two object tables as per-event dicts of named arrays, joined with the cluster table's ``first`` / ``size`` / ``cls``."""
+        itab, rtab, status = objects
+        counts = [int(t['first'].size) for t in tables]
+        total = int(sum(counts))
+        code = int(status.cpu().numpy()[0])
+        if code != 0:
+            raise _lib.UrsnError('cluster_features: the ids, table offsets and lists disagree (status %d)' % code)
+        assert total <= itab.shape[0], 'cluster_features: %d clusters, %d rows' % (total, itab.shape[0])
+        it, rt = itab[:total].cpu().numpy(), rtab[:total].cpu().numpy()
+        res, at = [], 0
+        for t, k in zip(tables, counts):
+            i, r = it[at:at + k], rt[at:at + k]
+            at += k
+            ev = {'n': i[:, 0].copy(), 'charge': i[:, 1].copy(), 's': i[:, 2:5].copy(), 'lo': i[:, 5:8].copy(),
+                  'hi': i[:, 8:11].copy(), 'm': i[:, 11:14].copy(), 'd': i[:, 14:17].copy(), 'dd': i[:, 17:23].copy(),
+                  'flags': i[:, 23].copy(), 'end_lo': i[:, 24].copy(), 'end_hi': i[:, 25].copy(),
+                  'centroid': r[:, 0:3].copy(), 'cov': r[:, 3:9].copy(), 'eval': r[:, 9:12].copy(), 'axis': r[:, 12:15].copy(),
+                  'length': r[:, 15].copy(), 't_lo': r[:, 16].astype(np.float32), 't_hi': r[:, 17].astype(np.float32),
+                  'first': t['first'].copy(), 'size': t['size'].copy(), 'cls': t['cls'].copy()}
+            assert np.array_equal(ev['n'], ev['size']), 'cluster_features: member counts and the cluster table disagree'
+            res.append(ev)
+        return res
+
+    def cluster_features(self, sess, voxels_or_lists, value, clusters, shape=None):
+        """Object records of clusters already made: ``voxels_or_lists`` and ``shape`` as ``cluster_voxels`` took them, ``value`` the
+        entries' values as one flat array or per-event arrays (None: a VoxelBatch's own, or no charge for plain lists), ``clusters``
+        the dict ``cluster_voxels`` returned.  Returns per event a dict of arrays with one row per cluster: the fields of
+        ``clusters.cluster_features_numpy`` (``end_lo`` / ``end_hi`` are positions in the concatenated list) plus ``first`` /
+        ``size`` / ``cls``."""
+        import torch
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_features: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = voxels_or_lists.value
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_features: %d events outside [1, 65535]' % n)
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_features: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids]) if n else np.zeros(0, np.int32)
+        if cluster.size != M or index.size != M or (value is not None and value.size != M):
+            raise ValueError('cluster_features: %d list entries, %d indices, %d ids, %s values'
+                             % (M, index.size, cluster.size, 'no' if value is None else value.size))
+        toff = np.concatenate([[0], np.cumsum([int(t['first'].size) for t in tables])]).astype(np.int64)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        d_off, d_index, d_toff = up(off, np.int64), up(index, np.int32), up(toff, np.int64)
+        d_cluster = up(cluster if M else np.zeros(1, np.int32), np.int32)
+        d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
+        objects = self._enqueue_cluster_features(sess, d_off, d_index, d_value, (d_cluster, None, d_toff, M, n, M), shape)
+        return self._fetch_cluster_features(objects, tables)
 
     # ------------------------------------------------------------------------------------------
     # tiling: volumes larger than the network (not in the reference, whose events have the network's size; boxes, their
@@ -1409,6 +1549,10 @@ class ssnet_base(object):
         pending = None
         if spec is not None:                       # behind the last scatter, on the stitched list in the large shape
             pending = self._enqueue_clusters(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], out[spec.on], n, M, big, spec)
+        objects = None
+        if pending is not None and getattr(self, '_cluster_features_on', False):   # the stitched list, in the large shape
+            objects = self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'],
+                                                     big_batch.ptr['value'], pending, big)
         res = {'index': [big_batch.index[off[i]:off[i + 1]].copy() for i in range(n)]}
         for w in want:
             if w == 'cluster':
@@ -1417,6 +1561,8 @@ class ssnet_base(object):
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
         if pending is not None:
             res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
+        if objects is not None:
+            res['objects'] = self._fetch_cluster_features(objects, res['clusters'])
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

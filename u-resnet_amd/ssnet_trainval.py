@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, objects_csv_header, objects_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -83,6 +83,7 @@ class ssnet_trainval(object):
         self._input_test = None
         self._output = None
         self._csv = None
+        self._objects = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -175,6 +176,8 @@ class ssnet_trainval(object):
                 raise ValueError('ANA_CLUSTER cannot be combined with ANA_TTA in the driver: cluster the averaged result with '
                                  'ssnet_base.cluster_voxels')
             self._cluster_spec = cfg.cluster_spec()
+        if cfg.ANA_OBJECTS and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_OBJECTS needs ANA_CLUSTER: the object records are reductions over the members of the clusters')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -192,6 +195,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._csv.write(ana_csv_header(cfg.NUM_CLASS))
                 self._csv.flush()
+        if cfg.ANA_OBJECTS and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_OBJECTS) or os.path.getsize(cfg.ANA_OBJECTS) == 0
+            self._objects = open(cfg.ANA_OBJECTS, 'a')
+            if fresh:
+                self._objects.write(objects_csv_header())
+                self._objects.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -208,6 +217,8 @@ class ssnet_trainval(object):
         self._skipped_reported = 0
         if self._cluster_spec is not None:   # default off: never called
             self._net.set_clustering(self._cluster_spec)
+            if self._objects:                # default off: never called
+                self._net.set_cluster_features(True)
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -553,6 +564,7 @@ class ssnet_trainval(object):
                 if clustered:
                     np.save(self._output, r['cluster'][i][keep])
             self._output.flush()
+        self._write_objects(r, entries, vb.offsets, self._net._dims[:-1])
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -562,9 +574,20 @@ class ssnet_trainval(object):
             if clustered:
                 for i, ev in enumerate(events):
                     ev['cluster'], ev['clusters'] = r['cluster'][i], r['clusters'][i]
+                    if 'objects' in r:
+                        ev['objects'] = r['objects'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
         self._advance_main()
         return result
+
+    def _write_objects(self, r, entries, off, shape):
+        """ANA_OBJECTS: one CSV row per cluster of every event of the result ``r``."""
+        if not getattr(self, '_objects', None) or 'objects' not in r:
+            return
+        for i, objects in enumerate(r['objects']):
+            for k in range(objects['n'].shape[0]):
+                self._objects.write(objects_csv_row(entries[i], k, objects, r['index'][i], off[i], shape))
+        self._objects.flush()
 
     def _ana_step_tiled(self, vb, entries, batch_mode):
         """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
@@ -589,6 +612,7 @@ class ssnet_trainval(object):
                 if clustered:
                     np.save(self._output, r['cluster'][i][keep])
             self._output.flush()
+        self._write_objects(r, entries, vb.offsets, c.ANA_TILE)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -598,6 +622,8 @@ class ssnet_trainval(object):
             if clustered:
                 for i, ev in enumerate(events):
                     ev['cluster'], ev['clusters'] = r['cluster'][i], r['clusters'][i]
+                    if 'objects' in r:
+                        ev['objects'] = r['objects'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
         self._advance_main()
@@ -766,7 +792,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
