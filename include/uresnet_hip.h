@@ -1012,6 +1012,92 @@ size_t ursn_cluster_features_scratch_bytes(int32_t n, int64_t m_total, int64_t c
 int ursn_cluster_features(const ursn_cluster_feat_desc* d, const ursn_cluster_feat_out* out, void* scratch, size_t scratch_bytes,
                           void* stream);
 
+/* ---- cluster matching: the contingency table of two clusterings of the same lists (cluster_match.hip) ---------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * The step between "objects" and "evaluation": are the predicted clusters the true ones?  Input: two id arrays over the same
+ * concatenated per-event lists, each as ursn_cluster_voxels writes them (event-local id or -1) with its table_offsets, and
+ * optionally the value list.  Side A is "predicted" and side B "true" by convention; the definition is symmetric.
+ * uresnet_amd/clusters.py (cluster_match_numpy) states every field operation by operation; the device gives the same bits.
+ *
+ * A CELL is a pair (A row, B row) of one event with at least one common entry: c = the number of common entries, q = the sum of
+ * rint((double)value * 2^16) over them (the charge rule of the object records: an entry with |value| >= 2^15 or a non-finite
+ * value adds nothing and sets bit 0 of the flags of both its rows; no value list: 0).
+ *
+ * Row record, one per row of each side (X the row's side, Y the other).  int64, URSN_CLMATCH_I columns:
+ *   [0] n         members of the row, whatever their Y id       [1] charge    fixed-point sum over the members
+ *   [2] matched   members whose Y id is >= 0                     [3] partners  cells of the row
+ *   [4] best      event-local Y id of the cell with the largest c, the lowest id among equals; -1 without a cell
+ *   [5] overlap   that cell's c (0 without a cell)               [6] overlap_charge   that cell's q
+ *   [7] flags     bit 0: a charge was dropped; bit 1: mutual (the best row's own best is this row)
+ * fp64, URSN_CLMATCH_R columns, each ONE correctly rounded division of integers converted to fp64:
+ *   [0] purity = overlap / n      [1] efficiency = overlap / n_Y(best)      [2] iou = overlap / (n + n_Y(best) - overlap)
+ *   [3] matched / n               ([1] and [2] are 0.0 without a cell)
+ * Event record, one per event.  int64, URSN_CLMATCH_EI columns:
+ *   [0] N = entries with both ids >= 0      [1] S = sum over cells of c (c - 1) / 2
+ *   [2] SA = sum over A rows of matched (matched - 1) / 2      [3] SB = the same over B rows
+ *   [4] cells   [5] KA   [6] KB   [7] mutual pairs
+ *   [8] sum over A rows of overlap   [9] sum over A rows of n   [10], [11] the same over B rows
+ * (with m_total < 2^31 every one of them is below 2^62).  fp64, URSN_CLMATCH_ER columns:
+ *   [0] adjusted Rand index: P = N (N - 1) / 2; 1.0 if P == 0; E = (f(SA) * f(SB)) / f(P); mean = (f(SA) + f(SB)) * 0.5;
+ *       den = mean - E; 1.0 if den == 0; else (f(S) - E) / den   (f = int64 -> fp64; one rounded operation each, never contracted)
+ *   [1] [8] / [9], 0.0 when [9] == 0      [2] [10] / [11], 0.0 when [11] == 0      [3] f(2 mutual) / f(KA + KB), 0.0 without rows
+ * Cell list (optional), CSR by global A row: pair_offsets[r] .. pair_offsets[r + 1] are the cells of A row r in ascending B id;
+ * pair_b = event-local B id, pair_n = c, pair_q = q.
+ *
+ * Method: every entry's (A row, B row) pair -- a missing side counts as a row of its own kind -- is counted in an open-addressing
+ * table in the scratch (64-bit keys claimed by compare-and-swap, count and charge by 64-bit INTEGER atomic adds, agent scope); a pass
+ * over the slots spreads each cell onto its two rows (integer adds, and ONE packed 64-bit atomic max per side for `best`:
+ * c << 32 | 0xFFFFFFFF - other row, so equal counts fall to the lower id); one thread per row writes the records; the event sums
+ * are integer adds; the cell list is an exclusive scan of `partners`, a drop into the row's segment at an atomic cursor and a rank
+ * by B id inside the segment.  Which slot a cell lands in depends on arrival order; nothing that is output does.  No float atomics.
+ * Equal-pair lanes next to each other in a wave are combined first, then the runs of a workgroup in an LDS table: one insertion per
+ * distinct pair of a workgroup (URSN_CLMATCH_WAVE=0: one insertion per entry; same bits).  Every device loop is bounded (a probe
+ * walk by the slot count, an event search by 17 halvings, a rank by `partners`).  Enqueues only, never synchronises; the scratch needs
+ * no initialisation; the same arguments give the same bits.
+ * *status is 0, or non-zero when an id lies outside [-1, K_e) of its event, a row has no member, the offsets are not those of the
+ * lists, or a bounded loop ran out (none can come from ursn_cluster_voxels); such an entry or row is skipped.  Rows at or beyond
+ * cap_a / cap_b and cells at or beyond pair_cap are never written; every row and cell below them is complete whatever the caps
+ * are, and pair_offsets holds the true counts.  m_total = 0 or no rows still writes *status, the event records and pair_offsets[0].
+ * Null, misaligned, out-of-domain and too-small arguments are refused with a message before any launch. */
+#define URSN_CLMATCH_I 8    /* int64 columns of a row record */
+#define URSN_CLMATCH_R 4    /* fp64 columns of a row record */
+#define URSN_CLMATCH_EI 12  /* int64 columns of an event record */
+#define URSN_CLMATCH_ER 4   /* fp64 columns of an event record */
+
+typedef struct ursn_cluster_match_desc { /* every pointer is a DEVICE pointer */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t reserved;                     /* 0 */
+  int64_t m_total;                      /* list entries, < 2^31 */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* cluster_a;             /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets_a;       /* [n+1] */
+  const int32_t* cluster_b;             /* [m_total] */
+  const int64_t* table_offsets_b;       /* [n+1] */
+  const float* value;                   /* [m_total], or null: every charge is 0 */
+} ursn_cluster_match_desc;
+
+typedef struct ursn_cluster_match_out { /* DEVICE pointers */
+  int64_t* a_int;                       /* [cap_a][URSN_CLMATCH_I] */
+  double* a_real;                       /* [cap_a][URSN_CLMATCH_R] */
+  int64_t cap_a;                        /* A rows at or beyond it are never written */
+  int64_t* b_int;                       /* [cap_b][URSN_CLMATCH_I] */
+  double* b_real;                       /* [cap_b][URSN_CLMATCH_R] */
+  int64_t cap_b;
+  int64_t* event_int;                   /* [n][URSN_CLMATCH_EI] */
+  double* event_real;                   /* [n][URSN_CLMATCH_ER] */
+  int64_t* pair_offsets;                /* [cap_a + 1], or null: no cell list; entries 0 .. min(KA_total, cap_a) are written */
+  int32_t* pair_b;                      /* [pair_cap] each, or all three null: the counts in pair_offsets only */
+  int64_t* pair_n;
+  int64_t* pair_q;
+  int64_t pair_cap;                     /* cells at or beyond it are never written */
+  int32_t* status;                      /* [1] */
+} ursn_cluster_match_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535], m_total outside [0, 2^31) or a cap < 0.  Host logic only. */
+size_t ursn_cluster_match_scratch_bytes(int32_t n, int64_t m_total, int64_t cap_a, int64_t cap_b, int64_t pair_cap);
+int ursn_cluster_match(const ursn_cluster_match_desc* d, const ursn_cluster_match_out* out, void* scratch, size_t scratch_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

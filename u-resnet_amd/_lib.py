@@ -131,6 +131,22 @@ class ursn_cluster_feat_out(C.Structure):
     _fields_ = [("itab", C.c_void_p), ("rtab", C.c_void_p), ("cap", C.c_int64), ("status", C.c_void_p)]
 
 
+CLMATCH_I, CLMATCH_R, CLMATCH_EI, CLMATCH_ER = 8, 4, 12, 4   # URSN_CLMATCH_*: columns of the row / event records of a match
+
+
+class ursn_cluster_match_desc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("m_total", C.c_int64), ("offsets", C.c_void_p),
+                ("cluster_a", C.c_void_p), ("table_offsets_a", C.c_void_p), ("cluster_b", C.c_void_p),
+                ("table_offsets_b", C.c_void_p), ("value", C.c_void_p)]
+
+
+class ursn_cluster_match_out(C.Structure):
+    _fields_ = [("a_int", C.c_void_p), ("a_real", C.c_void_p), ("cap_a", C.c_int64), ("b_int", C.c_void_p), ("b_real", C.c_void_p),
+                ("cap_b", C.c_int64), ("event_int", C.c_void_p), ("event_real", C.c_void_p), ("pair_offsets", C.c_void_p),
+                ("pair_b", C.c_void_p), ("pair_n", C.c_void_p), ("pair_q", C.c_void_p), ("pair_cap", C.c_int64),
+                ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -250,6 +266,8 @@ _SIGS = {
     "ursn_cluster_voxels": (C.c_int, [C.POINTER(ursn_cluster_desc), C.POINTER(ursn_cluster_out), _P, C.c_size_t, _P]),
     "ursn_cluster_features_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
     "ursn_cluster_features": (C.c_int, [C.POINTER(ursn_cluster_feat_desc), C.POINTER(ursn_cluster_feat_out), _P, C.c_size_t, _P]),
+    "ursn_cluster_match_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "ursn_cluster_match": (C.c_int, [C.POINTER(ursn_cluster_match_desc), C.POINTER(ursn_cluster_match_out), _P, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

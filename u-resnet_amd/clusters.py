@@ -261,3 +261,151 @@ def cluster_features_numpy(offsets, index, value, cluster, table_offsets, spatia
         out['t_lo'][row], out['t_hi'][row] = best_lo[0], best_hi[0]
         out['length'][row] = np.float64(best_hi[0]) - np.float64(best_lo[0])
     return out
+
+
+# ---- cluster matching (csrc/cluster_match.hip does it on the device; this is the statement) ---------------------------------------
+MATCH_ROW_INT = ('n', 'charge', 'matched', 'partners', 'best', 'overlap', 'overlap_charge', 'flags')
+MATCH_ROW_REAL = ('purity', 'efficiency', 'iou', 'matched_fraction')
+MATCH_EVENT_INT = ('n_both', 'pairs', 'pairs_a', 'pairs_b', 'cells', 'rows_a', 'rows_b', 'mutual', 'overlap_a', 'members_a',
+                   'overlap_b', 'members_b')
+MATCH_EVENT_REAL = ('ari', 'purity', 'efficiency', 'mutual_fraction')
+
+
+def cluster_match_numpy(offsets, cluster_a, table_offsets_a, cluster_b, table_offsets_b, value=None):
+    """The statement of the match of two clusterings of the same concatenated per-event lists: ``cluster_a`` / ``cluster_b`` hold
+    event-local ids or -1 as ``ursn_cluster_voxels`` writes them, each with its ``table_offsets`` [n+1] (global row =
+    ``table_offsets[event]`` + id).  A is "predicted" and B "true" by convention; the definition is symmetric.  Slow on purpose:
+    Python integers wherever 64 bits could overflow, scalar fp64 operations in one fixed order, one entry at a time.
+
+    A CELL is a pair (A row, B row) of one event with at least one common entry: ``c`` = the number of common entries, ``q`` = the
+    sum of rint(float64(value) * 2^16) over them (an entry with |value| >= 2^15 or a value that is not finite adds nothing and sets
+    bit 0 of the flags of BOTH its rows; no values: 0).
+
+    Row record of a row of side X (Y the other side), MATCH_ROW_INT: ``n`` members whatever their Y id, ``charge`` the fixed-point
+    sum over them, ``matched`` members whose Y id is >= 0, ``partners`` cells of the row, ``best`` the event-local Y id of the cell
+    with the largest c (the lowest id among equals; -1 without a cell), ``overlap`` / ``overlap_charge`` that cell's c / q (0
+    without one), ``flags`` bit 0 = a charge was dropped, bit 1 = mutual (the best row's own best is this row).  MATCH_ROW_REAL,
+    each ONE division of integers converted to fp64: ``purity`` = overlap / n, ``efficiency`` = overlap / n_Y(best), ``iou`` =
+    overlap / (n + n_Y(best) - overlap), ``matched_fraction`` = matched / n (efficiency and iou are 0.0 without a cell).
+
+    Event record, MATCH_EVENT_INT: [0] N = entries with both ids >= 0, [1] S = sum over cells of c (c - 1) / 2, [2] SA = sum over A
+    rows of matched (matched - 1) / 2, [3] SB the same over B rows, [4] cells, [5] KA, [6] KB, [7] mutual pairs, [8] / [9] sums over
+    A rows of overlap / n, [10] / [11] the same over B rows.  Bounds with fewer than 2^31 entries: N, KA, KB, cells, mutual and the
+    sums of overlap and n are below 2^31; S, SA, SB <= N (N - 1) / 2 < 2^61; |charge|, |q| <= 2^31 * 2^31 = 2^62 in a row record
+    and every event integer is below 2^62: all inside int64.  MATCH_EVENT_REAL: [0] the adjusted Rand index, in this order: P =
+    N (N - 1) / 2 as an integer, 1.0 if P == 0; E = (f(SA) * f(SB)) / f(P); mean = (f(SA) + f(SB)) * 0.5; den = mean - E, 1.0 if
+    den == 0; else (f(S) - E) / den, with f the int64 -> fp64 conversion and every operation rounded on its own; [1] = [8] / [9]
+    (0.0 when [9] == 0), [2] = [10] / [11] (0.0 when [11] == 0), [3] = f(2 mutual) / f(KA + KB) (0.0 without rows).
+
+    Cell list, CSR by global A row: ``pair_offsets`` [KA_total + 1], ``pair_b`` (event-local B id, ascending inside a row),
+    ``pair_n``, ``pair_q``.  An id outside [-1, K_e) of its event and a row without a member raise ValueError.
+
+    Returns a dict: ``a_int`` / ``b_int`` int64 [K, 8], ``a_real`` / ``b_real`` float64 [K, 4], ``event_int`` int64 [n, 12],
+    ``event_real`` float64 [n, 4], ``pair_offsets`` int64, ``pair_b`` int32, ``pair_n`` / ``pair_q`` int64."""
+    offsets = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [[int(x) for x in np.asarray(t).reshape(-1)] for t in (table_offsets_a, table_offsets_b)]
+    ids = [np.asarray(c, np.int64).reshape(-1) for c in (cluster_a, cluster_b)]
+    nev = len(offsets) - 1
+    if nev < 1 or any(len(t) != nev + 1 for t in toff) or ids[0].size != ids[1].size or offsets[0] != 0 or offsets[-1] != ids[0].size \
+            or any(t[0] != 0 or any(t[e + 1] < t[e] for e in range(nev)) for t in toff) \
+            or any(offsets[e + 1] < offsets[e] for e in range(nev)):
+        raise ValueError('cluster_match_numpy: offsets, table offsets and the id lists disagree')
+    if value is not None:
+        value = np.asarray(value, np.float32).reshape(-1)
+        if value.size != ids[0].size:
+            raise ValueError('cluster_match_numpy: %d values for %d entries' % (value.size, ids[0].size))
+    K = [t[-1] for t in toff]
+    rows = [[{'n': 0, 'charge': 0, 'matched': 0, 'flags': 0, 'cells': {}} for _ in range(K[x])] for x in (0, 1)]
+    for e in range(nev):
+        for j in range(offsets[e], offsets[e + 1]):
+            local = [int(ids[x][j]) for x in (0, 1)]
+            for x in (0, 1):
+                if not -1 <= local[x] < toff[x][e + 1] - toff[x][e]:
+                    raise ValueError('cluster_match_numpy: entry %d has id %d outside [-1, %d)' % (j, local[x], toff[x][e + 1] - toff[x][e]))
+            q, dropped = 0, False
+            if value is not None:
+                val = np.float64(value[j])
+                if not np.isfinite(val) or abs(val) >= FIX_LIMIT:
+                    dropped = True
+                else:
+                    q = int(np.rint(val * np.float64(2.0 ** FIX_SHIFT)))
+            for x in (0, 1):
+                if local[x] < 0:
+                    continue
+                row = rows[x][toff[x][e] + local[x]]
+                row['n'] += 1
+                row['charge'] += q
+                if dropped:
+                    row['flags'] |= 1
+                if local[1 - x] >= 0:
+                    row['matched'] += 1
+                    cell = row['cells'].setdefault(local[1 - x], [0, 0])
+                    cell[0] += 1
+                    cell[1] += q
+    event_of = [[e for e in range(nev) for _ in range(toff[x][e + 1] - toff[x][e])] for x in (0, 1)]
+    for x in (0, 1):
+        for r, row in enumerate(rows[x]):
+            if row['n'] == 0:
+                raise ValueError('cluster_match_numpy: row %d of side %s has no member' % (r, 'AB'[x]))
+            row['best'], row['overlap'], row['overlap_charge'] = -1, 0, 0
+            for other in sorted(row['cells']):                  # ascending id: a strict comparison keeps the lowest among equals
+                if row['cells'][other][0] > row['overlap']:
+                    row['best'], (row['overlap'], row['overlap_charge']) = other, row['cells'][other]
+    out = {'a_int': np.zeros((K[0], 8), np.int64), 'b_int': np.zeros((K[1], 8), np.int64),
+           'a_real': np.zeros((K[0], 4), np.float64), 'b_real': np.zeros((K[1], 4), np.float64),
+           'event_int': np.zeros((nev, 12), np.int64), 'event_real': np.zeros((nev, 4), np.float64)}
+    ev = [[0] * 12 for _ in range(nev)]
+    zero = np.float64(0.0)
+    for x in (0, 1):
+        for r, row in enumerate(rows[x]):
+            e = event_of[x][r]
+            n, matched, overlap = row['n'], row['matched'], row['overlap']
+            n_other, mutual = 0, False
+            if row['best'] >= 0:
+                other = rows[1 - x][toff[1 - x][e] + row['best']]
+                n_other = other['n']
+                mutual = other['best'] == r - toff[x][e]
+            flags = row['flags'] | (2 if mutual else 0)
+            out['ab'[x] + '_int'][r] = [n, row['charge'], matched, len(row['cells']), row['best'], overlap, row['overlap_charge'], flags]
+            fn = np.float64(n)
+            out['ab'[x] + '_real'][r] = [np.float64(overlap) / fn,
+                                         np.float64(overlap) / np.float64(n_other) if row['best'] >= 0 else zero,
+                                         np.float64(overlap) / np.float64(n + n_other - overlap) if row['best'] >= 0 else zero,
+                                         np.float64(matched) / fn]
+            if x == 0:
+                ev[e][0] += matched
+                ev[e][1] += sum(c * (c - 1) // 2 for c, _ in row['cells'].values())
+                ev[e][2] += matched * (matched - 1) // 2
+                ev[e][4] += len(row['cells'])
+                ev[e][7] += 1 if mutual else 0
+                ev[e][8] += overlap
+                ev[e][9] += n
+            else:
+                ev[e][3] += matched * (matched - 1) // 2
+                ev[e][10] += overlap
+                ev[e][11] += n
+    half = np.float64(0.5)
+    for e in range(nev):
+        ev[e][5], ev[e][6] = toff[0][e + 1] - toff[0][e], toff[1][e + 1] - toff[1][e]
+        assert all(0 <= v < 2 ** 62 for v in ev[e])
+        N, S, SA, SB = ev[e][:4]
+        P = N * (N - 1) // 2
+        ari = np.float64(1.0)
+        if P != 0:
+            E = (np.float64(SA) * np.float64(SB)) / np.float64(P)
+            mean = (np.float64(SA) + np.float64(SB)) * half
+            den = mean - E
+            if den != zero:
+                ari = (np.float64(S) - E) / den
+        out['event_int'][e] = ev[e]
+        out['event_real'][e] = [ari, np.float64(ev[e][8]) / np.float64(ev[e][9]) if ev[e][9] else zero,
+                                np.float64(ev[e][10]) / np.float64(ev[e][11]) if ev[e][11] else zero,
+                                np.float64(2 * ev[e][7]) / np.float64(ev[e][5] + ev[e][6]) if ev[e][5] + ev[e][6] else zero]
+    pair_offsets, pb, pn, pq = [0], [], [], []
+    for row in rows[0]:
+        for other in sorted(row['cells']):
+            pb.append(other), pn.append(row['cells'][other][0]), pq.append(row['cells'][other][1])
+        pair_offsets.append(len(pb))
+    out['pair_offsets'] = np.array(pair_offsets, np.int64)
+    out['pair_b'], out['pair_n'], out['pair_q'] = np.array(pb, np.int32), np.array(pn, np.int64), np.array(pq, np.int64)
+    return out

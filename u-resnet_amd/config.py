@@ -158,6 +158,12 @@ class ssnet_config(object):
     # class, size, charge, centroid, eigenvalues and principal axis of the covariance, length, and the two end points.  '' = off.
     # Refused without ANA_CLUSTER; ignored with TRAIN, like every ANA_* key
     ANA_OBJECTS = ''
+    # ANA_MATCH '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per event: the match of the predicted clusters with the
+    # clusters of the TRUE classes under the same CLUSTER_* keys (ssnet_base.set_cluster_matching; clusters.cluster_match_numpy holds
+    # the definition): entry, the twelve event integers (matched entries, pair counts, cells, rows, mutual pairs, overlaps) and the
+    # four event reals (adjusted Rand index, purity, efficiency, mutual fraction).  '' = off.  Refused without ANA_CLUSTER; ignored
+    # with TRAIN, like every ANA_* key
+    ANA_MATCH = ''
 
     def __init__(self):
         pass

@@ -206,6 +206,20 @@ def objects_csv_header():
     return ','.join(cols) + '\n'
 
 
+def match_csv_header():
+    """The header line of the ANA_MATCH file: one row per event."""
+    from .clusters import MATCH_EVENT_INT, MATCH_EVENT_REAL
+    return ','.join(('entry',) + MATCH_EVENT_INT + MATCH_EVENT_REAL) + '\n'
+
+
+def match_csv_row(entry, events, i):
+    """Event ``i`` of a match's ``events`` record as a CSV row: the twelve integers, then the four reals by ``repr`` (which reads
+    back to the same bits)."""
+    from .clusters import MATCH_EVENT_INT, MATCH_EVENT_REAL
+    return ','.join(['%d' % entry] + ['%d' % int(events[name][i]) for name in MATCH_EVENT_INT] +
+                    [repr(float(events[name][i])) for name in MATCH_EVENT_REAL]) + '\n'
+
+
 def objects_csv_row(entry, k, objects, index, start, shape):
     """Cluster ``k`` of one event's ``objects`` record as a CSV row.  ``index`` is the event's index list, ``start`` the list position
     of its first entry (``end_lo`` / ``end_hi`` count from the start of the batch), ``shape`` the shape the indices are row-major in.
@@ -892,6 +906,7 @@ class ssnet_base(object):
         # inference_voxel_scores reads offsets / index again after the forward pass and moves `consumed` behind its own launch
         self._fed_list = (slot, i, base + at['offsets'], base + at['index'])
         self._fed_value = base + at['value']       # the same buffer: read by the object-record passes under the same `consumed`
+        self._fed_label = (dst, at['label'], vb.label.nbytes) if with_label else None    # ... and where the label list lies in it
         return fd
 
     def _expand_voxel_list(self, b, with_label, with_weight, symmetry=None):
@@ -1042,6 +1057,9 @@ class ssnet_base(object):
             raise ValueError("inference_voxel_scores: want = %r, expected a non-empty subset of %r" % (want, self._want_names()))
         if 'ana' in want and self._num_class < 3:
             raise ValueError('inference_voxel_scores: the ana label needs >= 3 classes (num_class = %d)' % self._num_class)
+        matching = spec is not None and getattr(self, '_cluster_matching_on', False)
+        if matching and (not with_labels or voxels.label is None):
+            raise ValueError('inference_voxel_scores: cluster matching is on and the batch has no labels to cluster')
         fd = self._feed_voxels(voxels, with_label=with_labels, with_weight=False)
         n = int(fd['input_data'].shape[0])
         self._ensure_handle(n)
@@ -1065,6 +1083,12 @@ class ssnet_base(object):
         objects = None
         if pending is not None and getattr(self, '_cluster_features_on', False):   # behind the cluster passes, same lists
             objects = self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+        truth = match = None
+        if matching:                               # the TRUE classes under the same spec, then the match of the two id arrays
+            buf, at, nbytes = self._fed_label
+            truth = self._enqueue_clusters(sess, d_offsets, d_index, self._label_classes(buf[at:at + nbytes].view(torch.float32), M),
+                                           n, M, self._dims[:-1], spec)
+            match = self._enqueue_cluster_match(sess, d_offsets, pending, truth, self._fed_value, n, M, False)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self._device))
         slot.consumed[turn] = done                 # the gather head has read offsets / index: the list buffer is free again
@@ -1078,6 +1102,9 @@ class ssnet_base(object):
             res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
         if objects is not None:
             res['objects'] = self._fetch_cluster_features(objects, res['clusters'])
+        if match is not None:
+            res['true_cluster'], res['true_clusters'] = self._fetch_clusters(truth, off)
+            res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1303,6 +1330,150 @@ class ssnet_base(object):
         return self._fetch_cluster_features(objects, tables)
 
     # ------------------------------------------------------------------------------------------
+    # cluster matching (definition and numpy statement: clusters.cluster_match_numpy, device passes: csrc/cluster_match.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_matching(self, on):
+        """While on, and a cluster spec is set, and ``'cluster'`` is wanted, ``inference_voxel_scores`` (``with_labels``) and
+        ``inference_tiled_voxel_scores`` also cluster the TRUE classes -- the batch's resident label list cast to uint8 -- under the
+        same spec and enqueue ``ursn_cluster_match`` behind it with the resident value list; the result gains ``true_cluster`` /
+        ``true_clusters`` (as ``cluster`` / ``clusters``) and ``match`` (as ``match_clusters`` returns it, A = predicted, B = true).
+        A batch without labels is then refused.  The legal members of ``want`` do not change; never called, the results have the
+        keys they had."""
+        if type(on) is not bool:
+            raise ValueError('set_cluster_matching: on = %r, expected a bool' % (on,))
+        self._cluster_matching_on = on
+
+    @staticmethod
+    def _label_classes(label, M):
+        """The float label list on the device as the uint8 classes ``ursn_cluster_voxels`` reads (a cast: plumbing)."""
+        import torch
+        if M == 0:
+            return torch.zeros(1, dtype=torch.uint8, device=label.device)
+        return label[:M].clamp(0, 255).to(torch.uint8)
+
+    def _enqueue_cluster_match(self, sess, d_offsets, side_a, side_b, d_value, n, M, pairs):
+        """``ursn_cluster_match`` behind two ``_enqueue_clusters`` (``side_a`` / ``side_b``: what they returned; the ids and table
+        offsets stay on the device); enqueues only."""
+        import torch
+        lib = _lib.load()
+        cap = M
+        need = int(lib.ursn_cluster_match_scratch_bytes(n, M, cap, cap, cap))
+        if need == 0:
+            raise ValueError('match_clusters: %d events with %d list entries are out of domain' % (n, M))
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=self._device)
+        I, R, EI, ER = _lib.CLMATCH_I, _lib.CLMATCH_R, _lib.CLMATCH_EI, _lib.CLMATCH_ER
+        rows = max(cap, 1)
+        ints = torch.empty(2 * rows * I + n * EI + (rows + 1) + 2 * rows, dtype=torch.int64, device=self._device)
+        reals = torch.empty(2 * rows * R + n * ER, dtype=torch.float64, device=self._device)
+        small = torch.empty(rows + 1, dtype=torch.int32, device=self._device)     # pair_b | status
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_match_desc()
+        d.n, d.m_total, d.offsets, d.value = n, M, ptr(d_offsets), ptr(d_value)
+        d.cluster_a, d.table_offsets_a = side_a[0].data_ptr(), side_a[2].data_ptr()
+        d.cluster_b, d.table_offsets_b = side_b[0].data_ptr(), side_b[2].data_ptr()
+        o = _lib.ursn_cluster_match_out()
+        ib, rb = ints.data_ptr(), reals.data_ptr()
+        o.a_int, o.b_int, o.event_int = ib, ib + 8 * rows * I, ib + 16 * rows * I
+        o.a_real, o.b_real, o.event_real = rb, rb + 8 * rows * R, rb + 16 * rows * R
+        o.cap_a = o.cap_b = cap
+        at = 16 * rows * I + 8 * n * EI
+        if pairs:
+            o.pair_offsets, o.pair_n, o.pair_q = ib + at, ib + at + 8 * (rows + 1), ib + at + 8 * (rows + 1) + 8 * rows
+            o.pair_b, o.pair_cap = small.data_ptr(), cap
+        o.status = small.data_ptr() + 4 * rows
+        _lib.check(lib.ursn_cluster_match(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, ints, reals, small):
+            t.record_stream(cur)
+        return ints, reals, small, rows, n, pairs
+
+    @staticmethod
+    def _fetch_cluster_match(pending, tables_a, tables_b):
+        """The records as per-event dicts of named arrays for either side, named arrays for the events and, with ``pairs``, per
+        event ``(a, b, n, q)``; raises on a non-zero status."""
+        from .clusters import MATCH_EVENT_INT, MATCH_EVENT_REAL, MATCH_ROW_INT, MATCH_ROW_REAL
+        ints, reals, small, rows, n, pairs = pending
+        I, R, EI, ER = _lib.CLMATCH_I, _lib.CLMATCH_R, _lib.CLMATCH_EI, _lib.CLMATCH_ER
+        code = int(small[rows:].cpu().numpy()[0])
+        if code != 0:
+            raise _lib.UrsnError('match_clusters: the ids, table offsets and lists disagree (status %d)' % code)
+        counts = [[int(t['first'].size) for t in tables] for tables in (tables_a, tables_b)]
+        total = [int(sum(c)) for c in counts]
+        assert max(total) <= rows, 'match_clusters: %r rows, room for %d' % (total, rows)
+        hi, hr = ints.cpu().numpy(), reals.cpu().numpy()
+        res = {}
+        for x, side in enumerate('ab'):
+            it = hi[x * rows * I:(x * rows + total[x]) * I].reshape(total[x], I)
+            rt = hr[x * rows * R:(x * rows + total[x]) * R].reshape(total[x], R)
+            per, at = [], 0
+            for k in counts[x]:
+                ev = {name: it[at:at + k, c].copy() for c, name in enumerate(MATCH_ROW_INT)}
+                ev.update({name: rt[at:at + k, c].copy() for c, name in enumerate(MATCH_ROW_REAL)})
+                per.append(ev)
+                at += k
+            res[side] = per
+        ei = hi[2 * rows * I:2 * rows * I + n * EI].reshape(n, EI)
+        er = hr[2 * rows * R:2 * rows * R + n * ER].reshape(n, ER)
+        res['events'] = {name: ei[:, c].copy() for c, name in enumerate(MATCH_EVENT_INT)}
+        res['events'].update({name: er[:, c].copy() for c, name in enumerate(MATCH_EVENT_REAL)})
+        assert np.array_equal(res['events']['rows_a'], counts[0]) and np.array_equal(res['events']['rows_b'], counts[1]), \
+            'match_clusters: row counts and the cluster tables disagree'
+        if pairs:
+            at = 2 * rows * I + n * EI
+            po = hi[at:at + total[0] + 1]
+            pn, pq = hi[at + rows + 1:at + 2 * rows + 1], hi[at + 2 * rows + 1:at + 3 * rows + 1]
+            pb = small[:rows].cpu().numpy()
+            assert po[0] == 0 and po[-1] <= rows, 'match_clusters: %d cells, room for %d' % (int(po[-1]), rows)
+            res['pairs'], r0 = [], 0
+            for k in counts[0]:
+                lo, hi_ = int(po[r0]), int(po[r0 + k])
+                a = np.repeat(np.arange(k, dtype=np.int32), np.diff(po[r0:r0 + k + 1]))
+                res['pairs'].append((a, pb[lo:hi_].copy(), pn[lo:hi_].copy(), pq[lo:hi_].copy()))
+                r0 += k
+        return res
+
+    def match_clusters(self, sess, voxels_or_lists, clusters_a, clusters_b, value=None, pairs=False):
+        """The match of two clusterings of the same lists: ``voxels_or_lists`` as ``cluster_voxels`` took it, ``clusters_a``
+        (predicted) and ``clusters_b`` (true) the dicts ``cluster_voxels`` returned (or a result's ``cluster`` / ``clusters`` under
+        those keys), ``value`` the entries' values as one flat array or per-event arrays (None: a VoxelBatch's own, or no charge for
+        plain lists).  Returns ``{'a': [...], 'b': [...], 'events': {...}}``: per event a dict of arrays with one row per cluster of
+        that side (``clusters.MATCH_ROW_INT`` + ``MATCH_ROW_REAL``), named arrays with one row per event (``MATCH_EVENT_INT`` +
+        ``MATCH_EVENT_REAL``) and, with ``pairs``, ``pairs``: per event the cells as ``(a, b, n, q)`` arrays, by A id, then B id."""
+        import torch
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off = np.asarray(voxels_or_lists.offsets, np.int64)
+            if value is None:
+                value = voxels_or_lists.value
+        else:
+            sizes = [np.asarray(a).size for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('match_clusters: %d events outside [1, 65535]' % n)
+        if type(pairs) is not bool:
+            raise ValueError('match_clusters: pairs = %r, expected a bool' % (pairs,))
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+            if value.size != M:
+                raise ValueError('match_clusters: %d list entries, %d values' % (M, value.size))
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        sides = []
+        for name, c in (('clusters_a', clusters_a), ('clusters_b', clusters_b)):
+            ids, tables = c['cluster'], c['clusters']
+            if len(ids) != n or len(tables) != n:
+                raise ValueError('match_clusters: %d events, %s of %d / %d' % (n, name, len(ids), len(tables)))
+            flat = np.concatenate([np.asarray(i, np.int32).reshape(-1) for i in ids])
+            if flat.size != M or any(np.asarray(i).size != off[e + 1] - off[e] for e, i in enumerate(ids)):
+                raise ValueError('match_clusters: the ids of %s do not have the lengths of the lists' % name)
+            toff = np.concatenate([[0], np.cumsum([int(t['first'].size) for t in tables])]).astype(np.int64)
+            sides.append((up(flat if M else np.zeros(1, np.int32), np.int32), None, up(toff, np.int64)))
+        d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
+        pending = self._enqueue_cluster_match(sess, up(off, np.int64), sides[0], sides[1], d_value, n, M, pairs)
+        return self._fetch_cluster_match(pending, clusters_a['clusters'], clusters_b['clusters'])
+
+    # ------------------------------------------------------------------------------------------
     # tiling: volumes larger than the network (not in the reference, whose events have the network's size; boxes, their
     # cores and the numpy statement of the device passes: tiling.py)
     # ------------------------------------------------------------------------------------------
@@ -1490,6 +1661,9 @@ class ssnet_base(object):
         if tile_batch is not None and int(tile_batch) < 1:
             raise ValueError('inference_tiled_voxel_scores: tile_batch = %r < 1' % (tile_batch,))
         big = tuple(int(s) for s in big)
+        matching = spec is not None and getattr(self, '_cluster_matching_on', False)
+        if matching and ('label' not in big_batch.ptr if isinstance(big_batch, _DeviceVoxelBatch) else big_batch.label is None):
+            raise ValueError('inference_tiled_voxel_scores: cluster matching is on and the batch has no labels to cluster')
         if not isinstance(big_batch, _DeviceVoxelBatch):
             big_batch = self.upload_voxels(big_batch, big)
         if big_batch.big != big:
@@ -1553,6 +1727,13 @@ class ssnet_base(object):
         if pending is not None and getattr(self, '_cluster_features_on', False):   # the stitched list, in the large shape
             objects = self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'],
                                                      big_batch.ptr['value'], pending, big)
+        truth = match = None
+        if matching:                               # the large batch's own labels under the same spec, then the match
+            at = big_batch.ptr['label'] - big_batch.dev.data_ptr()
+            label = big_batch.dev[at:at + 4 * M].view(torch.float32)
+            truth = self._enqueue_clusters(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], self._label_classes(label, M),
+                                           n, M, big, spec)
+            match = self._enqueue_cluster_match(sess, big_batch.ptr['offsets'], pending, truth, big_batch.ptr['value'], n, M, False)
         res = {'index': [big_batch.index[off[i]:off[i + 1]].copy() for i in range(n)]}
         for w in want:
             if w == 'cluster':
@@ -1563,6 +1744,9 @@ class ssnet_base(object):
             res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
         if objects is not None:
             res['objects'] = self._fetch_cluster_features(objects, res['clusters'])
+        if match is not None:
+            res['true_cluster'], res['true_clusters'] = self._fetch_clusters(truth, off)
+            res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row, objects_csv_header, objects_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -84,6 +84,7 @@ class ssnet_trainval(object):
         self._output = None
         self._csv = None
         self._objects = None
+        self._match = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -178,6 +179,8 @@ class ssnet_trainval(object):
             self._cluster_spec = cfg.cluster_spec()
         if cfg.ANA_OBJECTS and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_OBJECTS needs ANA_CLUSTER: the object records are reductions over the members of the clusters')
+        if cfg.ANA_MATCH and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_MATCH needs ANA_CLUSTER: the match compares the predicted clusters with those of the true classes')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -201,6 +204,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._objects.write(objects_csv_header())
                 self._objects.flush()
+        if cfg.ANA_MATCH and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_MATCH) or os.path.getsize(cfg.ANA_MATCH) == 0
+            self._match = open(cfg.ANA_MATCH, 'a')
+            if fresh:
+                self._match.write(match_csv_header())
+                self._match.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -219,6 +228,8 @@ class ssnet_trainval(object):
             self._net.set_clustering(self._cluster_spec)
             if self._objects:                # default off: never called
                 self._net.set_cluster_features(True)
+            if self._match:                  # default off: never called
+                self._net.set_cluster_matching(True)
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -565,6 +576,7 @@ class ssnet_trainval(object):
                     np.save(self._output, r['cluster'][i][keep])
             self._output.flush()
         self._write_objects(r, entries, vb.offsets, self._net._dims[:-1])
+        self._write_match(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -576,7 +588,11 @@ class ssnet_trainval(object):
                     ev['cluster'], ev['clusters'] = r['cluster'][i], r['clusters'][i]
                     if 'objects' in r:
                         ev['objects'] = r['objects'][i]
+                    if 'match' in r:
+                        ev['true_cluster'], ev['true_clusters'] = r['true_cluster'][i], r['true_clusters'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
+            if 'match' in r:
+                result['match'] = r['match']
         self._advance_main()
         return result
 
@@ -588,6 +604,14 @@ class ssnet_trainval(object):
             for k in range(objects['n'].shape[0]):
                 self._objects.write(objects_csv_row(entries[i], k, objects, r['index'][i], off[i], shape))
         self._objects.flush()
+
+    def _write_match(self, r, entries):
+        """ANA_MATCH: one CSV row per event of the result ``r``."""
+        if not getattr(self, '_match', None) or 'match' not in r:
+            return
+        for i in range(len(entries)):
+            self._match.write(match_csv_row(entries[i], r['match']['events'], i))
+        self._match.flush()
 
     def _ana_step_tiled(self, vb, entries, batch_mode):
         """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
@@ -613,6 +637,7 @@ class ssnet_trainval(object):
                     np.save(self._output, r['cluster'][i][keep])
             self._output.flush()
         self._write_objects(r, entries, vb.offsets, c.ANA_TILE)
+        self._write_match(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -624,8 +649,12 @@ class ssnet_trainval(object):
                     ev['cluster'], ev['clusters'] = r['cluster'][i], r['clusters'][i]
                     if 'objects' in r:
                         ev['objects'] = r['objects'][i]
+                    if 'match' in r:
+                        ev['true_cluster'], ev['true_clusters'] = r['true_cluster'][i], r['true_clusters'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
+            if 'match' in r:
+                result['match'] = r['match']
         self._advance_main()
         return result
 
@@ -792,7 +821,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_objects', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_match', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
