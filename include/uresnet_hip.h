@@ -1098,6 +1098,94 @@ size_t ursn_cluster_match_scratch_bytes(int32_t n, int64_t m_total, int64_t cap_
 int ursn_cluster_match(const ursn_cluster_match_desc* d, const ursn_cluster_match_out* out, void* scratch, size_t scratch_bytes,
                        void* stream);
 
+/* ---- cluster contact graph: which clusters lie near each other, and the interaction groups they form (cluster_graph.hip) ---------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * The step from objects to relations to groups.  Input: the lists ursn_cluster_voxels read, the ids and table_offsets it wrote,
+ * optionally the value list and the cluster table's cls.  uresnet_amd/clusters.py (cluster_graph_numpy) states every field; the
+ * device gives the same bits.  Every quantity is an integer.
+ *
+ * Coordinates x[0..2] are the row-major coordinates of index[j] in `spatial` (2-D: x[2] = 0).  Two entries of one event are NEAR
+ * when each has an id >= 0, the ids differ and the coordinates differ by at most `gap` on every axis (Chebyshev distance, decided on
+ * coordinates: never across a row end, a plane end or an event boundary).  An EDGE is an unordered pair of rows a < b of one event
+ * with at least one near pair of entries, one in a and one in b.
+ *
+ * Edge record, URSN_CLGRAPH_E int64, CSR by global row a (edge_offsets[r] .. edge_offsets[r + 1], ascending b):
+ *   [0] b       event-local id of the higher row           [1] pairs   unordered near pairs of entries between the two rows
+ *   [2] touch   those at Chebyshev distance 1              [3] dist2   the smallest squared Euclidean distance over the near pairs
+ *   [4] pos_a   [5] pos_b   list positions (in the whole batch) of the near pair smallest in (dist2, position in a, position in b)
+ * Row record, URSN_CLGRAPH_I int64:
+ *   [0] degree  edges of the row, on either side           [1] group   event-local group id
+ *   [2] nearest event-local id of the partner smallest in (dist2, id); -1 without an edge      [3] nearest_dist2 (0 without one)
+ *   [4] pairs   summed over the row's edges                [5] touching   edges of the row with touch > 0
+ * GROUPS are the connected components of an event's rows under its edges (a row without an edge is a group of its own), numbered
+ * per event in the order of their lowest row id.  Group record, URSN_CLGRAPH_G int64, with group_offsets[n + 1]:
+ *   [0] rows   [1] edges   [2] n = member entries   [3] charge = sum of rint((double)value * 2^16) (|value| >= 2^15 or a non-finite
+ *   value adds nothing and sets bit 0 of the flags; no value list: 0)   [4..6] lo   [7..9] hi (the coordinate box, 0 for the missing
+ *   2-D axis)   [10] first_row   [11] class_mask | flags << 32 (bit cls of every member row; cls must be < 32; no cls: 0)
+ * Event record, URSN_CLGRAPH_EV int64: [0] groups   [1] edges   [2] isolated (rows of degree 0)   [3] the largest group's n.
+ * Per entry: group int32 = the event-local group of the entry's row, -1 for id -1.
+ *
+ * Bounds: every entry has at most (2 gap + 1)^3 - 1 = 342 neighbours and each pair is counted once, so pairs < m_total * 171 < 2^39
+ * in an edge, a row or summed over all; dist2 <= 3 * 3^2 = 27; box coordinates are below 2^15; |charge| <= 2^31 * 2^31 = 2^62.
+ *
+ * Method: one thread per entry visits the 5 / 13 / 25 rows of the volume before its own within +-gap and the left part of its own
+ * row, one binary search (<= 32 halvings) and at most 2 gap + 1 consecutive entries each: every unordered pair once, from its higher
+ * list position, no dense map.  Edges are counted in an open-addressing table in the scratch, a power of two >= 2 edge_cap + 2
+ * slots, keyed (row a << 32) | row b: 64-bit compare-and-swap claims and 64-bit INTEGER atomic adds at agent scope; the closest pair
+ * is ONE packed 64-bit atomic minimum (dist2 << 40 | pos_a << 9 | code of x_b - x_a, which orders pos_b), pos_b is found again by a
+ * binary search.  Equal-edge lanes next to each other in a wave are combined first, then the edges of a workgroup in a 256-slot LDS
+ * table that falls through to direct insertions when full (URSN_CLGRAPH_WAVE=0: one insertion per near pair; same bits).  Groups:
+ * union-find over global rows with 32-bit atomicMin links to the lower root, flatten, count / one-workgroup scan / rank; group
+ * records by 64-bit integer adds, minima, maxima and ors.  Edge list: scan, drop, rank by b.  No float atomics.  Enqueues only, never
+ * synchronises; the scratch needs no initialisation; every device loop is bounded; the same arguments give the same bits.
+ *
+ * *status is 0, or: bit 0 an id outside [-1, K_e) or offsets that are not those of the lists, bit 1 a row without a member, bit 2 an
+ * index outside the volume at an entry with an id, bit 3 a bounded loop ran out, bit 4 a cls >= 32 (such an entry or row is
+ * skipped); URSN_CLGRAPH_EDGE_OVERFLOW: more than edge_cap distinct edges exist -- decided by the arguments alone -- and then only
+ * *status is defined.  Rows, groups and edges at or beyond cap_rows / cap_groups / edge_out_cap are never written; everything below
+ * them is complete whatever the caps are; edge_offsets and group_offsets hold the true counts.  Null, misaligned, out-of-domain and
+ * too-small arguments are refused with a message that begins "cluster_graph:" before any launch. */
+#define URSN_CLGRAPH_E 6    /* int64 columns of an edge record */
+#define URSN_CLGRAPH_I 6    /* int64 columns of a row record */
+#define URSN_CLGRAPH_G 12   /* int64 columns of a group record */
+#define URSN_CLGRAPH_EV 4   /* int64 columns of an event record */
+#define URSN_CLGRAPH_EDGE_OVERFLOW 256 /* bit of *status */
+
+typedef struct ursn_cluster_graph_desc { /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t gap;                          /* 1..3 */
+  int64_t m_total;                      /* list entries, < 2^31 */
+  int64_t edge_cap;                     /* distinct edges the scratch has room for, [0, 2^30) */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] strictly increasing per event */
+  const int32_t* cluster;               /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets;         /* [n+1] */
+  const float* value;                   /* [m_total], or null: every charge is 0 */
+  const uint8_t* cls;                   /* [K_total] the cluster table's cls, or null: every class mask is 0 */
+} ursn_cluster_graph_desc;
+
+typedef struct ursn_cluster_graph_out { /* DEVICE pointers */
+  int64_t* rows;                        /* [cap_rows][URSN_CLGRAPH_I] */
+  int64_t cap_rows;
+  int64_t* groups;                      /* [cap_groups][URSN_CLGRAPH_G] */
+  int64_t cap_groups;
+  int64_t* group_offsets;               /* [n+1] */
+  int64_t* event;                       /* [n][URSN_CLGRAPH_EV] */
+  int32_t* group;                       /* [m_total] */
+  int64_t* edge_offsets;                /* [cap_rows + 1], or null: no edge list; entries 0 .. min(K_total, cap_rows) are written */
+  int64_t* edges;                       /* [edge_out_cap][URSN_CLGRAPH_E], or null: the counts in edge_offsets only */
+  int64_t edge_out_cap;
+  int32_t* status;                      /* [1] */
+} ursn_cluster_graph_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535], m_total outside [0, 2^31), a cap < 0 or edge_cap outside
+ * [0, 2^30).  Host logic only. */
+size_t ursn_cluster_graph_scratch_bytes(int32_t n, int64_t m_total, int64_t cap_rows, int64_t cap_groups, int64_t edge_cap);
+int ursn_cluster_graph(const ursn_cluster_graph_desc* d, const ursn_cluster_graph_out* out, void* scratch, size_t scratch_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,22 @@ class ursn_cluster_match_out(C.Structure):
                 ("status", C.c_void_p)]
 
 
+CLGRAPH_E, CLGRAPH_I, CLGRAPH_G, CLGRAPH_EV = 6, 6, 12, 4   # URSN_CLGRAPH_*: columns of the edge / row / group / event records
+CLGRAPH_EDGE_OVERFLOW = 256                                 # URSN_CLGRAPH_EDGE_OVERFLOW: bit of *status
+
+
+class ursn_cluster_graph_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("gap", C.c_int32), ("m_total", C.c_int64),
+                ("edge_cap", C.c_int64), ("offsets", C.c_void_p), ("index", C.c_void_p), ("cluster", C.c_void_p),
+                ("table_offsets", C.c_void_p), ("value", C.c_void_p), ("cls", C.c_void_p)]
+
+
+class ursn_cluster_graph_out(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("cap_rows", C.c_int64), ("groups", C.c_void_p), ("cap_groups", C.c_int64),
+                ("group_offsets", C.c_void_p), ("event", C.c_void_p), ("group", C.c_void_p), ("edge_offsets", C.c_void_p),
+                ("edges", C.c_void_p), ("edge_out_cap", C.c_int64), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -268,6 +284,8 @@ _SIGS = {
     "ursn_cluster_features": (C.c_int, [C.POINTER(ursn_cluster_feat_desc), C.POINTER(ursn_cluster_feat_out), _P, C.c_size_t, _P]),
     "ursn_cluster_match_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_match": (C.c_int, [C.POINTER(ursn_cluster_match_desc), C.POINTER(ursn_cluster_match_out), _P, C.c_size_t, _P]),
+    "ursn_cluster_graph_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "ursn_cluster_graph": (C.c_int, [C.POINTER(ursn_cluster_graph_desc), C.POINTER(ursn_cluster_graph_out), _P, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

@@ -409,3 +409,193 @@ def cluster_match_numpy(offsets, cluster_a, table_offsets_a, cluster_b, table_of
     out['pair_offsets'] = np.array(pair_offsets, np.int64)
     out['pair_b'], out['pair_n'], out['pair_q'] = np.array(pb, np.int32), np.array(pn, np.int64), np.array(pq, np.int64)
     return out
+
+
+# ---- cluster contact graph (csrc/cluster_graph.hip does it on the device; this is the statement) ----------------------------------
+GRAPH_EDGE = ('b', 'pairs', 'touch', 'dist2', 'pos_a', 'pos_b')
+GRAPH_ROW = ('degree', 'group', 'nearest', 'nearest_dist2', 'pairs', 'touching')
+GRAPH_GROUP = ('rows', 'edges', 'n', 'charge', 'lo0', 'lo1', 'lo2', 'hi0', 'hi1', 'hi2', 'first_row', 'mask_flags')
+GRAPH_EVENT = ('groups', 'edges', 'isolated', 'largest')
+GRAPH_MAX_GAP = 3
+
+
+class ClusterGraphSpec(object):
+    """``gap`` in [1, 3]: two entries of different clusters are near when their coordinates differ by at most ``gap`` on every
+    axis."""
+
+    def __init__(self, gap=1):
+        if type(gap) is not int or not 1 <= gap <= GRAPH_MAX_GAP:
+            raise ValueError('ClusterGraphSpec: gap = %r, expected an integer in [1, %d]' % (gap, GRAPH_MAX_GAP))
+        self.gap = gap
+
+    def __repr__(self):
+        return 'ClusterGraphSpec(gap=%r)' % (self.gap,)
+
+
+def cluster_graph_numpy(offsets, index, cluster, table_offsets, spatial, spec=None, value=None, cls=None):
+    """The statement of the contact graph of the clusters of concatenated per-event lists: ``index`` sorted per event, row-major in
+    ``spatial`` (2 or 3 extents <= 32768), ``cluster`` the event-local ids or -1 and ``table_offsets`` [n+1] as
+    ``ursn_cluster_voxels`` writes them (global row = ``table_offsets[event]`` + id), optionally ``value`` [m] and the cluster
+    table's ``cls`` [K_total].  Slow on purpose: Python integers, one entry and one offset at a time.
+
+    Coordinates are ``np.unravel_index(index, spatial)``, with x[2] = 0 in 2-D.  Two entries of one event are NEAR when each has an
+    id >= 0, the ids differ and the coordinates differ by at most ``spec.gap`` on every axis (Chebyshev distance, decided on
+    coordinates, never on indices).  An EDGE is an unordered pair of rows a < b of one event with at least one near pair of entries,
+    one in a and one in b.
+
+    GRAPH_EDGE: ``b`` (event-local), ``pairs`` the unordered near pairs between the two rows, ``touch`` those at Chebyshev distance
+    1, ``dist2`` the smallest squared Euclidean distance over them, ``pos_a`` / ``pos_b`` the positions in the concatenated list of
+    the near pair smallest in (dist2, position in a, position in b).  Stored as CSR by global row a, ascending b, with
+    ``edge_offsets`` [K_total + 1].  GRAPH_ROW: ``degree`` (edges on either side), ``group`` (event-local), ``nearest`` the
+    event-local id of the partner smallest in (dist2, id) or -1, ``nearest_dist2`` (0 without an edge), ``pairs`` summed over the
+    row's edges, ``touching`` its edges with touch > 0.  GROUPS are the connected components of an event's rows under its edges,
+    numbered per event in the order of their lowest row.  GRAPH_GROUP: ``rows``, ``edges``, ``n`` member entries, ``charge`` = sum of
+    rint(float64(value) * 2^16) (|value| >= 2^15 or a non-finite value adds nothing and sets bit 0 of the flags; 0 without values),
+    the coordinate box ``lo`` / ``hi`` (0 for the missing 2-D axis), ``first_row``, ``mask_flags`` = class_mask | flags << 32 with
+    bit ``cls`` of every member row (0 without ``cls``); with ``group_offsets`` [n+1].  GRAPH_EVENT: ``groups``, ``edges``,
+    ``isolated`` (rows of degree 0), ``largest`` (the largest group's n).  Per entry ``group``: the group of its row, -1 for id -1.
+
+    Bounds: an entry has at most 7^3 - 1 = 342 neighbours and every pair is counted once, so pairs < m * 171 < 2^39; dist2 <= 27;
+    the box is within 2^15; |charge| <= 2^31 * 2^31 = 2^62.
+
+    An id outside [-1, K_e), a row without a member, an index outside the volume at an entry with an id and a cls >= 32 raise
+    ValueError.  Returns a dict: ``edge_offsets`` int64 [K+1], ``edges`` int64 [E, 6], ``rows`` int64 [K, 6], ``group_offsets``
+    int64 [n+1], ``groups`` int64 [G, 12], ``events`` int64 [n, 4], ``group`` int32 [m]."""
+    spec = ClusterGraphSpec() if spec is None else spec
+    if not isinstance(spec, ClusterGraphSpec):
+        raise ValueError('cluster_graph_numpy: spec = %r, expected a ClusterGraphSpec' % (spec,))
+    gap = spec.gap
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or any(not 1 <= s <= MAX_EXTENT for s in spatial):
+        raise ValueError('cluster_graph_numpy: spatial = %r, expected 2 or 3 extents in [1, %d]' % (spatial, MAX_EXTENT))
+    offsets = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    index = [int(x) for x in np.asarray(index).reshape(-1)]
+    ids = [int(x) for x in np.asarray(cluster).reshape(-1)]
+    nev, m = len(offsets) - 1, len(index)
+    if nev < 1 or len(toff) != nev + 1 or len(ids) != m or offsets[0] != 0 or offsets[-1] != m or toff[0] != 0 \
+            or any(offsets[e + 1] < offsets[e] or toff[e + 1] < toff[e] for e in range(nev)):
+        raise ValueError('cluster_graph_numpy: offsets, table offsets and the lists disagree')
+    K = toff[-1]
+    if value is not None:
+        value = np.asarray(value, np.float32).reshape(-1)
+        if value.size != m:
+            raise ValueError('cluster_graph_numpy: %d values for %d entries' % (value.size, m))
+    if cls is not None:
+        cls = [int(c) for c in np.asarray(cls).reshape(-1)]
+        if len(cls) != K or any(not 0 <= c < 32 for c in cls):
+            raise ValueError('cluster_graph_numpy: cls must hold %d classes in [0, 32)' % K)
+    vox = 1
+    for s in spatial:
+        vox *= s
+    steps = [d for d in np.ndindex(*([2 * gap + 1] * len(spatial))) if any(x != gap for x in d)]
+    edges = {}                                   # (global a, global b) -> [pairs, touch, (dist2, pos_a, pos_b)]
+    members = [0] * K
+    coords = [None] * m
+    for e in range(nev):
+        ke = toff[e + 1] - toff[e]
+        where = {}
+        for j in range(offsets[e], offsets[e + 1]):
+            if not -1 <= ids[j] < ke:
+                raise ValueError('cluster_graph_numpy: entry %d has id %d outside [-1, %d)' % (j, ids[j], ke))
+            if ids[j] < 0:
+                continue
+            if not 0 <= index[j] < vox:
+                raise ValueError('cluster_graph_numpy: entry %d has index %d outside the volume %r' % (j, index[j], spatial))
+            x = tuple(int(c) for c in np.unravel_index(index[j], spatial))
+            coords[j] = x + (0,) * (3 - len(x))
+            where[x] = j
+            members[toff[e] + ids[j]] += 1
+        for x, j in where.items():
+            for d in steps:
+                y = tuple(x[k] + d[k] - gap for k in range(len(x)))
+                q = where.get(y)
+                if q is None or q > j or ids[q] == ids[j]:    # every unordered pair once, from its higher position
+                    continue
+                (ra, pa), (rb, pb) = sorted(((ids[j], j), (ids[q], q)))
+                delta = [abs(d[k] - gap) for k in range(len(x))]
+                cell = edges.setdefault((toff[e] + ra, toff[e] + rb), [0, 0, None])
+                cell[0] += 1
+                cell[1] += 1 if max(delta) == 1 else 0
+                rank = (sum(v * v for v in delta), pa, pb)
+                if cell[2] is None or rank < cell[2]:
+                    cell[2] = rank
+    for r in range(K):
+        if members[r] == 0:
+            raise ValueError('cluster_graph_numpy: row %d has no member' % r)
+    event_of = [e for e in range(nev) for _ in range(toff[e + 1] - toff[e])]
+    rows = [[0, -1, -1, 0, 0, 0] for _ in range(K)]
+    nearest = [None] * K
+    parent = list(range(K))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    edge_offsets, table = [0], []
+    by_row = [[] for _ in range(K)]
+    for (a, b) in sorted(edges):
+        by_row[a].append(b)
+    for a in range(K):
+        for b in by_row[a]:
+            pairs, touch, (dist2, pa, pb) = edges[(a, b)]
+            assert pairs < max(m, 1) * 171 and dist2 <= 27
+            table.append([b - toff[event_of[a]], pairs, touch, dist2, pa, pb])
+            for x, y in ((a, b), (b, a)):
+                rows[x][0] += 1
+                rows[x][4] += pairs
+                rows[x][5] += 1 if touch > 0 else 0
+                if nearest[x] is None or (dist2, y) < nearest[x]:
+                    nearest[x] = (dist2, y)
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+        edge_offsets.append(len(table))
+    roots = [find(r) for r in range(K)]
+    group_of, group_offsets, groups = [0] * K, [0], []
+    events = [[0, 0, 0, 0] for _ in range(nev)]
+    for e in range(nev):
+        local = {}
+        for r in range(toff[e], toff[e + 1]):
+            if roots[r] == r:
+                local[r] = len(local)
+                groups.append([0, 0, 0, 0, MAX_EXTENT, MAX_EXTENT, MAX_EXTENT, -1, -1, -1, r - toff[e], 0])
+            g = group_offsets[e] + local[roots[r]]              # a root is the lowest row of its group: it came first
+            group_of[r] = g
+            rows[r][1] = local[roots[r]]
+            if nearest[r] is not None:
+                rows[r][2], rows[r][3] = nearest[r][1] - toff[e], nearest[r][0]
+            groups[g][0] += 1
+            groups[g][1] += len(by_row[r])
+            if cls is not None:
+                groups[g][11] |= 1 << cls[r]
+            events[e][1] += len(by_row[r])
+            events[e][2] += 1 if rows[r][0] == 0 else 0
+        group_offsets.append(len(groups))
+        events[e][0] = len(local)
+    group = np.full(m, -1, np.int32)
+    for e in range(nev):
+        for j in range(offsets[e], offsets[e + 1]):
+            if ids[j] < 0:
+                continue
+            g = group_of[toff[e] + ids[j]]
+            rec = groups[g]
+            group[j] = g - group_offsets[e]
+            rec[2] += 1
+            if value is not None:
+                val = np.float64(value[j])
+                if not np.isfinite(val) or abs(val) >= FIX_LIMIT:
+                    rec[11] |= 1 << 32
+                else:
+                    rec[3] += int(np.rint(val * np.float64(2.0 ** FIX_SHIFT)))
+            for k in range(3):
+                rec[4 + k], rec[7 + k] = min(rec[4 + k], coords[j][k]), max(rec[7 + k], coords[j][k])
+    for e in range(nev):
+        for g in range(group_offsets[e], group_offsets[e + 1]):
+            assert abs(groups[g][3]) <= 2 ** 62
+            events[e][3] = max(events[e][3], groups[g][2])
+    return {'edge_offsets': np.array(edge_offsets, np.int64), 'edges': np.array(table, np.int64).reshape(-1, 6),
+            'rows': np.array(rows, np.int64).reshape(-1, 6), 'group_offsets': np.array(group_offsets, np.int64),
+            'groups': np.array(groups, np.int64).reshape(-1, 12), 'events': np.array(events, np.int64).reshape(-1, 4), 'group': group}

@@ -164,6 +164,13 @@ class ssnet_config(object):
     # four event reals (adjusted Rand index, purity, efficiency, mutual fraction).  '' = off.  Refused without ANA_CLUSTER; ignored
     # with TRAIN, like every ANA_* key
     ANA_MATCH = ''
+    # ANA_GRAPH '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per interaction group: the connected components of the
+    # predicted clusters under "some voxel of one lies within GRAPH_GAP voxels of some voxel of the other on every axis"
+    # (ssnet_base.set_cluster_graph; clusters.cluster_graph_numpy holds the definition): entry, group and the twelve group integers
+    # (rows, edges, entries, fixed-point charge, box, first row, class mask | flags << 32).  '' = off.  Refused without ANA_CLUSTER;
+    # ignored with TRAIN, like every ANA_* key.  GRAPH_GAP = 1, 2 or 3
+    ANA_GRAPH = ''
+    GRAPH_GAP = 1
 
     def __init__(self):
         pass
@@ -271,6 +278,9 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'CLUSTER_MIN_SIZE' and value < 1:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'GRAPH_GAP' and not 1 <= value <= 3:
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             setattr(self, key, value)

@@ -220,6 +220,18 @@ def match_csv_row(entry, events, i):
                     [repr(float(events[name][i])) for name in MATCH_EVENT_REAL]) + '\n'
 
 
+def graph_csv_header():
+    """The header line of the ANA_GRAPH file: one row per interaction group."""
+    from .clusters import GRAPH_GROUP
+    return ','.join(('entry', 'group') + GRAPH_GROUP) + '\n'
+
+
+def graph_csv_row(entry, g, groups):
+    """Group ``g`` of one event's ``groups`` record (a dict of columns, ``clusters.GRAPH_GROUP``) as a CSV row of integers."""
+    from .clusters import GRAPH_GROUP
+    return ','.join(['%d' % entry, '%d' % g] + ['%d' % int(groups[name][g]) for name in GRAPH_GROUP]) + '\n'
+
+
 def objects_csv_row(entry, k, objects, index, start, shape):
     """Cluster ``k`` of one event's ``objects`` record as a CSV row.  ``index`` is the event's index list, ``start`` the list position
     of its first entry (``end_lo`` / ``end_hi`` count from the start of the batch), ``shape`` the shape the indices are row-major in.
@@ -1089,6 +1101,11 @@ class ssnet_base(object):
             truth = self._enqueue_clusters(sess, d_offsets, d_index, self._label_classes(buf[at:at + nbytes].view(torch.float32), M),
                                            n, M, self._dims[:-1], spec)
             match = self._enqueue_cluster_match(sess, d_offsets, pending, truth, self._fed_value, n, M, False)
+        gspec = getattr(self, '_cluster_graph_spec', None) if pending is not None else None
+        graph = None
+        if gspec is not None:                      # behind the cluster passes, same lists
+            graph = self._enqueue_cluster_graph(sess, d_offsets, d_index, self._fed_value, pending[0], pending[2], pending[1], n, M,
+                                                self._dims[:-1], gspec, M + 1024, True)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self._device))
         slot.consumed[turn] = done                 # the gather head has read offsets / index: the list buffer is free again
@@ -1105,6 +1122,8 @@ class ssnet_base(object):
         if match is not None:
             res['true_cluster'], res['true_clusters'] = self._fetch_clusters(truth, off)
             res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
+        if graph is not None:
+            res['graph'] = self._finish_cluster_graph(sess, graph, voxels, res, gspec, self._dims[:-1])
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1474,6 +1493,180 @@ class ssnet_base(object):
         return self._fetch_cluster_match(pending, clusters_a['clusters'], clusters_b['clusters'])
 
     # ------------------------------------------------------------------------------------------
+    # cluster contact graph (definition and numpy statement: clusters.cluster_graph_numpy, device passes: csrc/cluster_graph.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_graph(self, spec):
+        """A ``clusters.ClusterGraphSpec``, while a cluster spec is set and ``'cluster'`` is wanted, makes
+        ``inference_voxel_scores`` and ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_graph`` behind the cluster passes
+        (tiled: on the stitched list in the large shape, so groups cross tile borders), with the batch's own resident value list;
+        the result gains ``graph`` (as ``cluster_graph`` returns it).  None takes it away again.  The legal members of ``want`` do
+        not change; never called, the results have the keys they had."""
+        from .clusters import ClusterGraphSpec
+        if spec is not None and not isinstance(spec, ClusterGraphSpec):
+            raise ValueError('set_cluster_graph: spec = %r, expected a clusters.ClusterGraphSpec or None' % (spec,))
+        self._cluster_graph_spec = spec
+
+    def _enqueue_cluster_graph(self, sess, d_offsets, d_index, d_value, d_cluster, d_toff, d_cls, n, M, shape, spec, edge_cap, edges):
+        """``ursn_cluster_graph`` on device lists, ids and table offsets (raw pointers or tensors); enqueues only."""
+        import torch
+        lib = _lib.load()
+        shape = [int(s) for s in shape]
+        edge_cap = int(min(max(edge_cap, 0), 2 ** 30 - 1))
+        cap = M
+        need = int(lib.ursn_cluster_graph_scratch_bytes(n, M, cap, cap, edge_cap))
+        if need == 0:
+            raise ValueError('cluster_graph: %d events with %d list entries are out of domain' % (n, M))
+        E, I, G, EV = _lib.CLGRAPH_E, _lib.CLGRAPH_I, _lib.CLGRAPH_G, _lib.CLGRAPH_EV
+        rows, ecap = max(cap, 1), max(edge_cap, 1)
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=self._device)
+        # rows | groups | group_offsets | event | edge_offsets | edges
+        ints = torch.empty(rows * (I + G) + (n + 1) + n * EV + (rows + 1) + (ecap * E if edges else 0), dtype=torch.int64,
+                           device=self._device)
+        small = torch.empty(rows + 1, dtype=torch.int32, device=self._device)      # group | status
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_graph_desc()
+        d.ndim, d.n, d.gap, d.m_total, d.edge_cap = len(shape), n, spec.gap, M, edge_cap
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ptr(d_cluster), ptr(d_toff)
+        d.value, d.cls = ptr(d_value), ptr(d_cls)
+        o = _lib.ursn_cluster_graph_out()
+        at = ints.data_ptr()
+        o.rows, o.cap_rows = at, cap
+        o.groups, o.cap_groups = at + 8 * rows * I, cap
+        o.group_offsets = at + 8 * rows * (I + G)
+        o.event = o.group_offsets + 8 * (n + 1)
+        if edges:
+            o.edge_offsets = o.event + 8 * n * EV
+            o.edges, o.edge_out_cap = o.edge_offsets + 8 * (rows + 1), edge_cap
+        o.group, o.status = small.data_ptr(), small.data_ptr() + 4 * rows
+        _lib.check(lib.ursn_cluster_graph(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, ints, small):
+            t.record_stream(cur)
+        return ints, small, rows, ecap, n, M, edges
+
+    @staticmethod
+    def _fetch_cluster_graph(pending, off, counts):
+        """The tables as per-event dicts (``counts``: rows per event), or None when the edge table was too small; raises on any
+        other status."""
+        from .clusters import GRAPH_EDGE, GRAPH_EVENT, GRAPH_GROUP, GRAPH_ROW
+        ints, small, rows, ecap, n, M, edges = pending
+        E, I, G, EV = _lib.CLGRAPH_E, _lib.CLGRAPH_I, _lib.CLGRAPH_G, _lib.CLGRAPH_EV
+        hs = small.cpu().numpy()
+        code = int(hs[rows])
+        if code == _lib.CLGRAPH_EDGE_OVERFLOW:
+            return None
+        if code != 0:
+            raise _lib.UrsnError('cluster_graph: the ids, table offsets and lists disagree (status %d)' % code)
+        total = int(sum(counts))
+        assert total <= rows, 'cluster_graph: %d rows, room for %d' % (total, rows)
+        hi = ints.cpu().numpy()
+        rt = hi[:total * I].reshape(total, I)
+        goff = hi[rows * (I + G):rows * (I + G) + n + 1]
+        gt = hi[rows * I:rows * I + int(goff[-1]) * G].reshape(int(goff[-1]), G)
+        at = rows * (I + G) + n + 1
+        ev = hi[at:at + n * EV].reshape(n, EV)
+        at += n * EV
+        res, r0 = [], 0
+        if edges:
+            eoff = hi[at:at + total + 1]
+            et = hi[at + rows + 1:at + rows + 1 + int(eoff[-1]) * E].reshape(int(eoff[-1]), E)
+        for i, k in enumerate(counts):
+            one = {'rows': {name: rt[r0:r0 + k, c].copy() for c, name in enumerate(GRAPH_ROW)},
+                   'groups': {name: gt[goff[i]:goff[i + 1], c].copy() for c, name in enumerate(GRAPH_GROUP)},
+                   'group': hs[off[i]:off[i + 1]].copy(),
+                   'event': {name: int(ev[i, c]) for c, name in enumerate(GRAPH_EVENT)}}
+            if edges:
+                lo = int(eoff[r0])
+                one['edge_offsets'] = (eoff[r0:r0 + k + 1] - lo).copy()
+                one['edges'] = {name: et[lo:int(eoff[r0 + k]), c].copy() for c, name in enumerate(GRAPH_EDGE)}
+            res.append(one)
+            r0 += k
+        return res
+
+    def _finish_cluster_graph(self, sess, pending, voxels_or_lists, res, spec, shape, value=None):
+        """The graph enqueued with a voxel-score call, or -- its edge table was too small -- ``cluster_graph`` on the returned ids."""
+        counts = [int(t['first'].size) for t in res['clusters']]
+        off = np.concatenate([[0], np.cumsum([np.asarray(c).size for c in res['cluster']])]).astype(np.int64)
+        got = self._fetch_cluster_graph(pending, off, counts)
+        if got is None:
+            got = self.cluster_graph(sess, voxels_or_lists, res, spec, value=value() if callable(value) else value, shape=shape)
+        return got
+
+    @staticmethod
+    def _resident_value(batch):
+        """The value list of an uploaded batch, read back from the device."""
+        import torch
+        if batch.m == 0:
+            return np.zeros(0, np.float32)
+        at = batch.ptr['value'] - batch.dev.data_ptr()
+        return batch.dev[at:at + 4 * batch.m].view(torch.float32).cpu().numpy()
+
+    def cluster_graph(self, sess, voxels_or_lists, clusters, spec, value=None, shape=None, edges=True):
+        """The contact graph and interaction groups of clusters already made: ``voxels_or_lists`` and ``shape`` as
+        ``cluster_voxels`` took them, ``clusters`` the dict it returned (or a result's ``cluster`` / ``clusters`` under those keys),
+        ``spec`` a ``clusters.ClusterGraphSpec``, ``value`` the entries' values as one flat array or per-event arrays (None: a
+        VoxelBatch's own, or no charge for plain lists).  Returns per event a dict: ``rows`` (columns ``clusters.GRAPH_ROW``, one
+        row per cluster), ``groups`` (columns ``GRAPH_GROUP``), ``group`` (int32 [m_i]), ``event`` (``GRAPH_EVENT`` as integers)
+        and, with ``edges``, ``edge_offsets`` [K_i + 1] and ``edges`` (columns ``GRAPH_EDGE``; ``pos_a`` / ``pos_b`` are positions
+        in the concatenated list).  The edge table starts at ``4 K_total + 1024`` edges and doubles while the device reports that it
+        was too small, up to the number of row pairs."""
+        import torch
+        from .clusters import ClusterGraphSpec
+        if not isinstance(spec, ClusterGraphSpec):
+            raise ValueError('cluster_graph: spec = %r, expected a clusters.ClusterGraphSpec' % (spec,))
+        if type(edges) is not bool:
+            raise ValueError('cluster_graph: edges = %r, expected a bool' % (edges,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_graph: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = voxels_or_lists.value
+        elif isinstance(voxels_or_lists, _DeviceVoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = self._resident_value(voxels_or_lists)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_graph: %d events outside [1, 65535]' % n)
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_graph: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids])
+        if cluster.size != M or index.size != M or (value is not None and value.size != M):
+            raise ValueError('cluster_graph: %d list entries, %d indices, %d ids, %s values'
+                             % (M, index.size, cluster.size, 'no' if value is None else value.size))
+        counts = [int(t['first'].size) for t in tables]
+        toff = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        cls = np.concatenate([np.asarray(t['cls'], np.uint8).reshape(-1) for t in tables])
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a if a.size else np.zeros(1, dt), dtype=dt)).to(self._device)
+        d_off, d_index, d_toff, d_cluster, d_cls = up(off, np.int64), up(index, np.int32), up(toff, np.int64), \
+            up(cluster, np.int32), up(cls, np.uint8)
+        d_value = None if value is None else up(value, np.float32)
+        most = sum(k * (k - 1) // 2 for k in counts)          # no more edges than pairs of rows
+        edge_cap = 4 * int(toff[-1]) + 1024
+        while True:
+            pending = self._enqueue_cluster_graph(sess, d_off, d_index, d_value, d_cluster, d_toff, d_cls, n, M, shape, spec,
+                                                  edge_cap, edges)
+            got = self._fetch_cluster_graph(pending, off, counts)
+            if got is not None:
+                return got
+            if edge_cap >= most or edge_cap >= 2 ** 30 - 1:
+                raise _lib.UrsnError('cluster_graph: the edge table overflowed at %d edges, the number of row pairs' % edge_cap)
+            edge_cap = min(2 * edge_cap, max(most, 1), 2 ** 30 - 1)
+
+    # ------------------------------------------------------------------------------------------
     # tiling: volumes larger than the network (not in the reference, whose events have the network's size; boxes, their
     # cores and the numpy statement of the device passes: tiling.py)
     # ------------------------------------------------------------------------------------------
@@ -1734,6 +1927,11 @@ class ssnet_base(object):
             truth = self._enqueue_clusters(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], self._label_classes(label, M),
                                            n, M, big, spec)
             match = self._enqueue_cluster_match(sess, big_batch.ptr['offsets'], pending, truth, big_batch.ptr['value'], n, M, False)
+        gspec = getattr(self, '_cluster_graph_spec', None) if pending is not None else None
+        graph = None
+        if gspec is not None:                      # the stitched list, in the large shape: groups cross tile borders
+            graph = self._enqueue_cluster_graph(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
+                                                pending[0], pending[2], pending[1], n, M, big, gspec, M + 1024, True)
         res = {'index': [big_batch.index[off[i]:off[i + 1]].copy() for i in range(n)]}
         for w in want:
             if w == 'cluster':
@@ -1747,6 +1945,9 @@ class ssnet_base(object):
         if match is not None:
             res['true_cluster'], res['true_clusters'] = self._fetch_clusters(truth, off)
             res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
+        if graph is not None:
+            lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
+            res['graph'] = self._finish_cluster_graph(sess, graph, lists, res, gspec, big, value=lambda: self._resident_value(big_batch))
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

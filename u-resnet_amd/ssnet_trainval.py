@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -85,6 +85,7 @@ class ssnet_trainval(object):
         self._csv = None
         self._objects = None
         self._match = None
+        self._graph = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -181,6 +182,8 @@ class ssnet_trainval(object):
             raise ValueError('ANA_OBJECTS needs ANA_CLUSTER: the object records are reductions over the members of the clusters')
         if cfg.ANA_MATCH and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_MATCH needs ANA_CLUSTER: the match compares the predicted clusters with those of the true classes')
+        if cfg.ANA_GRAPH and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_GRAPH needs ANA_CLUSTER: the interaction groups are components of the graph of the clusters')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -210,6 +213,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._match.write(match_csv_header())
                 self._match.flush()
+        if cfg.ANA_GRAPH and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_GRAPH) or os.path.getsize(cfg.ANA_GRAPH) == 0
+            self._graph = open(cfg.ANA_GRAPH, 'a')
+            if fresh:
+                self._graph.write(graph_csv_header())
+                self._graph.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -230,6 +239,9 @@ class ssnet_trainval(object):
                 self._net.set_cluster_features(True)
             if self._match:                  # default off: never called
                 self._net.set_cluster_matching(True)
+            if self._graph:                  # default off: never called
+                from .clusters import ClusterGraphSpec
+                self._net.set_cluster_graph(ClusterGraphSpec(cfg.GRAPH_GAP))
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -577,6 +589,7 @@ class ssnet_trainval(object):
             self._output.flush()
         self._write_objects(r, entries, vb.offsets, self._net._dims[:-1])
         self._write_match(r, entries)
+        self._write_graph(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -593,6 +606,8 @@ class ssnet_trainval(object):
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
             if 'match' in r:
                 result['match'] = r['match']
+            if 'graph' in r:
+                result['graph'] = r['graph']
         self._advance_main()
         return result
 
@@ -612,6 +627,15 @@ class ssnet_trainval(object):
         for i in range(len(entries)):
             self._match.write(match_csv_row(entries[i], r['match']['events'], i))
         self._match.flush()
+
+    def _write_graph(self, r, entries):
+        """ANA_GRAPH: one CSV row per interaction group of every event of the result ``r``."""
+        if not getattr(self, '_graph', None) or 'graph' not in r:
+            return
+        for i in range(len(entries)):
+            for g in range(int(r['graph'][i]['groups']['rows'].size)):
+                self._graph.write(graph_csv_row(entries[i], g, r['graph'][i]['groups']))
+        self._graph.flush()
 
     def _ana_step_tiled(self, vb, entries, batch_mode):
         """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
@@ -638,6 +662,7 @@ class ssnet_trainval(object):
             self._output.flush()
         self._write_objects(r, entries, vb.offsets, c.ANA_TILE)
         self._write_match(r, entries)
+        self._write_graph(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -655,6 +680,8 @@ class ssnet_trainval(object):
                       'tiles': (r['tiles_run'], r['tiles_total'])}
             if 'match' in r:
                 result['match'] = r['match']
+            if 'graph' in r:
+                result['graph'] = r['graph']
         self._advance_main()
         return result
 
@@ -821,7 +848,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_objects', '_match', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
