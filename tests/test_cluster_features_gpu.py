@@ -42,8 +42,12 @@ def _tables(f):
     return it, rt
 
 
-def _run(lib, off, index, value, cluster, toff, shape, cap):
-    """Four calls of ursn_cluster_features on guarded operands; returns per call (itab, rtab, status) as host arrays."""
+ROUTES = ((0xFF, True), (0x00, True), (None, True), (0xFF, False))
+
+
+def _run(lib, off, index, value, cluster, toff, shape, cap, routes=ROUTES):
+    """Four calls of ursn_cluster_features on guarded operands; returns per call (itab, rtab, status) as host arrays (`routes`:
+    the scratch fill and the URSN_CLFEAT_WAVE route of each call; tests/test_long_lists_gpu.py runs two)."""
     import torch
     n, M = off.size - 1, int(off[-1])
     g_off, g_toff = Guarded(n + 1, torch.int64, off), Guarded(n + 1, torch.int64, toff)
@@ -63,7 +67,7 @@ def _run(lib, off, index, value, cluster, toff, shape, cap):
     d.offsets, d.index, d.cluster, d.table_offsets = g_off.ptr, g_idx.ptr, g_cl.ptr, g_toff.ptr
     d.value = None if g_val is None else g_val.ptr
     results = []
-    for fill, wave in ((0xFF, True), (0x00, True), (None, True), (0xFF, False)):
+    for fill, wave in routes:
         if fill is not None:
             scratch.fill(fill)
         itab, rtab = Guarded((max(cap, 1), I), torch.int64), Guarded((max(cap, 1), R), torch.float64)

@@ -31,7 +31,7 @@ def _untouched(a):
 
 
 def _run(lib, off, index, ids, toff, spatial, gap, value, cls, cap_rows, cap_groups, edge_out_cap, edge_cap, rows, groups, edges,
-         with_edges=True, short_scratch=False):
+         with_edges=True, short_scratch=False, routes=ROUTES):
     """Four calls of ursn_cluster_graph on guarded operands.  The tables hold rows / groups / edges records whatever the caps are, so
     what lies at or beyond a cap can be seen to be untouched.  Returns per call a dict of host arrays."""
     import torch
@@ -58,7 +58,7 @@ def _run(lib, off, index, ids, toff, spatial, gap, value, cls, cap_rows, cap_gro
     inputs = [("offsets", g_off), ("table_offsets", g_toff), ("index", g_index), ("cluster", g_ids), ("scratch", scratch)] + \
         ([] if g_val is None else [("value", g_val)]) + ([] if g_cls is None else [("cls", g_cls)])
     results = []
-    for fill, wave in ROUTES:
+    for fill, wave in routes:
         if fill is not None:
             scratch.fill(fill)
         out = {"rows": Guarded((max(rows, 1), I), torch.int64), "groups": Guarded((max(groups, 1), G), torch.int64),

@@ -34,7 +34,7 @@ def _untouched(a):
     return bool((np.ascontiguousarray(a).view(np.uint8) == 0xFF).all())
 
 
-def _run(lib, off, a, toff_a, b, toff_b, value, cap_a, cap_b, pair_cap, rows_a, rows_b, cells, pairs=True):
+def _run(lib, off, a, toff_a, b, toff_b, value, cap_a, cap_b, pair_cap, rows_a, rows_b, cells, pairs=True, routes=ROUTES):
     """Four calls of ursn_cluster_match on guarded operands.  The tables hold rows_a / rows_b / cells entries whatever the caps are,
     so what lies at or beyond a cap can be seen to be untouched.  Returns per call a dict of host arrays."""
     import torch
@@ -56,7 +56,7 @@ def _run(lib, off, a, toff_a, b, toff_b, value, cap_a, cap_b, pair_cap, rows_a, 
     inputs = [("offsets", g_off), ("table_offsets_a", g_ta), ("table_offsets_b", g_tb), ("cluster_a", g_a), ("cluster_b", g_b),
               ("scratch", scratch)] + ([] if g_val is None else [("value", g_val)])
     results = []
-    for fill, wave in ROUTES:
+    for fill, wave in routes:
         if fill is not None:
             scratch.fill(fill)
         out = {"a_int": Guarded((max(rows_a, 1), I), torch.int64), "a_real": Guarded((max(rows_a, 1), R), torch.float64),

@@ -32,8 +32,12 @@ def _want(off, index, cls, shape, spec):
             "table_offsets": np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)}
 
 
-def _run(lib, off, index, cls, shape, spec, cap=None, table=True):
-    """Three calls of ursn_cluster_voxels on guarded operands; returns the three results as host arrays."""
+FILLS = (0xFF, 0x00, None)
+
+
+def _run(lib, off, index, cls, shape, spec, cap=None, table=True, fills=FILLS):
+    """Three calls of ursn_cluster_voxels on guarded operands; returns the three results as host arrays (`fills`: the scratch fill
+    before each call, None = as the call before left it; tests/test_long_lists_gpu.py runs two)."""
     import torch
     off = np.asarray(off, np.int64)
     index, cls = np.asarray(index, np.int32), np.asarray(cls, np.uint8)
@@ -56,7 +60,7 @@ def _run(lib, off, index, cls, shape, spec, cap=None, table=True):
     conn, _ = spec.axes(len(shape))
     d.connectivity, d.class_mask, d.same_class, d.min_size = conn, spec.class_mask(), int(spec.same_class), spec.min_size
     results = []
-    for fill in (0xFF, 0x00, None):
+    for fill in fills:
         if fill is not None:
             scratch.fill(fill)
         outs = {"cluster": Guarded(max(M, 1), torch.int32), "count": Guarded(n, torch.int32), "status": Guarded(1, torch.int32),
