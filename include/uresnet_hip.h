@@ -891,6 +891,18 @@ int ursn_read_loss_terms(ursn_net* net, float* out2, void* stream);
  *   b3wgrad  {workgroups = slabs written, planes per column, slabs the reduce kernel walks (after the fold), fold group (0: no fold)}
  *   bdwgrad  {workgroups, boxes a workgroup walks, slabs per channel block, boxes}: the last slice is short when boxes % steps != 0
  *   bwgrad   {workgroups, boxes a workgroup walks, slabs per channel block, box voxels}
+ *   tconv    {workgroups of one launch (a channel-blocked layer runs several such launches), planes per z segment, rows of
+ *            statistics partials (forward: one per workgroup), z segments}
+ *   twgrad   {workgroups of one launch, planes per z segment AFTER the plane-pair round-up of the Cout = 8 form, slabs reduced
+ *            afterwards (two per workgroup in the plane-pair form, else one), z segments + 2^32 when the round-up changed the
+ *            segment ursn_pick_zseg had picked (bit 32: the picked segment was odd and there is more than one)}
+ *   tdeconv  (also "tdeconv+pw") {workgroups of one launch, LOW-resolution planes per z segment, rows of statistics partials
+ *            (forward), z segments}
+ *   vwgrad   {workgroups, planes per z segment, slabs reduced afterwards, z segments}
+ *   b0conv   {workgroups, planes per z segment, rows of statistics partials (one per workgroup), z segments}
+ *   b0wgrad  {workgroups, planes per z segment, slabs reduced afterwards, z segments}
+ * In every z-marching family the last segment of a column is short when Z % planes != 0.  The resident-slot count the tiled families
+ * and the persistent box walks divide by is occupancy * CUs of the device; URSN_CU_COUNT=n (1..1024, tests) replaces the device's count.
  * Every other family (their splits have no plan struct, or no switch moves them): returns non-zero, "not reported". */
 int ursn_conv_partition(const ursn_conv_desc* d, int32_t pass, int64_t out[4]);
 

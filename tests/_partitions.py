@@ -2,8 +2,8 @@
 
 The launchers pick their work split (z segments, split-K groups, boxes per workgroup, grid caps) from workgroup counts tuned for 256
 CUs, so the guarded rows of tests/test_op_guards_gpu.py sit on the "too few workgroups" side of every threshold and the bench
-workloads on the other.  Each SET below moves, through switches that already exist, a group of those rows onto the branch a bench
-layer takes by default; tests/test_partitions_host.py proves on a CPU that the branch is taken (ursn_conv_partition, the scratch
+workloads on the other.  Each SET below moves, through the library's switches (two of them test inputs: URSN_CU_COUNT, the CU count
+the slot-count splits divide by, and URSN_B0_MINWG), a group of those rows onto the branch a bench layer takes by default; tests/test_partitions_host.py proves on a CPU that the branch is taken (ursn_conv_partition, the scratch
 queries) and tests/test_partitions_gpu.py runs the guarded checks there.  The switches are read once per process: one child process
 per set.  Plain helper module (no conftest), importable without a GPU."""
 import collections
@@ -50,10 +50,51 @@ REQUIRE = {
     # pconv: the cap holds, the first workgroup takes >= 3 steps of 256 voxels, the last step is short
     "pconv_capped": lambda d, g, ps: g["part"][0] == 2 < d["part"][0] and g["part"][1] >= 3 and 0 < g["part"][3] < 256 and
     (ps != FWD or g["stats"] < d["stats"]),
+    # tconv / twgrad / tdeconv / vwgrad (resident slots = occupancy x URSN_CU_COUNT): one segment of all the planes the kernel
+    # marches (Zm: the low-resolution Z for tdeconv), where the default split has two or more
+    "slots_whole_z": lambda d, g, ps: nz(g) == 1 and g["part"][1] == g["Zm"] and nz(d) >= 2 and d["part"][1] < g["Zm"] and
+    g["part"][0] < d["part"][0] and (ps != FWD or (g["part"][2] == g["part"][0] and g["stats"] < d["stats"])) and
+    (ps != WGRAD or g["wgrad"] <= d["wgrad"]),
+    # ... two or more segments, each longer than the default's, the last one short
+    "long_ragged": lambda d, g, ps: nz(g) >= 2 and g["part"][1] > d["part"][1] and g["Zm"] % g["part"][1] != 0 and
+    (nz(g) - 1) * g["part"][1] < g["Zm"],
+    # ... whose length is odd
+    "long_ragged_odd_last": lambda d, g, ps: REQUIRE["long_ragged"](d, g, ps) and (g["Zm"] % g["part"][1]) % 2 == 1,
+    # twgradz: ursn_pick_zseg picked an odd segment and make_wplan rounded it up to a plane pair (bit 32 of word 3), which the
+    # default split of the row may do too -- at another length; the last segment is short and odd
+    "long_ragged_pair_up": lambda d, g, ps: REQUIRE["long_ragged_odd_last"](d, g, ps) and g["part"][3] >> 32 == 1 and g["part"][1] % 2 == 0 and
+    g["part"][2] == 2 * g["part"][0],
+    # twgradz: an even picked segment, no round-up
+    "long_ragged_no_pair_up": lambda d, g, ps: REQUIRE["long_ragged"](d, g, ps) and g["part"][3] >> 32 == 0,
+    # bconv / bwgrad: a persistent workgroup walks two or more boxes of the default's size (default: one box per workgroup, so its
+    # word 2 is the box count) ...
+    "box_walk": lambda d, g, ps: g["part"][1] >= 2 and d["part"][1] == 1 and g["part"][3] == d["part"][3] and g["part"][0] < d["part"][0] and
+    g["part"][1] * (g["part"][2] - 1) < d["part"][2] <= g["part"][1] * g["part"][2],
+    # ... and the last workgroup's walk is short
+    "box_walk_ragged": lambda d, g, ps: REQUIRE["box_walk"](d, g, ps) and d["part"][2] % g["part"][1] != 0,
+    # ... and the contraction has several chunks (weights re-staged per chunk inside the walk)
+    "box_walk_chunks": lambda d, g, ps: REQUIRE["box_walk"](d, g, ps) and g["chunks"] >= 2,
+    # b0conv / b0wgrad: one segment of all Z planes (default: 16 or fewer)
+    "b0_whole_z": lambda d, g, ps: nz(g) == 1 and g["part"][1] == g["Z"] >= 40 and d["part"][1] <= 16 and nz(d) > 1 and g["part"][0] < d["part"][0] and
+    (ps != FWD or d["stats"] >= g["stats"] >= g["part"][2] * 32 * 8) and (ps != WGRAD or g["wgrad"] <= d["wgrad"]),      # (the query is the larger of this and the 8 -> 8 kernel's)
+    # b0conv / b0wgrad: two segments of 20 planes or more ...
+    "b0_long_segments": lambda d, g, ps: nz(g) == 2 and g["part"][1] >= 20 and d["part"][1] <= 16,
+    # ... the second one short
+    "b0_long_ragged": lambda d, g, ps: REQUIRE["b0_long_segments"](d, g, ps) and g["Z"] % g["part"][1] != 0,
 }
 
+
+def nz(r):
+    """z segments of a report (word 3 without the twgrad round-up bit)"""
+    return r["part"][3] & 0xFFFFFFFF
+
+
+_LONG = ("tconv3d_long", "tconv3d_long_split")
+_LONG_DG = ("tconv3d_long_pw", "tconv3d_long_bs2", "tconv3d_long_vdz")
+
 # the kernel the last launch of a forward / weight-gradient check must have noted under the requirement
-KERNEL = {"dconv_gsplit1": b"dconv", "bd_box256": b"bdconv_bf16<2,8>", "bd_form1": b"bdconv_bf16<4,8>"}
+KERNEL = {"dconv_gsplit1": b"dconv", "bd_box256": b"bdconv_bf16<2,8>", "bd_form1": b"bdconv_bf16<4,8>",
+          "long_ragged_pair_up": b"twgradz<8,8>", "long_ragged_no_pair_up": b"twgradz<8,8>"}
 
 Set = collections.namedtuple("Set", "name env rows extras bench")
 SETS = [
@@ -110,6 +151,44 @@ SETS = [
         [("pconv3d_grid", FWD, "pconv_capped"), ("pconv3d_grid", DGRAD, "pconv_capped")], ("bn", "bn_bf16", "head", "loss_head", "adam"),
         "every level-0 / level-1 layer of cfg1-cfg5: the caps (512 / 1,024 / 4,096 blocks, 1,024 pconv workgroups) are saturated from "
         "2^19 voxels up, every block takes hundreds of trips and the partial buffers hold exactly `cap` rows"),
+    Set("slots_whole_z", {"URSN_CU_COUNT": "1"},
+        [(t, ps, "slots_whole_z") for t in _LONG + ("tconv3d_cblocks", "tconv2d_odd") for ps in (FWD, DGRAD, WGRAD)] +
+        [("tconv3d_long_norm", FWD, "slots_whole_z"), ("tconv3d_long_norm", WGRAD, "slots_whole_z")] +
+        [(t, DGRAD, "slots_whole_z") for t in _LONG_DG + ("tdeconv3d_dgrad_zseg", "tdeconv3d_pw_zseg")] +
+        [("tdeconv3d_zseg", FWD, "slots_whole_z"), ("tdeconv2d_zseg", FWD, "slots_whole_z"), ("vwgrad3d_zseg", WGRAD, "slots_whole_z")], (),
+        "cfg3 (192^3 x 4, fp32) levels 0 and 1: ursn_pick_zseg takes several rounds over 256 x occupancy slots and segments of tens of planes; "
+        "one segment of the whole column is the longest march (the plane ring wraps 10 to 13 times at Z = 37 / 41, twice by default) and "
+        "what a volume of many tiles and few planes gets"),
+    Set("slots_long_ragged", {"URSN_CU_COUNT": "4"},
+        [(t, ps, "long_ragged_odd_last") for t in _LONG for ps in (FWD, DGRAD)] + [(t, DGRAD, "long_ragged_odd_last") for t in _LONG_DG] +
+        [(t, WGRAD, "long_ragged_pair_up") for t in _LONG] +
+        [("tconv2d_odd", FWD, "long_ragged_odd_last"), ("tconv2d_odd", DGRAD, "long_ragged_odd_last"), ("tconv2d_odd", WGRAD, "long_ragged")], (),
+        "cfg3 levels 0 and 1 (192 / 96 planes): several long segments per column with seams between them; 192 and 96 split evenly, "
+        "other volumes leave a short last segment, and twgradz rounds an odd pick up to a plane pair (here 21 -> 22 + 19)"),
+    Set("slots_long_ragged_16", {"URSN_CU_COUNT": "5"},
+        [("tconv3d_long_norm", FWD, "long_ragged_odd_last"), ("tconv3d_long_norm", WGRAD, "long_ragged_odd_last"),
+         ("tconv3d_long", WGRAD, "long_ragged_no_pair_up"), ("tconv3d_long_split", WGRAD, "long_ragged_no_pair_up"),
+         ("tconv2d_odd", WGRAD, "long_ragged")], (),
+        "as slots_long_ragged for the 16 -> 16 kernels (occupancy 2 and 1: another count gives them 14 + 14 + 13), and twgradz on an "
+        "even pick (14), which the round-up leaves alone"),
+    Set("box_walks", {"URSN_CU_COUNT": "2"},
+        [("bsconv_k3s2_lowodd", FWD, "box_walk_ragged")] +
+        [(t, FWD, "box_walk") for t in ("bsconv_k3s2_n2_sc", "bconv_k1s2_n2", "bconv_24_40", "bconv2d_n2", "bconv2d_s2_n2")] +
+        [("bsconv_deconv_odd", DGRAD, "box_walk_ragged"), ("bsconv_deconv_rag_sc", DGRAD, "box_walk_chunks")] +
+        [(t, DGRAD, "box_walk") for t in ("bsconv_deconv_n2_sc", "bcbconv_16_24_cb", "bconv2d_n2", "bconv2d_s2_n2")] +
+        [(t, WGRAD, "box_walk_ragged") for t in ("bconv_k3s2_odd", "bpw_odd", "bcbconv_16_24_cb")] +
+        [("bsconv_deconv_rag_sc", WGRAD, "box_walk_chunks")] +
+        [(t, WGRAD, "box_walk") for t in ("bsconv_deconv_odd", "bconv2d_n2", "bconv2d_deconv", "bconv_24_40")], (),
+        "every bconv / bwgrad layer of cfg5 (256^3 x 4, bf16): a persistent grid of 256 x occupancy workgroups, each walking several boxes "
+        "and re-staging its LDS between them (two to hundreds); the last workgroup's walk is short whenever boxes % per != 0"),
+    Set("b0_whole_z", {"URSN_B0_MINWG": "1"},
+        [(t, ps, "b0_whole_z") for t in ("b0conv_zseg", "b0conv_zseg_odd") for ps in (FWD, WGRAD)], (),
+        "cfg5 conv0 (256^3 x 4): 4,096 tiles >= 2,048, so every workgroup marches the whole 256-plane column"),
+    Set("b0_long_segments", {"URSN_B0_MINWG": "5"},
+        [("b0conv_zseg", FWD, "b0_long_segments"), ("b0conv_zseg", WGRAD, "b0_long_segments"),
+         ("b0conv_zseg_odd", FWD, "b0_long_ragged"), ("b0conv_zseg_odd", WGRAD, "b0_long_ragged")], (),
+        "conv0 of a volume with 1,024 to 2,047 tiles (128^3 x 4 has 1,024): two long segments per column with a seam between them; "
+        "20 + 20 planes, and 21 + 20"),
 ]
 # rows a set names that the default plan already puts on the set's branch (the requirement holds; nothing moves)
 AT_DEFAULT = {("dconv_gsplit1", "dconv3d_rag", FWD): "192 contraction channels are 12 chunks: no split but gsplit 1 is legal, so this row "
@@ -159,13 +238,16 @@ def report(name):
     out = {}
     for tag, ps in rows:
         row = G.BY_TAG[tag]
-        assert row.algo == 0 and row.fams[ps] is not None, (tag, ps)
+        assert row.fams[ps] is not None and (row.algo == 0 or row.fams[ps] in G.FORCED[row.algo]), (tag, ps)
         d = G.build_desc(row, ps)
         part = (ctypes.c_int64 * 4)()
         rc = lib.ursn_conv_partition(ctypes.byref(d), ps, part)
         K = row.co if ps == DGRAD else row.ci
         out["%s/%d" % (tag, ps)] = {
-            "fam": G.plan_name(row, ps, d), "want_fam": row.fams[ps], "part": list(part) if rc == 0 else None, "chunks": K // 32, "Z": row.S[0], "no_stats": bool(row.dtype == G.B and row.tr),
+            # (a forced algo names its family itself: ursn_conv_plan does not see it, ursn_conv_partition follows the dispatcher)
+            "fam": G.plan_name(row, ps, d) if row.algo == 0 else row.fams[ps], "want_fam": row.fams[ps], "part": list(part) if rc == 0 else None,
+            "chunks": K // 32, "Z": row.S[0], "Zm": row.S[0] // 2 if row.stride == 2 and not row.tr and ps == DGRAD else row.S[0],
+            "no_stats": bool(row.dtype == G.B and row.tr),
             "stats": int(lib.ursn_conv_stats_scratch_bytes(ctypes.byref(d))) if ps == FWD else None,
             "wgrad": int(lib.ursn_conv_wgrad_scratch_bytes(ctypes.byref(d))) if ps == WGRAD else None}
     V, big = G.V_BN_BLOCKS, 1 << 24

@@ -74,6 +74,9 @@ SWITCHES = [
     ("bf16", {"URSN_B3_NZSEG": "1", "URSN_B3W_MINWG": "1", "URSN_SLAB_FOLD": "3", "URSN_BDWGRAD_WGS": "5", "URSN_BCONV_MINWG": "1",
               "URSN_BWGRAD_MINWG": "1", "URSN_BCB_MINWG": "1", "URSN_BDCONV_MINWG": "1"}),   # whole-Z segments and columns, a short last fold group (16 slabs in threes), several boxes per bdwgrad workgroup, the larger boxes
     ("fp32", {"URSN_DCONV_MINWG": "1", "URSN_PCONV_GRID": "2"}),   # dconv at gsplit 1 with its own statistics partials (levels 3-4), pconv on two workgroups
+    # the slot-count partitions (URSN_CU_COUNT: the CU count the z split of the fp32 tiled kernels and the persistent box grids divide by)
+    ("fp32", {"URSN_CU_COUNT": "4"}),   # set slots_long_ragged: long z segments with seams in tconv / twgrad / twgradz / tdeconv / vwgrad, sized and carved by the plan
+    ("bf16", {"URSN_CU_COUNT": "2", "URSN_B0_MINWG": "1"}),   # set box_walks: several boxes per bconv / bwgrad workgroup; conv0 and its weight gradient march whole columns
 ]
 
 

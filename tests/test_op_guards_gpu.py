@@ -75,6 +75,13 @@ ROWS = [Row(*r) for r in [
     ("tconv3d_vdz", F, 3, 2, (9, 11, 37), 8, 8, 3, 1, 0, 0, {"vdz": 1, "vdz_relu": 1}, (None, "tconv", None)),
     ("tconv3d_vdz_bs2", F, 3, 2, (21, 8, 40), 8, 8, 3, 1, 0, 0, {"vdz": 1, "vdz_relu": 0, "bs": 2, "bs_relu": 2}, (None, "tconv", None)),
     ("tconv3d_cblocks", F, 3, 2, (24, 48, 48), 32, 16, 3, 1, 0, 3, {}, ("tconv", "tconv", "twgrad")),
+    # a long column, Z = 41: five z segments of 9 planes by default (twgradz: 10 after the plane-pair round-up), and long ragged ones under tests/_partitions.py
+    ("tconv3d_long", F, 3, 2, (41, 9, 33), 8, 8, 3, 1, 0, 0, {}, ("tconv", "tconv", "twgrad")),
+    ("tconv3d_long_split", F, 3, 2, (41, 9, 33), 16, 8, 3, 1, 0, 0, {"split": 8}, ("tconv", "tconv", "twgrad")),
+    ("tconv3d_long_norm", F, 3, 2, (41, 9, 33), 16, 16, 3, 1, 0, 0, {"norm": 1}, ("tconv", None, "twgrad")),
+    ("tconv3d_long_pw", F, 3, 2, (41, 9, 33), 16, 8, 3, 1, 0, 0, {"pw": 1}, (None, "tconv", None)),
+    ("tconv3d_long_bs2", F, 3, 2, (41, 9, 33), 8, 8, 3, 1, 0, 0, {"bs": 2, "bs_relu": 2}, (None, "tconv", None)),
+    ("tconv3d_long_vdz", F, 3, 2, (41, 9, 33), 8, 8, 3, 1, 0, 0, {"vdz": 1, "vdz_relu": 1}, (None, "tconv", None)),
     ("tconv2d_odd", F, 2, 1, (37, 300), 16, 16, 3, 1, 0, 0, {}, ("tconv", "tconv", "twgrad")),
     ("tconv2d_n2", F, 2, 2, (16, 256), 16, 16, 3, 1, 0, 0, {}, ("tconv", "tconv", "twgrad")),
     ("tconv2d_pad5", F, 2, 2, (16, 256), 16, 5, 3, 1, 0, 0, {"out_cs": 8}, ("tconv", "tconv", "twgrad")),
@@ -83,6 +90,7 @@ ROWS = [Row(*r) for r in [
     ("tconv2d_pw", F, 2, 2, (16, 256), 16, 16, 3, 1, 0, 0, {"pw": 1}, (None, "tconv", None)),
     ("vwgrad3d", F, 3, 2, (10, 7, 70), 8, 3, 3, 1, 0, 0, {"out_cs": 4}, (None, None, "vwgrad")),
     ("vwgrad3d_odd", F, 3, 2, (9, 7, 71), 8, 3, 3, 1, 0, 0, {"out_cs": 4}, (None, None, "vwgrad")),
+    ("vwgrad3d_zseg", F, 3, 2, (19, 5, 53), 8, 3, 3, 1, 0, 0, {"out_cs": 4}, (None, None, "vwgrad")),      # two z segments: 10 planes and 9
     ("s2scatter3d_odd", F, 3, 1, (5, 7, 19), 16, 16, 3, 2, 1, 0, {}, ("s2scatter", None, None)),
     ("s2scatter3d_n2", F, 3, 2, (8, 16, 32), 32, 16, 3, 2, 1, 0, {}, ("s2scatter", None, None)),
     ("s2scatter2d_odd", F, 2, 1, (17, 35), 16, 32, 3, 2, 1, 0, {}, ("s2scatter", None, None)),
@@ -92,10 +100,14 @@ ROWS = [Row(*r) for r in [
     ("tdeconv3d_odd", F, 3, 1, (9, 11, 37), 16, 8, 3, 2, 1, 0, {}, ("tdeconv", None, None)),
     ("tdeconv3d_n2", F, 3, 2, (8, 16, 32), 16, 8, 3, 2, 1, 0, {}, ("tdeconv", None, None)),
     ("tdeconv2d_odd", F, 2, 1, (9, 300), 16, 8, 3, 2, 1, 0, {}, ("tdeconv", None, None)),
+    ("tdeconv3d_zseg", F, 3, 2, (13, 9, 19), 16, 8, 3, 2, 1, 0, {}, ("tdeconv", None, None)),      # low-resolution Z >= 12: two z segments (7 + 6 planes), a seam inside the column
+    ("tdeconv2d_zseg", F, 2, 1, (13, 300), 16, 8, 3, 2, 1, 0, {}, ("tdeconv", None, None)),
     ("tdeconv3d_dgrad_rag", F, 3, 1, (18, 22, 74), 8, 16, 3, 2, 0, 0, {}, (None, "tdeconv", None)),
     ("tdeconv3d_dgrad_n2", F, 3, 2, (16, 32, 64), 8, 16, 3, 2, 0, 0, {}, (None, "tdeconv", None)),
+    ("tdeconv3d_dgrad_zseg", F, 3, 1, (26, 18, 38), 8, 16, 3, 2, 0, 0, {}, (None, "tdeconv", None)),      # low-resolution (13, 9, 19): 7 + 6 planes
     ("tdeconv3d_pw", F, 3, 2, (18, 22, 74), 8, 16, 3, 2, 0, 0, {"pw": 1}, (None, "tdeconv+pw", None)),
     ("tdeconv3d_pw_cs24", F, 3, 2, (16, 16, 64), 8, 16, 3, 2, 0, 0, {"pw": 1, "pw_cs": 24}, (None, "tdeconv+pw", None)),
+    ("tdeconv3d_pw_zseg", F, 3, 2, (30, 16, 34), 8, 16, 3, 2, 0, 0, {"pw": 1}, (None, "tdeconv+pw", None)),      # low-resolution (15, 8, 17): 8 + 7 planes
     ("s2conv3d_odd", F, 3, 1, (17, 21, 45), 16, 32, 3, 2, 0, 0, {}, ("s2conv", None, "s2wgrad")),
     ("s2conv3d_n2", F, 3, 2, (16, 32, 64), 8, 16, 3, 2, 0, 0, {}, ("s2conv", None, "s2wgrad")),
     ("s2conv2d_odd", F, 2, 1, (37, 75), 8, 16, 3, 2, 0, 0, {}, ("s2conv", None, "s2wgrad")),
@@ -113,6 +125,7 @@ ROWS = [Row(*r) for r in [
     # ---- bf16 -----------------------------------------------------------------------------------------------------------------
     ("b0conv_odd", B, 3, 2, (9, 21, 37), 1, 8, 3, 1, 0, 0, {}, ("b0conv", None, "b0wgrad")),
     ("b0conv_zseg", B, 3, 1, (40, 18, 34), 1, 8, 3, 1, 0, 0, {}, ("b0conv", None, "b0wgrad")),
+    ("b0conv_zseg_odd", B, 3, 1, (41, 9, 70), 1, 8, 3, 1, 0, 0, {}, ("b0conv", None, "b0wgrad")),      # 11 + 11 + 11 + 8 planes by default; one halving gives 21 + 20
     ("bs2k8_n2", B, 3, 2, (8, 12, 36), 8, 16, 3, 2, 0, 0, {}, ("bs2k8", "bdeconv", "bs2k8w")),
     ("bs2k8_odd", B, 3, 1, (7, 11, 35), 8, 16, 3, 2, 0, 0, {}, ("bs2k8", "bconv", "bs2k8w")),
     ("bs2k8_lowodd", B, 3, 1, (14, 22, 70), 8, 16, 3, 2, 0, 0, {}, ("bs2k8", "bdeconv", "bs2k8w")),

@@ -327,7 +327,8 @@ C0Plan c0_plan(const GatherGeom& g) {
   p.nty = (g.in_d[1] + C0_TY - 1) / C0_TY;
   const int64_t tiles = (int64_t)g.N * p.nty * p.ntx;
   int zseg = Z;
-  while (zseg > 16 && tiles * ((Z + zseg - 1) / zseg) < 2048) zseg = (zseg + 1) / 2;
+  static const int64_t minwg = ursn_env_int("URSN_B0_MINWG", 2048);   // tests: long segments at small shapes
+  while (zseg > 16 && tiles * ((Z + zseg - 1) / zseg) < minwg) zseg = (zseg + 1) / 2;
   p.zseg = zseg;
   p.nzseg = (Z + zseg - 1) / zseg;
   p.grid = (int)(tiles * p.nzseg);
@@ -360,6 +361,14 @@ bool b0conv_ok(const GatherGeom& g) {
 int b0conv_grid_blocks(const GatherGeom& g) { return c0_plan(g).grid; }
 size_t b0conv_pack_elems() { return 3 * 64 * 4 + 8; }
 
+// ursn_conv_partition: {workgroups, planes per z segment, rows of statistics partials (one per workgroup), z segments}
+bool b0conv_partition(const GatherGeom& g, int64_t out[4]) {
+  if (!b0conv_ok(g)) return false;
+  const C0Plan p = c0_plan(g);
+  out[0] = p.grid; out[1] = p.zseg; out[2] = p.grid; out[3] = p.nzseg;
+  return true;
+}
+
 int launch_b0conv(const GatherGeom& g, const float* x, const float* w, int Nw, bf16_t* wpack, bf16_t* out, double* stats_partial,
                   hipStream_t s) {
   URSN_REQUIRE(b0conv_ok(g) && x && w && wpack && out, "bf16 conv0: unsupported geometry");
@@ -388,6 +397,14 @@ bool b0wgrad_ok(const GatherGeom& g) {
   return b0conv_on() && g.K == 8 && (g.out_cs & 7) == 0 && c0_geom_ok(g);
 }
 size_t b0wgrad_scratch_bytes(const GatherGeom& g) { return (size_t)c0_plan(g).grid * 256 * sizeof(float) + 256; }
+
+// ursn_conv_partition: {workgroups, planes per z segment, slabs reduced afterwards, z segments}
+bool b0wgrad_partition(const GatherGeom& g, int64_t out[4]) {
+  if (!b0wgrad_ok(g)) return false;
+  const C0Plan p = c0_plan(g);
+  out[0] = p.grid; out[1] = p.zseg; out[2] = p.grid; out[3] = p.nzseg;
+  return true;
+}
 
 int launch_b0wgrad(const GatherGeom& g, const float* x, const bf16_t* dz, float* dw, int Nw, void* scratch, size_t scratch_bytes,
                    hipStream_t s) {

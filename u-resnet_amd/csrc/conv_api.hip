@@ -686,6 +686,12 @@ bool bdwgrad_partition(const GatherGeom& g, int64_t out[4]);
 bool bconv_partition(const GatherGeom& g, int64_t out[4]);
 bool bwgrad_partition(const GatherGeom& g, int64_t out[4]);
 bool bsconv_partition(const GatherGeom* g, int cnt, int64_t out[4]);
+bool tiled_conv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]);
+bool tiled_wgrad_partition(const ursn_conv_desc& d, int64_t out[4]);
+bool tiled_deconv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]);
+bool valu_wgrad_partition(const ursn_conv_desc& d, int64_t out[4]);
+bool b0conv_partition(const GatherGeom& g, int64_t out[4]);
+bool b0wgrad_partition(const GatherGeom& g, int64_t out[4]);
 
 // The work split the family ursn_conv_plan names takes for this descriptor / pass: host logic only, no device access.
 extern "C" int ursn_conv_partition(const ursn_conv_desc* d0, int32_t pass_, int64_t out[4]) {
@@ -712,9 +718,20 @@ extern "C" int ursn_conv_partition(const ursn_conv_desc* d0, int32_t pass_, int6
     else if (is("b3wgrad")) ok = b3wgrad_partition(g[0], out);
     else if (is("bdwgrad")) ok = bdwgrad_partition(g[0], out);
     else if (is("bwgrad")) ok = bwgrad_partition(g[0], out);
+    else if (is("b0conv")) ok = b0conv_partition(g[0], out);
+    else if (is("b0wgrad")) ok = b0wgrad_partition(g[0], out);
+  } else if (d0->algo == 3 && !d0->vdz_z && !d0->bs_partial && !d0->in_mean && !d0->pw_dy && !d0->in_split) {
+    // a forced tiled family (ursn_conv_plan is blind to it): what conv_dispatch / wgrad_dispatch hand an algo 3 call to
+    if (pass == PASS_WGRAD) { ok = tiled_wgrad_partition(*d0, out); snprintf(name, sizeof(name), "twgrad"); }
+    else if (tiled_deconv_supported(*d0, pass)) { ok = tiled_deconv_partition(*d0, pass, out); snprintf(name, sizeof(name), "tdeconv"); }
+    else { ok = tiled_conv_supported(*d0, pass) && tiled_conv_partition(*d0, pass, out); snprintf(name, sizeof(name), "tconv"); }
   } else {
     if (is("dconv")) ok = deep_conv_partition(*d0, pass, out);
     else if (is("pconv")) ok = pointwise_conv_partition(*d0, pass, out);
+    else if (is("tconv")) ok = tiled_conv_partition(*d0, pass, out);
+    else if (is("twgrad")) ok = tiled_wgrad_partition(*d0, out);
+    else if (is("tdeconv") || is("tdeconv+pw")) ok = tiled_deconv_partition(*d0, pass, out);
+    else if (is("vwgrad")) ok = valu_wgrad_partition(*d0, out);
   }
   if (!ok) {
     ursn_set_error("conv_partition: the partition of family %s is not reported", name);

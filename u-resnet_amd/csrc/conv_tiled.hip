@@ -39,6 +39,8 @@ struct Blocking {
 int ursn_cu_count() {
   static int n = 0;
   if (!n) {
+    const int forced = ursn_env_int("URSN_CU_COUNT", 0);   // tests: the splits of a many-round launch at small shapes
+    if (forced >= 1 && forced <= 1024) return n = forced;
     hipDeviceProp_t pr;
     int dev = 0;
     n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
@@ -159,6 +161,15 @@ int tiled_conv_supported(const ursn_conv_desc& d, ConvPass pass) {
   if (d.bs_partial && !(pass == PASS_DGRAD && p.mode == 3 && p.cout == 8 && (p.cin == 8 || p.cin == 4) && b.nbi == 1 &&
                         (b.nbo == 1 || b.split))) return 0;
   return 1;
+}
+
+// ursn_conv_partition: {workgroups of one launch, planes per z segment, rows of statistics partials (forward), z segments}
+bool tiled_conv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]) {
+  TPlan p;
+  Blocking b;
+  if (!make_plan(d, pass, p, b)) return false;
+  out[0] = p.grid; out[1] = p.zseg; out[2] = pass == PASS_FWD ? p.grid : 0; out[3] = p.nzseg;
+  return true;
 }
 
 int tiled_conv_bs_blocks(const ursn_conv_desc& d) {
@@ -288,7 +299,7 @@ static bool use_wgradz(const ursn_conv_desc& d) {  // Cout == 8: plane-pair kern
   return v && d.cout == 8 && (d.cin == 8 || d.cin == 16);
 }
 
-static bool make_wplan(const ursn_conv_desc& d, TWPlan& p, Blocking& b) {
+static bool make_wplan(const ursn_conv_desc& d, TWPlan& p, Blocking& b, bool* pair_rounded = nullptr) {
   if (ursn_tiled_disabled() && d.algo != 3) return false;
   if (d.transposed || d.k != 3 || d.stride != 1) return false;
   p.mode = d.ndim; p.cin = d.cin; p.cout = (d.cout + 3) & ~3;
@@ -342,7 +353,9 @@ static bool make_wplan(const ursn_conv_desc& d, TWPlan& p, Blocking& b) {
   if (p.lds > 160 * 1024) return false;
   if (d.in_mean && (blocked_shape || (!use_wgradz(d) && use_wgrad4(d, p)))) return false;   // kernels without the staging affine
   ursn_pick_zseg(p.grid, p.Z, occ_limit(vg, p.lds), 8, p.zseg, p.nzseg);
-  if (use_wgradz(d) && (p.zseg & 1) && p.nzseg > 1) { p.zseg += 1; p.nzseg = (p.Z + p.zseg - 1) / p.zseg; }   // plane pairs
+  const bool pair_up = use_wgradz(d) && (p.zseg & 1) && p.nzseg > 1;
+  if (pair_up) { p.zseg += 1; p.nzseg = (p.Z + p.zseg - 1) / p.zseg; }   // plane pairs
+  if (pair_rounded) *pair_rounded = pair_up;
   p.grid *= p.nzseg;
   return true;
 }
@@ -351,6 +364,17 @@ int tiled_wgrad_supported(const ursn_conv_desc& d) {
   TWPlan p;
   Blocking b;
   return make_wplan(d, p, b) ? 1 : 0;
+}
+
+// ursn_conv_partition: {workgroups of one launch, planes per z segment after the plane-pair round-up, slabs reduced afterwards,
+// z segments + 2^32 when the round-up changed the picked segment}
+bool tiled_wgrad_partition(const ursn_conv_desc& d, int64_t out[4]) {
+  TWPlan p;
+  Blocking b;
+  bool pair_rounded = false;
+  if (!make_wplan(d, p, b, &pair_rounded)) return false;
+  out[0] = p.grid; out[1] = p.zseg; out[2] = (int64_t)p.grid * (use_wgradz(d) ? 2 : 1); out[3] = p.nzseg + (pair_rounded ? (int64_t)1 << 32 : 0);
+  return true;
 }
 
 size_t tiled_wgrad_scratch_bytes(const ursn_conv_desc& d) {

@@ -84,6 +84,15 @@ int tiled_deconv_supported(const ursn_conv_desc& d, ConvPass pass) {
   return make_dplan(d, pass, p, b) ? 1 : 0;
 }
 
+// ursn_conv_partition: {workgroups of one launch, low-resolution planes per z segment, rows of statistics partials (forward), z segments}
+bool tiled_deconv_partition(const ursn_conv_desc& d, ConvPass pass, int64_t out[4]) {
+  TDPlan p;
+  DBlocking b;
+  if (!make_dplan(d, pass, p, b)) return false;
+  out[0] = p.grid; out[1] = p.zseg; out[2] = pass == PASS_FWD ? p.grid : 0; out[3] = p.nzseg;
+  return true;
+}
+
 size_t tiled_deconv_stats_scratch_doubles(const ursn_conv_desc& d) {
   TDPlan p;
   DBlocking b;

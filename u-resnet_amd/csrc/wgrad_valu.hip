@@ -186,6 +186,14 @@ size_t valu_wgrad_scratch_bytes(const ursn_conv_desc& d) {
   return vw_plan(d, p) ? (size_t)p.grid * 27 * 24 * sizeof(float) : 0;
 }
 
+// ursn_conv_partition: {workgroups, planes per z segment, slabs reduced afterwards, z segments}
+bool valu_wgrad_partition(const ursn_conv_desc& d, int64_t out[4]) {
+  VWPlan p;
+  if (!vw_plan(d, p)) return false;
+  out[0] = p.grid; out[1] = p.zseg; out[2] = p.grid; out[3] = p.nzseg;
+  return true;
+}
+
 int launch_valu_wgrad(const ursn_conv_desc& d, const float* x, const float* dy, float* dw, void* scratch, size_t scratch_bytes,
                       hipStream_t s) {
   VWPlan p;
