@@ -1198,6 +1198,86 @@ size_t ursn_cluster_graph_scratch_bytes(int32_t n, int64_t m_total, int64_t cap_
 int ursn_cluster_graph(const ursn_cluster_graph_desc* d, const ursn_cluster_graph_out* out, void* scratch, size_t scratch_bytes,
                        void* stream);
 
+/* ---- per-cluster charge profiles along the principal axis (cluster_profile.hip) ---------------------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * The step after the object record: the charge of a cluster segment by segment along its axis (dQ/dx, which end the charge rises
+ * towards, empty segments of a broken track, the kink of the trajectory through the segment centroids).  Input: the lists and ids
+ * ursn_cluster_features read and the two tables it wrote for them.  uresnet_amd/clusters.py (cluster_profile_numpy) states every
+ * field operation by operation; the device gives the same bits.
+ *
+ * Row r with the object record's n, anchor m, axis, t_lo and length has, in fp64 and one rounded operation at a time,
+ *   nb_true = floor(length / step) + 1     nb = min(nb_true, max_bins)     pad = ((double)nb_true * step - length) / 2
+ * segments (bins).  A member's bin is b = min(max(floor((((double)t - t_lo) + pad) / step), 0), nb - 1) with t the object record's
+ * fp32 projection of the member.  Bins are CSR by global row: bin_offsets[r] .. bin_offsets[r + 1].
+ * Bin record, URSN_CLPROF_BI int64:  [0] n   [1] charge = sum of rint((double)value * 2^16) (|value| >= 2^15 or a non-finite value
+ *   adds nothing and sets bit 0 of flags; no value list: 0)   [2..4] d = sum (x - m)   [5] flags.
+ * Bin record, URSN_CLPROF_BR fp64:   [0..2] c = (double)m + (double)d / (double)n   [3] dqdx = ((double)charge / 2^16) / step;
+ *   an empty bin holds +0.0 in all four.
+ * Row record, URSN_CLPROF_RI int64:  [0] bins = nb   [1] filled   [2] gaps (maximal runs of empty bins between filled ones)
+ *   [3] longest_gap   [4] peak_bin (largest charge, lowest among equals)   [5] h = min(end_bins, nb / 2)   [6] head_n, [7] head_charge
+ *   over bins [0, h)   [8] tail_n, [9] tail_charge over bins [nb - h, nb)   [10] direction = sign(tail_charge - head_charge), 0 for
+ *   h == 0: a charge-asymmetry sign and nothing more   [11] flags: bit 0 a bin is flagged, bit 1 nb_true > max_bins (truncated).
+ * Row record, URSN_CLPROF_RR fp64:   [0] path = length of the polyline through the centroids of the filled bins   [1] min_cos = the
+ *   smallest cosine between consecutive polyline segments (1.0 without a pair)   [2] kink_bin = the bin of that pair's middle point
+ *   (-1.0 without one)   [3] head_dqdx, [4] tail_dqdx = ((double)charge / 2^16) / ((double)h * step) (0.0 for h == 0)
+ *   [5] straightness = length / path (1.0 for path == 0).
+ * Bounds with every extent <= 32768 and m_total < 2^31: bin n < 2^31, |d| < 2^46, |charge| <= 2^62, nb <= 65536.
+ *
+ * Method: per row nb; a one-workgroup scan into bin_offsets; the bins below the total cleared; one thread per list entry adds n,
+ * charge and d with 64-bit INTEGER atomic adds at agent scope and ors the flag, nothing else (equal bins of adjacent lanes of a wave
+ * are combined first, then a workgroup's runs in a 256-slot LDS table that falls through to direct atomics when full;
+ * URSN_CLPROF_WAVE=0: one atomic set per entry; same bits); one thread per bin for the fp64 columns; one thread per row for the row
+ * record.  Six launches, enqueues only, never synchronises; the scratch needs no initialisation; every device loop is bounded.
+ *
+ * Rows considered: below min(table_offsets[n], feat_cap, cap_rows, m_total); rows at or beyond it are never written, and bin_offsets
+ * is written for entries 0 .. that count and holds the true counts whatever bin_cap is.  *status is 0, or: bit 0 an id outside its
+ * event's rows, offsets that are not those of the lists, an index outside the volume at an entry with an id, or a length that is no
+ * object record's; bit 1 a row without a member (such entries and rows are skipped, a skipped row has no bins);
+ * URSN_CLPROF_BIN_OVERFLOW: the total exceeds bin_cap -- decided by the arguments alone -- and then only bin_offsets and *status
+ * are defined.  Null, misaligned, out-of-domain and too-small arguments are refused with a message that begins "cluster_profile:"
+ * before any launch. */
+#define URSN_CLPROF_BI 6    /* int64 columns of a bin record */
+#define URSN_CLPROF_BR 4    /* fp64 columns of a bin record */
+#define URSN_CLPROF_RI 12   /* int64 columns of a row record */
+#define URSN_CLPROF_RR 6    /* fp64 columns of a row record */
+#define URSN_CLPROF_BIN_OVERFLOW 256 /* bit of *status */
+
+typedef struct ursn_cluster_prof_desc { /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t reserved;                     /* 0 */
+  int64_t m_total;                      /* list entries, < 2^31 */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] */
+  const float* value;                   /* [m_total], or null: charge = 0 */
+  const int32_t* cluster;               /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets;         /* [n+1] as ursn_cluster_voxels wrote it */
+  const int64_t* itab;                  /* [feat_cap][URSN_CLFEAT_I] as ursn_cluster_features wrote it for these lists */
+  const double* rtab;                   /* [feat_cap][URSN_CLFEAT_R] */
+  int64_t feat_cap;                     /* the cap of those tables */
+  double step;                          /* finite, [0.5, 4096] */
+  int32_t end_bins;                     /* 1..16 */
+  int32_t max_bins;                     /* 1..65536 */
+} ursn_cluster_prof_desc;
+
+typedef struct ursn_cluster_prof_out {  /* DEVICE pointers */
+  int64_t* bin_offsets;                 /* [cap_rows + 1] */
+  int64_t* bin_itab;                    /* [bin_cap][URSN_CLPROF_BI] */
+  double* bin_rtab;                     /* [bin_cap][URSN_CLPROF_BR] */
+  int64_t* row_itab;                    /* [cap_rows][URSN_CLPROF_RI] */
+  double* row_rtab;                     /* [cap_rows][URSN_CLPROF_RR] */
+  int64_t cap_rows;
+  int64_t bin_cap;                      /* [0, 2^31) */
+  int32_t* status;                      /* [1] */
+} ursn_cluster_prof_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535], m_total outside [0, 2^31), cap_rows < 0 or bin_cap
+ * outside [0, 2^31).  Host logic only. */
+size_t ursn_cluster_profile_scratch_bytes(int32_t n, int64_t m_total, int64_t cap_rows, int64_t bin_cap);
+int ursn_cluster_profile(const ursn_cluster_prof_desc* d, const ursn_cluster_prof_out* out, void* scratch, size_t scratch_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,22 @@ class ursn_cluster_graph_out(C.Structure):
                 ("edges", C.c_void_p), ("edge_out_cap", C.c_int64), ("status", C.c_void_p)]
 
 
+CLPROF_BI, CLPROF_BR, CLPROF_RI, CLPROF_RR = 6, 4, 12, 6    # URSN_CLPROF_*: int64 / fp64 columns of the bin and row records
+CLPROF_BIN_OVERFLOW = 256                                   # URSN_CLPROF_BIN_OVERFLOW: bit of *status
+
+
+class ursn_cluster_prof_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("reserved", C.c_int32), ("m_total", C.c_int64),
+                ("offsets", C.c_void_p), ("index", C.c_void_p), ("value", C.c_void_p), ("cluster", C.c_void_p),
+                ("table_offsets", C.c_void_p), ("itab", C.c_void_p), ("rtab", C.c_void_p), ("feat_cap", C.c_int64),
+                ("step", C.c_double), ("end_bins", C.c_int32), ("max_bins", C.c_int32)]
+
+
+class ursn_cluster_prof_out(C.Structure):
+    _fields_ = [("bin_offsets", C.c_void_p), ("bin_itab", C.c_void_p), ("bin_rtab", C.c_void_p), ("row_itab", C.c_void_p),
+                ("row_rtab", C.c_void_p), ("cap_rows", C.c_int64), ("bin_cap", C.c_int64), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -284,6 +300,9 @@ _SIGS = {
     "ursn_cluster_features": (C.c_int, [C.POINTER(ursn_cluster_feat_desc), C.POINTER(ursn_cluster_feat_out), _P, C.c_size_t, _P]),
     "ursn_cluster_match_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_match": (C.c_int, [C.POINTER(ursn_cluster_match_desc), C.POINTER(ursn_cluster_match_out), _P, C.c_size_t, _P]),
+    # cluster_profile.hip (declared last in the header; the order of this table carries no meaning for the library)
+    "ursn_cluster_profile_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
+    "ursn_cluster_profile": (C.c_int, [C.POINTER(ursn_cluster_prof_desc), C.POINTER(ursn_cluster_prof_out), _P, C.c_size_t, _P]),
     "ursn_cluster_graph_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_graph": (C.c_int, [C.POINTER(ursn_cluster_graph_desc), C.POINTER(ursn_cluster_graph_out), _P, C.c_size_t, _P]),
 }

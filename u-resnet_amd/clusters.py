@@ -599,3 +599,190 @@ def cluster_graph_numpy(offsets, index, cluster, table_offsets, spatial, spec=No
     return {'edge_offsets': np.array(edge_offsets, np.int64), 'edges': np.array(table, np.int64).reshape(-1, 6),
             'rows': np.array(rows, np.int64).reshape(-1, 6), 'group_offsets': np.array(group_offsets, np.int64),
             'groups': np.array(groups, np.int64).reshape(-1, 12), 'events': np.array(events, np.int64).reshape(-1, 4), 'group': group}
+
+
+# ---- per-cluster charge profiles along the principal axis (csrc/cluster_profile.hip does it on the device; this is the statement) --
+PROFILE_BIN_INT = ('n', 'charge', 'd0', 'd1', 'd2', 'flags')
+PROFILE_BIN_REAL = ('c0', 'c1', 'c2', 'dqdx')
+PROFILE_ROW_INT = ('bins', 'filled', 'gaps', 'longest_gap', 'peak_bin', 'h', 'head_n', 'head_charge', 'tail_n', 'tail_charge',
+                   'direction', 'flags')
+PROFILE_ROW_REAL = ('path', 'min_cos', 'kink_bin', 'head_dqdx', 'tail_dqdx', 'straightness')
+PROFILE_MIN_STEP, PROFILE_MAX_STEP = 0.5, 4096.0
+PROFILE_MAX_END_BINS = 16
+PROFILE_MAX_BINS = 65536
+
+
+class ClusterProfileSpec(object):
+    """``step``: the segment length along the principal axis in voxels, a finite float in [0.5, 4096]; ``end_bins`` in [1, 16]: the
+    segments at either end whose charge is compared; ``max_bins`` in [1, 65536]: a longer profile is truncated into its last bin."""
+
+    def __init__(self, step=1.0, end_bins=3, max_bins=4096):
+        if type(step) not in (int, float) or not np.isfinite(step) or not PROFILE_MIN_STEP <= step <= PROFILE_MAX_STEP:
+            raise ValueError('ClusterProfileSpec: step = %r, expected a finite float in [%g, %g]'
+                             % (step, PROFILE_MIN_STEP, PROFILE_MAX_STEP))
+        if type(end_bins) is not int or not 1 <= end_bins <= PROFILE_MAX_END_BINS:
+            raise ValueError('ClusterProfileSpec: end_bins = %r, expected an integer in [1, %d]' % (end_bins, PROFILE_MAX_END_BINS))
+        if type(max_bins) is not int or not 1 <= max_bins <= PROFILE_MAX_BINS:
+            raise ValueError('ClusterProfileSpec: max_bins = %r, expected an integer in [1, %d]' % (max_bins, PROFILE_MAX_BINS))
+        self.step, self.end_bins, self.max_bins = float(step), end_bins, max_bins
+
+    def __repr__(self):
+        return 'ClusterProfileSpec(step=%r, end_bins=%r, max_bins=%r)' % (self.step, self.end_bins, self.max_bins)
+
+
+def profile_bin_count(length, step, max_bins):
+    """(nb, nb_true, pad) of a cluster of this ``length``: three fp64 operations, each rounded on its own.  The host sizes the bin
+    table with it, the device follows it."""
+    length, step = np.float64(length), np.float64(step)
+    nb_true = int(np.floor(length / step)) + 1
+    pad = (np.float64(nb_true) * step - length) / np.float64(2.0)
+    return min(nb_true, int(max_bins)), nb_true, pad
+
+
+def cluster_profile_numpy(offsets, index, value, cluster, table_offsets, spatial, spec):
+    """The statement of the per-cluster charge profiles: every cluster's members are sorted into segments of ``spec.step`` voxels
+    along the principal axis of its object record, and each segment (bin) gets a count, a charge and a centroid.  Slow on purpose,
+    in the style of ``cluster_features_numpy``, which it calls first: Python integers, scalar fp64 operations each rounded on its
+    own, one member at a time.  From the object record of row r it takes ``n``, the anchor ``m``, ``axis``, ``t_lo`` and ``length``.
+
+    Segment count, in fp64: ``nb_true`` = floor(length / step) + 1, ``nb`` = min(nb_true, max_bins), ``pad`` = (float64(nb_true) *
+    step - length) / 2 (the slack of the last segment, split evenly between the two ends, so that head and tail are comparable).
+    Segment of a member: t = (axis[0] * (x_0 - m_0) + axis[1] * (x_1 - m_1)) + axis[2] * (x_2 - m_2) in fp64, rounded once to fp32
+    (a zero of either sign counts as +0): the object record's own expression; u = ((float64(t) - float64(t_lo)) + pad) / step;
+    b = min(max(floor(u), 0), nb - 1).
+
+    Bins, CSR by global row (``bin_offsets`` [K_total + 1]).  int64 ``n`` members, ``charge`` = sum of rint(float64(value) * 2^16),
+    ``d`` [3] = sum (x - m), ``flags``: a member with a value that is not finite or with |value| >= 2^15 adds to n and d, adds
+    nothing to charge and sets bit 0 (the object record's rule; no values: charge 0).  fp64 ``c`` [3] = float64(m) + float64(d) /
+    float64(n) and ``dqdx`` = (float64(charge) / 2^16) / step; an empty bin holds +0.0 in all four.
+    Bounds, with every extent <= 32768 and fewer than 2^31 entries: bin n < 2^31, |d| < 2^15 * 2^31 = 2^46, |charge| <= 2^31 *
+    2^31 = 2^62 (any sum over bins of one row obeys the same bound), nb <= 65536.
+
+    Rows.  int64 ``bins`` = nb, ``filled`` bins with n > 0, ``gaps`` maximal runs of empty bins between filled ones and
+    ``longest_gap`` the longest, ``peak_bin`` the bin of the largest charge (lowest among equals), ``h`` = min(end_bins, nb // 2),
+    ``head_n`` / ``head_charge`` over bins [0, h), ``tail_n`` / ``tail_charge`` over bins [nb - h, nb), ``direction`` = +1 if
+    tail_charge > head_charge, -1 if smaller, 0 if equal or h == 0, ``flags``: bit 0 some bin is flagged, bit 1 nb_true > max_bins
+    (truncated into the last bin).  ``direction`` is the sign of a charge asymmetry between the two ends and NOTHING MORE: whether
+    the particle stopped there is the consumer's judgement.
+    fp64 ``path`` = the length of the polyline through the centroids of the filled bins in ascending order, each segment
+    sqrt((dx * dx + dy * dy) + dz * dz), added one after another; ``min_cos`` = the smallest dot / (s1 * s2) over consecutive
+    pairs of polyline segments (dot in the same association; a pair with s1 * s2 == 0 is skipped; 1.0 without a pair) and
+    ``kink_bin`` the bin of that pair's middle point as a float (lowest among equals, -1.0 without one); ``head_dqdx`` =
+    (float64(head_charge) / 2^16) / (float64(h) * step), ``tail_dqdx`` likewise (both 0.0 when h == 0); ``straightness`` = length
+    / path, or 1.0 when path == 0.
+
+    An id outside its event's rows, a row without a member and an index outside the volume at an entry with an id raise, as in
+    ``cluster_features_numpy``.  Returns ``{'objects': that function's dict, 'bin_offsets': int64 [K + 1], 'bins': {name: [B]},
+    'rows': {name: [K]}}`` with the names of PROFILE_BIN_INT / _REAL and PROFILE_ROW_INT / _REAL."""
+    if not isinstance(spec, ClusterProfileSpec):
+        raise ValueError('cluster_profile_numpy: spec = %r, expected a ClusterProfileSpec' % (spec,))
+    spatial = tuple(int(s) for s in spatial)
+    off = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    index = np.asarray(index, np.int64).reshape(-1)
+    cluster = np.asarray(cluster, np.int64).reshape(-1)
+    vox = int(np.prod(spatial, dtype=np.int64)) if spatial else 0
+    for e in range(min(len(off), len(toff)) - 1):
+        for j in range(off[e], min(off[e + 1], cluster.size, index.size)):
+            if cluster[j] >= 0 and not cluster[j] < toff[e + 1] - toff[e]:
+                raise ValueError('cluster_profile_numpy: entry %d has id %d, its event has %d clusters'
+                                 % (j, cluster[j], toff[e + 1] - toff[e]))
+            if cluster[j] >= 0 and not 0 <= index[j] < vox:
+                raise ValueError('cluster_profile_numpy: entry %d has index %d outside the volume' % (j, index[j]))
+    f = cluster_features_numpy(offsets, index, value, cluster, table_offsets, spatial)
+    if value is not None:
+        value = np.asarray(value, np.float32).reshape(-1)
+    ndim, K = len(spatial), toff[-1]
+    step, two16 = np.float64(spec.step), np.float64(2.0 ** FIX_SHIFT)
+    members = [[] for _ in range(K)]
+    for e in range(len(off) - 1):
+        for j in range(off[e], off[e + 1]):
+            if cluster[j] >= 0:
+                members[toff[e] + int(cluster[j])].append(j)
+    bin_offsets = [0]
+    bins = {k: [] for k in PROFILE_BIN_INT + PROFILE_BIN_REAL}
+    rows = {k: [] for k in PROFILE_ROW_INT + PROFILE_ROW_REAL}
+    zero, one = np.float64(0.0), np.float64(1.0)
+    for r in range(K):
+        m, ax = [int(x) for x in f['m'][r]], [np.float64(x) for x in f['axis'][r]]
+        t_lo, length = np.float64(f['t_lo'][r]), np.float64(f['length'][r])
+        nb, nb_true, pad = profile_bin_count(length, step, spec.max_bins)
+        bn, bq, bf = [0] * nb, [0] * nb, [0] * nb
+        bd = [[0, 0, 0] for _ in range(nb)]
+        for j in members[r]:
+            c = np.unravel_index(int(index[j]), spatial)
+            x = [int(c[a]) if a < ndim else 0 for a in range(3)]
+            t = (ax[0] * np.float64(x[0] - m[0]) + ax[1] * np.float64(x[1] - m[1])) + ax[2] * np.float64(x[2] - m[2])
+            t = np.float32(t)
+            if t == np.float32(0.0):
+                t = np.float32(0.0)
+            u = ((np.float64(t) - t_lo) + pad) / step
+            b = min(max(int(np.floor(u)), 0), nb - 1)
+            bn[b] += 1
+            for a in range(3):
+                bd[b][a] += x[a] - m[a]
+            if value is not None:
+                val = np.float64(value[j])
+                if not np.isfinite(val) or abs(val) >= FIX_LIMIT:
+                    bf[b] |= 1
+                else:
+                    bq[b] += int(np.rint(val * two16))
+        cents = []
+        for b in range(nb):
+            assert bn[b] < 2 ** 31 and all(abs(v) < 2 ** 46 for v in bd[b]) and abs(bq[b]) <= 2 ** 62
+            if bn[b] > 0:
+                c = [np.float64(m[a]) + np.float64(bd[b][a]) / np.float64(bn[b]) for a in range(3)]
+                dq = (np.float64(bq[b]) / two16) / step
+                cents.append((b, c))
+            else:
+                c, dq = [zero, zero, zero], zero
+            for k, v in zip(PROFILE_BIN_INT, (bn[b], bq[b], bd[b][0], bd[b][1], bd[b][2], bf[b])):
+                bins[k].append(v)
+            for k, v in zip(PROFILE_BIN_REAL, (c[0], c[1], c[2], dq)):
+                bins[k].append(v)
+        bin_offsets.append(bin_offsets[-1] + nb)
+        filled = len(cents)
+        gaps = longest = run = 0
+        seen = False
+        for b in range(nb):
+            if bn[b] > 0:
+                if seen and run > 0:
+                    gaps, longest = gaps + 1, max(longest, run)
+                seen, run = True, 0
+            else:
+                run += 1
+        peak = 0
+        for b in range(1, nb):
+            if bq[b] > bq[peak]:
+                peak = b
+        h = min(spec.end_bins, nb // 2)
+        head_n, head_q = sum(bn[:h]), sum(bq[:h])
+        tail_n, tail_q = sum(bn[nb - h:nb]), sum(bq[nb - h:nb])
+        direction = 0 if h == 0 else (1 if tail_q > head_q else -1 if tail_q < head_q else 0)
+        flags = (1 if any(bf) else 0) | (2 if nb_true > spec.max_bins else 0)
+        path, best, kink = zero, None, np.float64(-1.0)
+        prev = None                                               # the segment before: (dx, dy, dz, s)
+        for k in range(1, len(cents)):
+            d = [cents[k][1][a] - cents[k - 1][1][a] for a in range(3)]
+            s = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+            path = path + s
+            if prev is not None:
+                den = prev[3] * s
+                if den != zero:
+                    cos = ((prev[0] * d[0] + prev[1] * d[1]) + prev[2] * d[2]) / den
+                    if best is None or cos < best:
+                        best, kink = cos, np.float64(cents[k - 1][0])
+            prev = (d[0], d[1], d[2], s)
+        if h > 0:
+            head_dqdx = (np.float64(head_q) / two16) / (np.float64(h) * step)
+            tail_dqdx = (np.float64(tail_q) / two16) / (np.float64(h) * step)
+        else:
+            head_dqdx = tail_dqdx = zero
+        straight = length / path if path != zero else one
+        for k, v in zip(PROFILE_ROW_INT, (nb, filled, gaps, longest, peak, h, head_n, head_q, tail_n, tail_q, direction, flags)):
+            rows[k].append(v)
+        for k, v in zip(PROFILE_ROW_REAL, (path, one if best is None else best, kink, head_dqdx, tail_dqdx, straight)):
+            rows[k].append(v)
+    out_bins = {k: np.array(bins[k], np.int64 if k in PROFILE_BIN_INT else np.float64).reshape(-1) for k in bins}
+    out_rows = {k: np.array(rows[k], np.int64 if k in PROFILE_ROW_INT else np.float64).reshape(-1) for k in rows}
+    return {'objects': f, 'bin_offsets': np.array(bin_offsets, np.int64), 'bins': out_bins, 'rows': out_rows}

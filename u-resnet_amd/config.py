@@ -171,6 +171,15 @@ class ssnet_config(object):
     # ignored with TRAIN, like every ANA_* key.  GRAPH_GAP = 1, 2 or 3
     ANA_GRAPH = ''
     GRAPH_GAP = 1
+    # ANA_PROFILES '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per cluster: the row record of its charge profile along
+    # the principal axis (ssnet_base.set_cluster_profiles; clusters.cluster_profile_numpy holds the definition): entry, id, the
+    # twelve row integers (bins, filled, gaps, longest gap, peak bin, end bins, count and fixed-point charge at the head and the
+    # tail, the sign of their charge asymmetry, flags) and the six row reals (path, smallest cosine, its bin, dQ/dx at the head and
+    # the tail, straightness).  '' = off.  Refused without ANA_CLUSTER; ignored with TRAIN, like every ANA_* key.  PROFILE_STEP =
+    # the segment length in voxels, a float in [0.5, 4096]; PROFILE_END_BINS = 1 .. 16 segments at either end
+    ANA_PROFILES = ''
+    PROFILE_STEP = 1.0
+    PROFILE_END_BINS = 3
 
     def __init__(self):
         pass
@@ -281,6 +290,12 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'GRAPH_GAP' and not 1 <= value <= 3:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'PROFILE_STEP' and not 0.5 <= value <= 4096.0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'PROFILE_END_BINS' and not 1 <= value <= 16:
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             setattr(self, key, value)

@@ -206,6 +206,20 @@ def objects_csv_header():
     return ','.join(cols) + '\n'
 
 
+def profiles_csv_header():
+    """The header line of the ANA_PROFILES file: one row per cluster."""
+    from .clusters import PROFILE_ROW_INT, PROFILE_ROW_REAL
+    return ','.join(('entry', 'cluster') + PROFILE_ROW_INT + PROFILE_ROW_REAL) + '\n'
+
+
+def profiles_csv_row(entry, k, rows):
+    """Cluster ``k`` of one event's profile ``rows`` record (a dict of columns) as a CSV row: the twelve integers, then the six
+    reals by ``repr`` (which reads back to the same bits)."""
+    from .clusters import PROFILE_ROW_INT, PROFILE_ROW_REAL
+    return ','.join(['%d' % entry, '%d' % k] + ['%d' % int(rows[name][k]) for name in PROFILE_ROW_INT] +
+                    [repr(float(rows[name][k])) for name in PROFILE_ROW_REAL]) + '\n'
+
+
 def match_csv_header():
     """The header line of the ANA_MATCH file: one row per event."""
     from .clusters import MATCH_EVENT_INT, MATCH_EVENT_REAL
@@ -1095,6 +1109,13 @@ class ssnet_base(object):
         objects = None
         if pending is not None and getattr(self, '_cluster_features_on', False):   # behind the cluster passes, same lists
             objects = self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+        pspec = getattr(self, '_cluster_profile_spec', None) if pending is not None else None
+        prof = None
+        if pspec is not None:                      # behind the object records, which run for it in any case
+            prof_objects = objects if objects is not None else \
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+            prof = self._enqueue_cluster_profile(sess, d_offsets, d_index, self._fed_value, pending, prof_objects, self._dims[:-1],
+                                                 pspec, self._profile_bin_cap(M, pspec))
         truth = match = None
         if matching:                               # the TRUE classes under the same spec, then the match of the two id arrays
             buf, at, nbytes = self._fed_label
@@ -1124,6 +1145,9 @@ class ssnet_base(object):
             res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
         if graph is not None:
             res['graph'] = self._finish_cluster_graph(sess, graph, voxels, res, gspec, self._dims[:-1])
+        if prof is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, res['clusters'])
+            res['profiles'] = self._finish_cluster_profile(sess, prof, records, voxels, res, pspec, self._dims[:-1])
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1347,6 +1371,160 @@ class ssnet_base(object):
         d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
         objects = self._enqueue_cluster_features(sess, d_off, d_index, d_value, (d_cluster, None, d_toff, M, n, M), shape)
         return self._fetch_cluster_features(objects, tables)
+
+    # ------------------------------------------------------------------------------------------
+    # per-cluster charge profiles along the principal axis (definition and numpy statement: clusters.cluster_profile_numpy, device
+    # passes: csrc/cluster_profile.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_profiles(self, spec):
+        """A ``clusters.ClusterProfileSpec``: while one is set, and a cluster spec is set, and ``'cluster'`` is wanted,
+        ``inference_voxel_scores`` and ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_profile`` behind the cluster passes
+        and the object records (which run for it whether or not ``set_cluster_features`` is on; tiled: on the stitched list in the
+        large shape), and the result gains ``profiles``: per event what ``cluster_profiles`` returns.  The row count is not known
+        on the host there, so the bin table is sized from the list length alone: ``int(M * (1.75 / step + 1)) + 1`` bins -- a
+        connected cluster of n members is at most sqrt(3) (n - 1) long (1.75 covers the fp32 rounding of the two end projections),
+        so it has at most 1.75 (n - 1) / step + 1 bins.  Ids that are not connected clusters can exceed it; the device then reports
+        the overflow and the result is made again by ``cluster_profiles`` on the returned ids, which sizes the table exactly.
+        None switches it off.  The legal members of ``want`` do not change; never called, the results have the keys they had."""
+        from .clusters import ClusterProfileSpec
+        if spec is not None and not isinstance(spec, ClusterProfileSpec):
+            raise ValueError('set_cluster_profiles: spec = %r, expected a clusters.ClusterProfileSpec or None' % (spec,))
+        self._cluster_profile_spec = spec
+
+    @staticmethod
+    def _profile_bin_cap(M, spec):
+        """Bins enough for every connected cluster of a list of ``M`` entries (``set_cluster_profiles`` has the reasoning)."""
+        return min(int(M * (1.75 / spec.step + 1.0)) + 1, 2 ** 31 - 1)
+
+    def _enqueue_cluster_profile(self, sess, d_offsets, d_index, d_value, pending, objects, shape, spec, bin_cap):
+        """``ursn_cluster_profile`` behind ``_enqueue_cluster_features`` (whose tables stay on the device); enqueues only."""
+        import torch
+        lib = _lib.load()
+        ints, _, toff, _, n, M = pending
+        itab, rtab, _ = objects
+        shape = [int(s) for s in shape]
+        cap_rows, bin_cap = M, int(bin_cap)
+        need = int(lib.ursn_cluster_profile_scratch_bytes(n, M, cap_rows, bin_cap))
+        if need == 0:
+            raise ValueError('cluster_profiles: %d events with %d list entries and %d bins are out of domain' % (n, M, bin_cap))
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=self._device)
+        boff = torch.empty(cap_rows + 1, dtype=torch.int64, device=self._device)
+        bi = torch.empty((max(bin_cap, 1), _lib.CLPROF_BI), dtype=torch.int64, device=self._device)
+        br = torch.empty((max(bin_cap, 1), _lib.CLPROF_BR), dtype=torch.float64, device=self._device)
+        ri = torch.empty((max(cap_rows, 1), _lib.CLPROF_RI), dtype=torch.int64, device=self._device)
+        rr = torch.empty((max(cap_rows, 1), _lib.CLPROF_RR), dtype=torch.float64, device=self._device)
+        status = torch.empty(1, dtype=torch.int32, device=self._device)
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_prof_desc()
+        d.ndim, d.n, d.m_total = len(shape), n, M
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.value, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ptr(d_value), ints.data_ptr(), \
+            toff.data_ptr()
+        d.itab, d.rtab, d.feat_cap = itab.data_ptr(), rtab.data_ptr(), M
+        d.step, d.end_bins, d.max_bins = spec.step, spec.end_bins, spec.max_bins
+        o = _lib.ursn_cluster_prof_out()
+        o.bin_offsets, o.bin_itab, o.bin_rtab, o.row_itab, o.row_rtab = boff.data_ptr(), bi.data_ptr(), br.data_ptr(), \
+            ri.data_ptr(), rr.data_ptr()
+        o.cap_rows, o.bin_cap, o.status = cap_rows, bin_cap, status.data_ptr()
+        _lib.check(lib.ursn_cluster_profile(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, boff, bi, br, ri, rr, status, itab, rtab):
+            t.record_stream(cur)
+        return boff, bi, br, ri, rr, status, bin_cap
+
+    @staticmethod
+    def _fetch_cluster_profile(prof, objects):
+        """The profile tables as per-event dicts (``objects``: what ``_fetch_cluster_features`` returned for the same rows), or None
+        when the bin table was too small."""
+        from .clusters import PROFILE_BIN_INT, PROFILE_BIN_REAL, PROFILE_ROW_INT, PROFILE_ROW_REAL
+        boff, bi, br, ri, rr, status, bin_cap = prof
+        code = int(status.cpu().numpy()[0])
+        if code & _lib.CLPROF_BIN_OVERFLOW:
+            return None
+        if code != 0:
+            raise _lib.UrsnError('cluster_profile: the ids, table offsets, lists and object records disagree (status %d)' % code)
+        counts = [int(o['n'].shape[0]) for o in objects]
+        total = int(sum(counts))
+        off = boff[:total + 1].cpu().numpy()
+        B = int(off[-1])
+        assert off[0] == 0 and B <= bin_cap, 'cluster_profile: %d bins, %d in the table' % (B, bin_cap)
+        bi, br, ri, rr = bi[:B].cpu().numpy(), br[:B].cpu().numpy(), ri[:total].cpu().numpy(), rr[:total].cpu().numpy()
+        res, at = [], 0
+        for o, k in zip(objects, counts):
+            lo, hi = int(off[at]), int(off[at + k])
+            bins = {name: bi[lo:hi, c].copy() for c, name in enumerate(PROFILE_BIN_INT)}
+            bins.update({name: br[lo:hi, c].copy() for c, name in enumerate(PROFILE_BIN_REAL)})
+            rows = {name: ri[at:at + k, c].copy() for c, name in enumerate(PROFILE_ROW_INT)}
+            rows.update({name: rr[at:at + k, c].copy() for c, name in enumerate(PROFILE_ROW_REAL)})
+            res.append({'objects': o, 'rows': rows, 'bins': bins, 'bin_offsets': off[at:at + k + 1] - off[at]})
+            at += k
+        return res
+
+    def _finish_cluster_profile(self, sess, prof, objects, voxels_or_lists, res, spec, shape, value=None):
+        """The profiles enqueued with a voxel-score call, or -- the bin table was too small -- ``cluster_profiles`` on the
+        returned ids."""
+        got = self._fetch_cluster_profile(prof, objects)
+        if got is None:
+            got = self.cluster_profiles(sess, voxels_or_lists, value() if callable(value) else value, res, spec, shape=shape)
+        return got
+
+    def cluster_profiles(self, sess, voxels_or_lists, value, clusters, spec, shape=None):
+        """Charge profiles of clusters already made: ``voxels_or_lists``, ``value``, ``clusters`` and ``shape`` as
+        ``cluster_features`` takes them, ``spec`` a ``clusters.ClusterProfileSpec``.  Runs the object records, reads their
+        ``length`` back, sizes the bin table exactly from it (``clusters.profile_bin_count``: the fp64 expression the device
+        evaluates) and runs the profile.  Returns per event a dict: ``objects`` (as ``cluster_features``), ``rows`` (named columns
+        ``clusters.PROFILE_ROW_INT`` / ``PROFILE_ROW_REAL``, one row per cluster), ``bins`` (``PROFILE_BIN_INT`` /
+        ``PROFILE_BIN_REAL``, one row per bin) and ``bin_offsets`` [K_i + 1], event-local: the bins of cluster k are
+        ``bin_offsets[k] .. bin_offsets[k + 1]``.  ``rows['direction']`` is the sign of the charge asymmetry between the two ends
+        and nothing more."""
+        import torch
+        from .clusters import ClusterProfileSpec
+        if not isinstance(spec, ClusterProfileSpec):
+            raise ValueError('cluster_profiles: spec = %r, expected a clusters.ClusterProfileSpec' % (spec,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_profiles: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = voxels_or_lists.value
+        elif isinstance(voxels_or_lists, _DeviceVoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = self._resident_value(voxels_or_lists)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_profiles: %d events outside [1, 65535]' % n)
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_profiles: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids]) if n else np.zeros(0, np.int32)
+        if cluster.size != M or index.size != M or (value is not None and value.size != M):
+            raise ValueError('cluster_profiles: %d list entries, %d indices, %d ids, %s values'
+                             % (M, index.size, cluster.size, 'no' if value is None else value.size))
+        toff = np.concatenate([[0], np.cumsum([int(t['first'].size) for t in tables])]).astype(np.int64)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        d_off, d_index, d_toff = up(off, np.int64), up(index, np.int32), up(toff, np.int64)
+        d_cluster = up(cluster if M else np.zeros(1, np.int32), np.int32)
+        d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
+        pending = (d_cluster, None, d_toff, M, n, M)
+        dev_objects = self._enqueue_cluster_features(sess, d_off, d_index, d_value, pending, shape)
+        objects = self._fetch_cluster_features(dev_objects, tables)
+        from .clusters import profile_bin_count
+        bin_cap = sum(profile_bin_count(length, spec.step, spec.max_bins)[0] for o in objects for length in o['length'])
+        prof = self._enqueue_cluster_profile(sess, d_off, d_index, d_value, pending, dev_objects, shape, spec, bin_cap)
+        got = self._fetch_cluster_profile(prof, objects)
+        assert got is not None, 'cluster_profile: %d bins sized from the returned lengths were not enough' % bin_cap
+        return got
 
     # ------------------------------------------------------------------------------------------
     # cluster matching (definition and numpy statement: clusters.cluster_match_numpy, device passes: csrc/cluster_match.hip)
@@ -1920,6 +2098,14 @@ class ssnet_base(object):
         if pending is not None and getattr(self, '_cluster_features_on', False):   # the stitched list, in the large shape
             objects = self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'],
                                                      big_batch.ptr['value'], pending, big)
+        pspec = getattr(self, '_cluster_profile_spec', None) if pending is not None else None
+        prof = None
+        if pspec is not None:                      # the stitched list, in the large shape, behind the object records
+            prof_objects = objects if objects is not None else \
+                self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
+                                               pending, big)
+            prof = self._enqueue_cluster_profile(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
+                                                 pending, prof_objects, big, pspec, self._profile_bin_cap(M, pspec))
         truth = match = None
         if matching:                               # the large batch's own labels under the same spec, then the match
             at = big_batch.ptr['label'] - big_batch.dev.data_ptr()
@@ -1948,6 +2134,11 @@ class ssnet_base(object):
         if graph is not None:
             lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
             res['graph'] = self._finish_cluster_graph(sess, graph, lists, res, gspec, big, value=lambda: self._resident_value(big_batch))
+        if prof is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, res['clusters'])
+            lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
+            res['profiles'] = self._finish_cluster_profile(sess, prof, records, lists, res, pspec, big,
+                                                           value=lambda: self._resident_value(big_batch))
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, profiles_csv_header, profiles_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -86,6 +86,7 @@ class ssnet_trainval(object):
         self._objects = None
         self._match = None
         self._graph = None
+        self._profiles = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -184,6 +185,8 @@ class ssnet_trainval(object):
             raise ValueError('ANA_MATCH needs ANA_CLUSTER: the match compares the predicted clusters with those of the true classes')
         if cfg.ANA_GRAPH and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_GRAPH needs ANA_CLUSTER: the interaction groups are components of the graph of the clusters')
+        if cfg.ANA_PROFILES and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_PROFILES needs ANA_CLUSTER: the charge profiles run along the axes of the clusters')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -219,6 +222,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._graph.write(graph_csv_header())
                 self._graph.flush()
+        if cfg.ANA_PROFILES and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_PROFILES) or os.path.getsize(cfg.ANA_PROFILES) == 0
+            self._profiles = open(cfg.ANA_PROFILES, 'a')
+            if fresh:
+                self._profiles.write(profiles_csv_header())
+                self._profiles.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -242,6 +251,9 @@ class ssnet_trainval(object):
             if self._graph:                  # default off: never called
                 from .clusters import ClusterGraphSpec
                 self._net.set_cluster_graph(ClusterGraphSpec(cfg.GRAPH_GAP))
+            if self._profiles:               # default off: never called
+                from .clusters import ClusterProfileSpec
+                self._net.set_cluster_profiles(ClusterProfileSpec(cfg.PROFILE_STEP, cfg.PROFILE_END_BINS))
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -590,6 +602,7 @@ class ssnet_trainval(object):
         self._write_objects(r, entries, vb.offsets, self._net._dims[:-1])
         self._write_match(r, entries)
         self._write_graph(r, entries)
+        self._write_profiles(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -603,6 +616,8 @@ class ssnet_trainval(object):
                         ev['objects'] = r['objects'][i]
                     if 'match' in r:
                         ev['true_cluster'], ev['true_clusters'] = r['true_cluster'][i], r['true_clusters'][i]
+                    if 'profiles' in r:
+                        ev['profiles'] = r['profiles'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
             if 'match' in r:
                 result['match'] = r['match']
@@ -637,6 +652,16 @@ class ssnet_trainval(object):
                 self._graph.write(graph_csv_row(entries[i], g, r['graph'][i]['groups']))
         self._graph.flush()
 
+    def _write_profiles(self, r, entries):
+        """ANA_PROFILES: one CSV row per cluster of every event of the result ``r``."""
+        if not getattr(self, '_profiles', None) or 'profiles' not in r:
+            return
+        for i in range(len(entries)):
+            rows = r['profiles'][i]['rows']
+            for k in range(int(rows['bins'].size)):
+                self._profiles.write(profiles_csv_row(entries[i], k, rows))
+        self._profiles.flush()
+
     def _ana_step_tiled(self, vb, entries, batch_mode):
         """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
         (``inference_tiled_voxel_scores``).  Records and the interactive result are those of ``_ana_step_voxel_scores`` with
@@ -663,6 +688,7 @@ class ssnet_trainval(object):
         self._write_objects(r, entries, vb.offsets, c.ANA_TILE)
         self._write_match(r, entries)
         self._write_graph(r, entries)
+        self._write_profiles(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -676,6 +702,8 @@ class ssnet_trainval(object):
                         ev['objects'] = r['objects'][i]
                     if 'match' in r:
                         ev['true_cluster'], ev['true_clusters'] = r['true_cluster'][i], r['true_clusters'][i]
+                    if 'profiles' in r:
+                        ev['profiles'] = r['profiles'][i]
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
             if 'match' in r:
@@ -848,7 +876,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
