@@ -1278,6 +1278,113 @@ size_t ursn_cluster_profile_scratch_bytes(int32_t n, int64_t m_total, int64_t ca
 int ursn_cluster_profile(const ursn_cluster_prof_desc* d, const ursn_cluster_prof_out* out, void* scratch, size_t scratch_bytes,
                          void* stream);
 
+/* ---- vertex candidates: where the end points of the object records meet (cluster_vertex.hip) ----------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
+ * The step from objects to interactions: which ends meet at one point, how many objects leave it and at what angles, which objects
+ * pass it with their body (a T-junction), and which vertex an object starts and stops at.  Input: the lists and ids
+ * ursn_cluster_features read, the two tables it wrote for them, optionally the cluster table's cls.  uresnet_amd/clusters.py
+ * (cluster_vertices_numpy) states every field operation by operation; the device gives the same bits.
+ *
+ * A global row r is ELIGIBLE when its object record has n >= min_size and, with class_mask != 0, bit cls[r] of class_mask is set.  An
+ * eligible row has END POINTS at the list positions end_lo and end_hi of its object record (one when the two are equal), with the KEY
+ * 2 r + side (side 0 = end_lo) and the DIRECTION u = +axis at the lo end, -axis at the hi end (it points from the end into the row).
+ * Coordinates x[0..2] are the row-major coordinates of index[j] in `spatial` (2-D: x[2] = 0); two entries are IN REACH when their
+ * coordinates differ by at most `radius` on every axis (decided on coordinates: never across a row end, a plane end or an event
+ * boundary).  Two end points of one event and of DIFFERENT rows in reach of each other are linked; a VERTEX is a connected component
+ * of end points under links, numbered per event in the order of its lowest key: vertex_offsets[n + 1].
+ * For every end point p of vertex v and every entry j of the same event with an id in reach of p (j = p included), the pair (p, j)
+ * counts towards the INCIDENCE (v, row of j).  Incidence record, URSN_CLVTX_IN int64, CSR by global vertex (inc_offsets[v] ..
+ * inc_offsets[v + 1], ascending row):
+ *   [0] row   event-local      [1] kind   bit 0 / bit 1: set by the pair (p, p) alone according to p's side, so the set of the row's
+ *   own ends inside v; 0 = the row passes v with its body, 3 = both of its ends are in v      [2] near   the number of such pairs
+ *   [3] dist2, [4] pos   the squared Euclidean distance and the list position of j of the pair smallest in (dist2, position of j)
+ * Vertex record, URSN_CLVTX_VI int64:
+ *   [0] ends   [1] rows = incidences   [2] bodies = incidences of kind 0   [3] near summed over the incidences
+ *   [4] n, [5] charge   the object records' n and fixed-point charge summed over the incident rows
+ *   [6..8] s = the sum of the end-point coordinates   [9..11] lo, [12..14] hi   their box   [15] first_pos = the list position of the
+ *   lowest-key end point   [16] class mask of the incident rows (0 without cls) | flags << 32; flag bit 0: more than 16 ends, the
+ *   cosines use the first 16; flag bit 1: an incident row with length == 0
+ * Vertex record, URSN_CLVTX_VR fp64:
+ *   [0..2] c = (double)s / (double)ends   [3] min_cos, [4] max_cos over the pairs i < k of the first min(ends, 16) end directions in
+ *   ascending key order, cos = (u_i[0] * u_k[0] + u_i[1] * u_k[1]) + u_i[2] * u_k[2]; both +0.0 with fewer than two ends
+ * The record does not decide what the vertex is: two ends with min_cos near -1 and no body are what a broken track looks like, and
+ * whether it is one is the consumer's judgement.
+ * Per row: row_vertex int32 [2] = the event-local vertex of the lo and the hi end; -1, -1 for a row that is not eligible; both equal
+ * for a single end point.  Event record, URSN_CLVTX_EV int64: [0] vertices   [1] junctions (ends >= 2 or bodies >= 1)   [2] free (the
+ * others)   [3] primary = the vertex largest in (rows, n), the lowest id among equals; -1 without a vertex.
+ *
+ * Bounds with every extent <= 32768, m_total < 2^30 and K rows: a vertex has at most 2 K end points with at most 7^3 = 343 entries in
+ * reach each, so near < 2 K * 343 < 2^41; the incident rows of a vertex are distinct rows of one event, so n < 2^31 and
+ * |charge| <= 2^62; |s| < 2^15 * 2^32 = 2^47; dist2 <= 27.  The packed words fit: vertex << 32 | row with vertex < 2 K < 2^31 and
+ * row < 2^30; dist2 << 32 | position with position < 2^30; rows << 32 | n with rows < 2^30 and n < 2^31, below 2^63.  m_total is
+ * bounded by 2^30, not 2^31, so that every key 2 r + side is an int32.
+ *
+ * Method: twelve launches (cluster_vertex.hip lists them).  The walk from an end point visits the (2 radius + 1)^2 rows of the volume
+ * around it, one lower-bound binary search (<= 32 halvings) and at most 2 radius + 1 consecutive entries each, no dense map: one
+ * wave64 per end point, one lane per row.  Links are a union-find over the keys with 32-bit atomicMin to the lower root; one
+ * workgroup scans the root flags, so a vertex's number is the count of roots before its own.  Incidences are counted in an
+ * open-addressing table in the scratch, a power of two >= 2 inc_cap + 2 slots keyed vertex << 32 | row: 64-bit compare-and-swap
+ * claims, 64-bit INTEGER atomic adds and ors at agent scope, ONE packed 64-bit atomic minimum for (dist2, pos); equal keys of adjacent
+ * lanes are combined first, then a workgroup's runs in a 256-slot LDS table that falls through to direct insertions when full
+ * (URSN_CLVTX_WAVE=0: one thread per end point, one insertion per pair; same bits).  A slot pass spreads each incidence onto its
+ * vertex; scan, drop, rank by row give the list; one thread per vertex computes every fp64 value in the order above under
+ * contract(off); a packed 64-bit atomic maximum and one minimum find the primary.  No float atomics.  Enqueues only, never
+ * synchronises; the scratch needs no initialisation; every device loop is bounded; the same arguments give the same bits.
+ *
+ * Rows considered: below min(table_offsets[n], feat_cap, m_total).  *status is 0, or: bit 0 an id outside [-1, K_e) or offsets that
+ * are not those of the lists, bit 1 a row without a member, bit 2 an index outside the volume at an entry with an id, bit 3 a bounded loop
+ * ran out, bit 4 a cls >= 32, bit 5 an end position that is not a member of its row, bit 6 table_offsets[n] > feat_cap (such an entry
+ * or row is skipped; every entry with an id and every row is checked, whether or not a walk meets it, and the bits are the same
+ * whenever the arguments are); URSN_CLVTX_INC_OVERFLOW: more than inc_cap distinct incidences exist -- decided by the arguments alone -- and
+ * then only vertex_offsets and *status are defined and nothing else is written.  Vertices, incidences and rows at or beyond
+ * cap_vertices / inc_out_cap / cap_rows are never written; everything below them is complete whatever the caps are; vertex_offsets
+ * and inc_offsets (entries 0 .. min(V, cap_vertices)) hold the true counts.  m_total = 0 or no clusters still writes *status, the
+ * offsets and the event records.  Null, misaligned, out-of-domain and too-small arguments are refused with a message that begins
+ * "cluster_vertices:" before any launch. */
+#define URSN_CLVTX_VI 17    /* int64 columns of a vertex record */
+#define URSN_CLVTX_VR 5     /* fp64 columns of a vertex record */
+#define URSN_CLVTX_IN 5     /* int64 columns of an incidence record */
+#define URSN_CLVTX_EV 4     /* int64 columns of an event record */
+#define URSN_CLVTX_INC_OVERFLOW 256 /* bit of *status */
+
+typedef struct ursn_cluster_vtx_desc {  /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t radius;                       /* 1..3 */
+  int64_t m_total;                      /* list entries, < 2^30 */
+  int64_t inc_cap;                      /* distinct incidences the scratch has room for, [0, 2^30) */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] strictly increasing per event */
+  const int32_t* cluster;               /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets;         /* [n+1] as ursn_cluster_voxels wrote it */
+  const int64_t* itab;                  /* [feat_cap][URSN_CLFEAT_I] as ursn_cluster_features wrote it for these lists */
+  const double* rtab;                   /* [feat_cap][URSN_CLFEAT_R] */
+  int64_t feat_cap;                     /* the cap of those tables */
+  const uint8_t* cls;                   /* [K_total] the cluster table's cls, or null: every class mask is 0 */
+  int32_t min_size;                     /* >= 1 */
+  uint32_t class_mask;                  /* 0: rows of every class are eligible; else bit cls[r] decides, and cls must be given */
+} ursn_cluster_vtx_desc;
+
+typedef struct ursn_cluster_vtx_out {   /* DEVICE pointers */
+  int64_t* vertex_offsets;              /* [n+1] */
+  int64_t* vtx_itab;                    /* [cap_vertices][URSN_CLVTX_VI] */
+  double* vtx_rtab;                     /* [cap_vertices][URSN_CLVTX_VR] */
+  int64_t cap_vertices;
+  int64_t* inc_offsets;                 /* [cap_vertices + 1] */
+  int64_t* incidence;                   /* [inc_out_cap][URSN_CLVTX_IN] */
+  int64_t inc_out_cap;
+  int32_t* row_vertex;                  /* [cap_rows][2] */
+  int64_t cap_rows;
+  int64_t* event;                       /* [n][URSN_CLVTX_EV] */
+  int32_t* status;                      /* [1] */
+} ursn_cluster_vtx_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535] or m_total / inc_cap outside [0, 2^30).  Host logic only. */
+size_t ursn_cluster_vertices_scratch_bytes(int32_t n, int64_t m_total, int64_t inc_cap);
+int ursn_cluster_vertices(const ursn_cluster_vtx_desc* d, const ursn_cluster_vtx_out* out, void* scratch, size_t scratch_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,23 @@ class ursn_cluster_prof_out(C.Structure):
                 ("row_rtab", C.c_void_p), ("cap_rows", C.c_int64), ("bin_cap", C.c_int64), ("status", C.c_void_p)]
 
 
+CLVTX_VI, CLVTX_VR, CLVTX_IN, CLVTX_EV = 17, 5, 5, 4        # URSN_CLVTX_*: columns of the vertex, incidence and event records
+CLVTX_INC_OVERFLOW = 256                                    # URSN_CLVTX_INC_OVERFLOW: bit of *status
+
+
+class ursn_cluster_vtx_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("radius", C.c_int32), ("m_total", C.c_int64),
+                ("inc_cap", C.c_int64), ("offsets", C.c_void_p), ("index", C.c_void_p), ("cluster", C.c_void_p),
+                ("table_offsets", C.c_void_p), ("itab", C.c_void_p), ("rtab", C.c_void_p), ("feat_cap", C.c_int64),
+                ("cls", C.c_void_p), ("min_size", C.c_int32), ("class_mask", C.c_uint32)]
+
+
+class ursn_cluster_vtx_out(C.Structure):
+    _fields_ = [("vertex_offsets", C.c_void_p), ("vtx_itab", C.c_void_p), ("vtx_rtab", C.c_void_p), ("cap_vertices", C.c_int64),
+                ("inc_offsets", C.c_void_p), ("incidence", C.c_void_p), ("inc_out_cap", C.c_int64), ("row_vertex", C.c_void_p),
+                ("cap_rows", C.c_int64), ("event", C.c_void_p), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -300,9 +317,12 @@ _SIGS = {
     "ursn_cluster_features": (C.c_int, [C.POINTER(ursn_cluster_feat_desc), C.POINTER(ursn_cluster_feat_out), _P, C.c_size_t, _P]),
     "ursn_cluster_match_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_match": (C.c_int, [C.POINTER(ursn_cluster_match_desc), C.POINTER(ursn_cluster_match_out), _P, C.c_size_t, _P]),
-    # cluster_profile.hip (declared last in the header; the order of this table carries no meaning for the library)
+    # cluster_profile.hip (the order of this table carries no meaning for the library)
     "ursn_cluster_profile_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_profile": (C.c_int, [C.POINTER(ursn_cluster_prof_desc), C.POINTER(ursn_cluster_prof_out), _P, C.c_size_t, _P]),
+    # cluster_vertex.hip (declared last in the header; an existing test pins the graph's two as the last of this table)
+    "ursn_cluster_vertices_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "ursn_cluster_vertices": (C.c_int, [C.POINTER(ursn_cluster_vtx_desc), C.POINTER(ursn_cluster_vtx_out), _P, C.c_size_t, _P]),
     "ursn_cluster_graph_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_graph": (C.c_int, [C.POINTER(ursn_cluster_graph_desc), C.POINTER(ursn_cluster_graph_out), _P, C.c_size_t, _P]),
 }

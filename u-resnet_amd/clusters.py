@@ -786,3 +786,256 @@ def cluster_profile_numpy(offsets, index, value, cluster, table_offsets, spatial
     out_bins = {k: np.array(bins[k], np.int64 if k in PROFILE_BIN_INT else np.float64).reshape(-1) for k in bins}
     out_rows = {k: np.array(rows[k], np.int64 if k in PROFILE_ROW_INT else np.float64).reshape(-1) for k in rows}
     return {'objects': f, 'bin_offsets': np.array(bin_offsets, np.int64), 'bins': out_bins, 'rows': out_rows}
+
+
+# ---- vertex candidates: where cluster end points meet (csrc/cluster_vertex.hip does it on the device; this is the statement) ------
+VERTEX_INT = ('ends', 'rows', 'bodies', 'near', 'n', 'charge', 's0', 's1', 's2', 'lo0', 'lo1', 'lo2', 'hi0', 'hi1', 'hi2', 'first_pos',
+              'mask_flags')
+VERTEX_REAL = ('c0', 'c1', 'c2', 'min_cos', 'max_cos')
+VERTEX_INCIDENCE = ('row', 'kind', 'near', 'dist2', 'pos')
+VERTEX_EVENT = ('vertices', 'junctions', 'free', 'primary')
+VERTEX_MAX_RADIUS = 3
+VERTEX_MAX_DIRECTIONS = 16
+
+
+class ClusterVertexSpec(object):
+    """``radius`` in [1, 3]: two end points, or an end point and an entry, are near when their coordinates differ by at most
+    ``radius`` on every axis; ``min_size`` >= 1: clusters with fewer members have no end points; ``classes`` None = clusters of
+    every class, else distinct class numbers in [0, 32): only clusters of these classes have end points (needs the table's cls)."""
+
+    def __init__(self, radius=2, min_size=3, classes=None):
+        if type(radius) is not int or not 1 <= radius <= VERTEX_MAX_RADIUS:
+            raise ValueError('ClusterVertexSpec: radius = %r, expected an integer in [1, %d]' % (radius, VERTEX_MAX_RADIUS))
+        if type(min_size) is not int or not 1 <= min_size < 2 ** 31:
+            raise ValueError('ClusterVertexSpec: min_size = %r, expected an integer >= 1' % (min_size,))
+        if classes is not None:
+            given = classes
+            try:
+                classes = tuple(classes)
+            except TypeError:
+                classes = ()
+            if not classes or any(type(c) is not int or not 0 <= c < 32 for c in classes) or len(set(classes)) != len(classes):
+                raise ValueError('ClusterVertexSpec: classes = %r, expected None or distinct integers in [0, 32)' % (given,))
+        self.radius, self.min_size, self.classes = radius, min_size, classes
+
+    def class_mask(self):
+        """Bit k set = clusters of class k have end points; 0 = every class."""
+        m = 0
+        for c in self.classes or ():
+            m |= 1 << c
+        return m
+
+    def __repr__(self):
+        return 'ClusterVertexSpec(radius=%r, min_size=%r, classes=%r)' % (self.radius, self.min_size, self.classes)
+
+
+def cluster_vertices_numpy(offsets, index, value, cluster, table_offsets, spatial, spec, cls=None):
+    """The statement of the vertex candidates of concatenated per-event lists: which cluster end points meet at one point, how many
+    objects leave that point and at what angles, and which clusters pass it with their body.  Slow on purpose, in the style of
+    ``cluster_features_numpy``, which it calls first (its result is returned under ``objects``): Python integers, scalar fp64
+    operations each rounded on its own, one entry at a time.
+
+    END POINTS.  A global row r is ELIGIBLE when its object record has n >= ``spec.min_size`` and, with ``spec.classes``,
+    ``cls[r]`` is one of them.  An eligible row has end points at the list positions ``end_lo[r]`` and ``end_hi[r]`` of its object
+    record -- one end point when the two are equal.  The KEY of an end point is 2 r + side, side 0 for end_lo and 1 for end_hi (a
+    single end point has side 0); its DIRECTION is u = +axis[r] at the lo end and -axis[r] (unary minus) at the hi end: it points
+    from the end into its cluster.  Coordinates are ``np.unravel_index(index, spatial)`` with x[2] = 0 in 2-D; NEAR means a
+    difference of at most ``spec.radius`` on every axis (Chebyshev distance, decided on coordinates, never on indices: never across
+    a row end, a plane end or an event boundary).
+
+    VERTICES.  Two end points of one event and of DIFFERENT rows are linked when they are near.  A vertex is a connected component
+    of end points under links (a lone end point is a vertex with ends = 1); vertices are numbered per event in the order of their
+    lowest key, ``vertex_offsets`` [n + 1].
+
+    INCIDENCES.  For every end point p of vertex v and every entry j of the same event with ``cluster[j] >= 0`` near p (j = p
+    included) the pair (p, j) counts towards the incidence (v, row of j).  VERTEX_INCIDENCE: ``row`` (event-local); ``kind`` bit
+    0 / bit 1 set by the pair (p, p) alone according to p's side -- the set of that row's own ends inside v, 0 = the row passes v
+    with its body, 3 = both of its ends are in v; ``near`` the number of such pairs; ``dist2`` / ``pos`` the squared Euclidean
+    distance and the list position of j of the pair smallest in (dist2, position of j), dist2 <= 27.  Stored CSR by global vertex,
+    ascending row, ``inc_offsets`` [V + 1].
+
+    VERTEX_INT: ``ends``; ``rows`` its incidences; ``bodies`` those of kind 0; ``near`` summed over them; ``n`` / ``charge`` the
+    object records' n and fixed-point charge summed over the incident rows; ``s0..2`` the sum of the end-point coordinates;
+    ``lo0..2`` / ``hi0..2`` their box; ``first_pos`` the list position of the lowest-key end point; ``mask_flags`` = the class mask
+    of the incident rows (bit ``cls``; 0 without ``cls``) | flags << 32, flag bit 0: more than 16 ends, the cosines use the first 16;
+    flag bit 1: an incident row with length == 0.  VERTEX_REAL: ``c0..2`` = float64(s[a]) / float64(ends); ``min_cos`` / ``max_cos``
+    over the pairs i < k of the first min(ends, 16) end directions in ascending key order, cos = (u_i[0] * u_k[0] + u_i[1] *
+    u_k[1]) + u_i[2] * u_k[2], the first pair's value kept unless a later one is strictly smaller / larger; both +0.0 with fewer
+    than two ends.
+
+    What the record does NOT decide: two ends with min_cos near -1 and no body are what a track broken in two looks like, three
+    ends at right angles what an interaction looks like, one end on a body what a delta ray or a decay looks like -- which of them
+    it is, is the consumer's judgement.  Nothing here orders the incidences into parent and child, and ``rows['direction']`` of the
+    charge profile says nothing more than it did.
+
+    Per row ``row_vertex`` int32 [K, 2]: the event-local vertex of the lo and the hi end, -1 for a row that is not eligible, both
+    equal for a single end point.  VERTEX_EVENT: ``vertices``; ``junctions`` (ends >= 2 or bodies >= 1); ``free`` (the others);
+    ``primary`` the vertex largest in (rows, n), the lowest id among equals, -1 without a vertex.
+
+    Bounds, with every extent <= 32768, fewer than 2^30 entries (so that every key is an int32) and K rows: a vertex has at most 2 K
+    end points, each with at most
+    7^3 = 343 near entries, so near < 2 K * 343 < 2^41; the incident rows of a vertex are distinct rows of one event, so n < 2^31
+    and |charge| <= 2^62; |s| < 2^15 * 2^32 = 2^47; dist2 <= 27.
+
+    An id outside its event's rows, a row without a member, an index outside the volume at an entry with an id, an end position
+    that is not a member of its row and a cls >= 32 raise ValueError.  Returns a dict: ``objects``; ``vertex_offsets`` int64
+    [n + 1]; ``vertices`` {name: [V]} over VERTEX_INT (int64) and VERTEX_REAL (float64); ``inc_offsets`` int64 [V + 1];
+    ``incidence`` int64 [I, 5]; ``row_vertex`` int32 [K, 2]; ``events`` int64 [n, 4]."""
+    if not isinstance(spec, ClusterVertexSpec):
+        raise ValueError('cluster_vertices_numpy: spec = %r, expected a ClusterVertexSpec' % (spec,))
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or any(not 1 <= s <= MAX_EXTENT for s in spatial):
+        raise ValueError('cluster_vertices_numpy: spatial = %r, expected 2 or 3 extents in [1, %d]' % (spatial, MAX_EXTENT))
+    off = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    idx = [int(x) for x in np.asarray(index).reshape(-1)]
+    ids = [int(x) for x in np.asarray(cluster).reshape(-1)]
+    nev, m, ndim, g = len(off) - 1, len(idx), len(spatial), spec.radius
+    if nev < 1 or len(toff) != nev + 1 or len(ids) != m or off[0] != 0 or off[-1] != m or toff[0] != 0 \
+            or any(off[e + 1] < off[e] or toff[e + 1] < toff[e] for e in range(nev)):
+        raise ValueError('cluster_vertices_numpy: offsets, table offsets and the lists disagree')
+    K = toff[-1]
+    if cls is not None:
+        cls = [int(c) for c in np.asarray(cls).reshape(-1)]
+        if len(cls) != K or any(not 0 <= c < 32 for c in cls):
+            raise ValueError('cluster_vertices_numpy: cls must hold %d classes in [0, 32)' % K)
+    if spec.classes is not None and cls is None:
+        raise ValueError('cluster_vertices_numpy: spec.classes = %r needs the cluster table\'s cls' % (spec.classes,))
+    vox = 1
+    for s in spatial:
+        vox *= s
+    coords, where = [None] * m, [dict() for _ in range(nev)]
+    for e in range(nev):
+        for j in range(off[e], off[e + 1]):
+            if ids[j] < 0:
+                continue
+            if not ids[j] < toff[e + 1] - toff[e]:
+                raise ValueError('cluster_vertices_numpy: entry %d has id %d, its event has %d clusters' % (j, ids[j], toff[e + 1] - toff[e]))
+            if not 0 <= idx[j] < vox:
+                raise ValueError('cluster_vertices_numpy: entry %d has index %d outside the volume %r' % (j, idx[j], spatial))
+            x = tuple(int(c) for c in np.unravel_index(idx[j], spatial))
+            coords[j] = x + (0,) * (3 - ndim)
+            where[e][coords[j]] = j
+    f = cluster_features_numpy(offsets, index, value, cluster, table_offsets, spatial)    # raises on a row without a member
+    event_of = [e for e in range(nev) for _ in range(toff[e + 1] - toff[e])]
+    mask = spec.class_mask()
+    ends = {}                                             # key -> list position
+    for r in range(K):
+        if int(f['n'][r]) < spec.min_size or (mask and not (mask >> cls[r]) & 1):
+            continue
+        e = event_of[r]
+        for side, p in ((0, int(f['end_lo'][r])), (1, int(f['end_hi'][r]))):
+            if not off[e] <= p < off[e + 1] or ids[p] != r - toff[e]:
+                raise ValueError('cluster_vertices_numpy: the end position %d of row %d is not a member of it' % (p, r))
+            if side == 0 or p != int(f['end_lo'][r]):
+                ends[2 * r + side] = p
+    key_at = {p: k for k, p in ends.items()}              # a position is the end of one row only
+    steps = [tuple(d[a] - g if a < ndim else 0 for a in range(3)) for d in np.ndindex(*([2 * g + 1] * ndim))]
+
+    entry_event = [e for e in range(nev) for _ in range(off[e], off[e + 1])]
+
+    def near(p):
+        """(position, dist2) of every entry with an id near the entry at position p, itself included."""
+        for d in steps:
+            q = where[entry_event[p]].get(tuple(coords[p][a] + d[a] for a in range(3)))
+            if q is not None:
+                yield q, d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+
+    parent = {k: k for k in ends}
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for k in sorted(ends):
+        for q, _ in near(ends[k]):
+            other = key_at.get(q)
+            if other is None or other >> 1 == k >> 1:
+                continue
+            a, b = find(k), find(other)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    vertex_of, vertex_offsets, members = {}, [0], []      # members[v]: the keys of global vertex v, ascending
+    for e in range(nev):
+        for k in sorted(ends):
+            if event_of[k >> 1] != e:
+                continue
+            root = find(k)
+            if root == k:
+                vertex_of[k] = len(members)
+                members.append([])
+            vertex_of[k] = vertex_of[root]                # a root is the lowest key of its vertex: it came first
+            members[vertex_of[k]].append(k)
+        vertex_offsets.append(len(members))
+    V = len(members)
+    row_vertex = np.full((K, 2), -1, np.int32)
+    for k, v in vertex_of.items():
+        r, local = k >> 1, v - vertex_offsets[event_of[k >> 1]]
+        row_vertex[r][k & 1] = local
+        if int(f['end_lo'][r]) == int(f['end_hi'][r]):
+            row_vertex[r][1] = local
+    vert = {name: [] for name in VERTEX_INT + VERTEX_REAL}
+    inc_offsets, incidence = [0], []
+    events = [[vertex_offsets[e + 1] - vertex_offsets[e], 0, 0, -1] for e in range(nev)]
+    best = [None] * nev
+    zero = np.float64(0.0)
+    for v in range(V):
+        e = event_of[members[v][0] >> 1]
+        cells = {}                                        # global row -> [kind, near, (dist2, pos)]
+        for k in members[v]:
+            p = ends[k]
+            for q, d2 in near(p):
+                cell = cells.setdefault(toff[e] + ids[q], [0, 0, None])
+                cell[1] += 1
+                if q == p:
+                    cell[0] |= 1 << (k & 1)
+                if cell[2] is None or (d2, q) < cell[2]:
+                    cell[2] = (d2, q)
+        n_sum = q_sum = near_sum = bodies = cmask = flags = 0
+        for r in sorted(cells):
+            kind, cnt, (d2, pos) = cells[r]
+            assert d2 <= 27 and cnt < 2 * max(K, 1) * 343
+            incidence.append([r - toff[e], kind, cnt, d2, pos])
+            near_sum, bodies = near_sum + cnt, bodies + (1 if kind == 0 else 0)
+            n_sum, q_sum = n_sum + int(f['n'][r]), q_sum + int(f['charge'][r])
+            if cls is not None:
+                cmask |= 1 << cls[r]
+            if f['length'][r] == zero:
+                flags |= 2
+        inc_offsets.append(len(incidence))
+        xs = [coords[ends[k]] for k in members[v]]
+        s = [sum(x[a] for x in xs) for a in range(3)]
+        assert n_sum < 2 ** 31 and abs(q_sum) <= 2 ** 62 and all(abs(t) < 2 ** 47 for t in s)
+        if len(members[v]) > VERTEX_MAX_DIRECTIONS:
+            flags |= 1
+        us = []
+        for k in members[v][:VERTEX_MAX_DIRECTIONS]:
+            ax = [np.float64(t) for t in f['axis'][k >> 1]]
+            us.append(ax if k & 1 == 0 else [-t for t in ax])
+        lo_cos = hi_cos = None
+        for i in range(len(us)):
+            for k in range(i + 1, len(us)):
+                cos = (us[i][0] * us[k][0] + us[i][1] * us[k][1]) + us[i][2] * us[k][2]
+                if lo_cos is None:
+                    lo_cos = hi_cos = cos
+                if cos < lo_cos:
+                    lo_cos = cos
+                if cos > hi_cos:
+                    hi_cos = cos
+        fe = np.float64(len(xs))
+        ints = [len(xs), len(cells), bodies, near_sum, n_sum, q_sum] + s + [min(x[a] for x in xs) for a in range(3)] + \
+            [max(x[a] for x in xs) for a in range(3)] + [ends[members[v][0]], cmask | flags << 32]
+        reals = [np.float64(s[a]) / fe for a in range(3)] + [zero if lo_cos is None else lo_cos, zero if hi_cos is None else hi_cos]
+        for name, val in zip(VERTEX_INT + VERTEX_REAL, ints + reals):
+            vert[name].append(val)
+        junction = len(xs) >= 2 or bodies >= 1
+        events[e][1] += 1 if junction else 0
+        events[e][2] += 0 if junction else 1
+        if best[e] is None or (len(cells), n_sum) > best[e]:          # ascending id: a strict comparison keeps the lowest
+            best[e], events[e][3] = (len(cells), n_sum), v - vertex_offsets[e]
+    vertices = {k: np.array(vert[k], np.int64 if k in VERTEX_INT else np.float64).reshape(-1) for k in vert}
+    return {'objects': f, 'vertex_offsets': np.array(vertex_offsets, np.int64), 'vertices': vertices,
+            'inc_offsets': np.array(inc_offsets, np.int64), 'incidence': np.array(incidence, np.int64).reshape(-1, 5),
+            'row_vertex': row_vertex, 'events': np.array(events, np.int64).reshape(-1, 4)}

@@ -180,6 +180,17 @@ class ssnet_config(object):
     ANA_PROFILES = ''
     PROFILE_STEP = 1.0
     PROFILE_END_BINS = 3
+    # ANA_VERTICES '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per vertex candidate: a point where end points of the
+    # clusters' object records meet within VERTEX_RADIUS voxels (ssnet_base.set_cluster_vertices; clusters.cluster_vertices_numpy
+    # holds the definition): entry, vertex, the seventeen vertex integers (ends, incident rows, bodies passing by, near entries,
+    # entries and fixed-point charge of the incident rows, sum and box of the end-point coordinates, first end position, class mask
+    # | flags << 32) and the five reals (centroid, smallest and largest cosine between the end directions).  '' = off.  Refused
+    # without ANA_CLUSTER; ignored with TRAIN, like every ANA_* key.  VERTEX_RADIUS = 1, 2 or 3; VERTEX_MIN_SIZE = smaller clusters
+    # have no end points; VERTEX_CLASSES = the classes whose clusters have end points, [] = all
+    ANA_VERTICES = ''
+    VERTEX_RADIUS = 2
+    VERTEX_MIN_SIZE = 3
+    VERTEX_CLASSES = []
 
     def __init__(self):
         pass
@@ -290,6 +301,15 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'GRAPH_GAP' and not 1 <= value <= 3:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'VERTEX_RADIUS' and not 1 <= value <= 3:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'VERTEX_MIN_SIZE' and value < 1:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'VERTEX_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'PROFILE_STEP' and not 0.5 <= value <= 4096.0:

@@ -220,6 +220,20 @@ def profiles_csv_row(entry, k, rows):
                     [repr(float(rows[name][k])) for name in PROFILE_ROW_REAL]) + '\n'
 
 
+def vertices_csv_header():
+    """The header line of the ANA_VERTICES file: one row per vertex."""
+    from .clusters import VERTEX_INT, VERTEX_REAL
+    return ','.join(('entry', 'vertex') + VERTEX_INT + VERTEX_REAL) + '\n'
+
+
+def vertices_csv_row(entry, k, vertices):
+    """Vertex ``k`` of one event's ``vertices`` record (a dict of columns) as a CSV row: the integers, then the reals by ``repr``
+    (which reads back to the same bits)."""
+    from .clusters import VERTEX_INT, VERTEX_REAL
+    return ','.join(['%d' % entry, '%d' % k] + ['%d' % int(vertices[name][k]) for name in VERTEX_INT] +
+                    [repr(float(vertices[name][k])) for name in VERTEX_REAL]) + '\n'
+
+
 def match_csv_header():
     """The header line of the ANA_MATCH file: one row per event."""
     from .clusters import MATCH_EVENT_INT, MATCH_EVENT_REAL
@@ -1116,6 +1130,13 @@ class ssnet_base(object):
                 self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
             prof = self._enqueue_cluster_profile(sess, d_offsets, d_index, self._fed_value, pending, prof_objects, self._dims[:-1],
                                                  pspec, self._profile_bin_cap(M, pspec))
+        vspec = getattr(self, '_cluster_vertex_spec', None) if pending is not None else None
+        vtx = None
+        if vspec is not None:                      # behind the object records, which run for it in any case
+            vtx_objects = objects if objects is not None else prof_objects if pspec is not None else \
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+            vtx = self._enqueue_cluster_vertices(sess, d_offsets, d_index, pending, vtx_objects, pending[1], self._dims[:-1], vspec,
+                                                 M, self._vertex_inc_cap(M))
         truth = match = None
         if matching:                               # the TRUE classes under the same spec, then the match of the two id arrays
             buf, at, nbytes = self._fed_label
@@ -1148,6 +1169,9 @@ class ssnet_base(object):
         if prof is not None:
             records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, res['clusters'])
             res['profiles'] = self._finish_cluster_profile(sess, prof, records, voxels, res, pspec, self._dims[:-1])
+        if vtx is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, res['clusters'])
+            res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, voxels, res, vspec, self._dims[:-1])
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1525,6 +1549,173 @@ class ssnet_base(object):
         got = self._fetch_cluster_profile(prof, objects)
         assert got is not None, 'cluster_profile: %d bins sized from the returned lengths were not enough' % bin_cap
         return got
+
+    # ------------------------------------------------------------------------------------------
+    # vertex candidates: where cluster end points meet (definition and numpy statement: clusters.cluster_vertices_numpy, device
+    # passes: csrc/cluster_vertex.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_vertices(self, spec):
+        """A ``clusters.ClusterVertexSpec``: while one is set, and a cluster spec is set, and ``'cluster'`` is wanted,
+        ``inference_voxel_scores`` and ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_vertices`` behind the cluster passes
+        and the object records (which run for it whether or not ``set_cluster_features`` is on; tiled: on the stitched list in the
+        large shape, so a vertex can join ends from two tiles), and the result gains ``vertices``: per event what
+        ``cluster_vertices`` returns.  The row count is not known on the host there, so the incidence table is sized from the list
+        length; when the device reports more distinct incidences the result is made again by ``cluster_vertices`` on the returned
+        ids.  Memory: with the row count unknown, the tables are laid out for ``M`` rows of a list of ``M`` entries -- 2 M vertex
+        records, 4 M + 1024 incidences and the scratch for both, 1.1 to 1.4 KB of device memory per list entry for the duration of
+        the call (4 to 5 GB for a list of 3.5 M entries); ``cluster_vertices`` on returned ids sizes them from the row count instead.
+        None switches it off.  The legal members of ``want`` do not change; never called, the results have the keys they had."""
+        from .clusters import ClusterVertexSpec
+        if spec is not None and not isinstance(spec, ClusterVertexSpec):
+            raise ValueError('set_cluster_vertices: spec = %r, expected a clusters.ClusterVertexSpec or None' % (spec,))
+        self._cluster_vertex_spec = spec
+
+    @staticmethod
+    def _vertex_inc_cap(K):
+        """The first incidence table for ``K`` rows: an end point mostly meets its own row and a few others."""
+        return min(4 * K + 1024, 2 ** 30 - 1)
+
+    def _enqueue_cluster_vertices(self, sess, d_offsets, d_index, pending, objects, d_cls, shape, spec, rows, inc_cap):
+        """``ursn_cluster_vertices`` behind ``_enqueue_cluster_features`` (whose tables stay on the device); ``rows`` bounds the
+        cluster rows (the list length when the count is still on the device); enqueues only."""
+        import torch
+        lib = _lib.load()
+        ints, _, toff, _, n, M = pending
+        itab, rtab, _ = objects
+        shape = [int(s) for s in shape]
+        rows, inc_cap = int(rows), int(inc_cap)
+        need = int(lib.ursn_cluster_vertices_scratch_bytes(n, M, inc_cap))
+        if need == 0:
+            raise ValueError('cluster_vertices: %d events with %d list entries and %d incidences are out of domain' % (n, M, inc_cap))
+        cap_v = 2 * rows
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=self._device)
+        voff = torch.empty(n + 1, dtype=torch.int64, device=self._device)
+        ioff = torch.empty(cap_v + 1, dtype=torch.int64, device=self._device)
+        vi = torch.empty((max(cap_v, 1), _lib.CLVTX_VI), dtype=torch.int64, device=self._device)
+        vr = torch.empty((max(cap_v, 1), _lib.CLVTX_VR), dtype=torch.float64, device=self._device)
+        inc = torch.empty((max(inc_cap, 1), _lib.CLVTX_IN), dtype=torch.int64, device=self._device)
+        rv = torch.empty((max(rows, 1), 2), dtype=torch.int32, device=self._device)
+        ev = torch.empty((n, _lib.CLVTX_EV), dtype=torch.int64, device=self._device)
+        status = torch.empty(1, dtype=torch.int32, device=self._device)
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_vtx_desc()
+        d.ndim, d.n, d.m_total, d.radius, d.inc_cap = len(shape), n, M, spec.radius, inc_cap
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ints.data_ptr(), toff.data_ptr()
+        d.itab, d.rtab, d.feat_cap, d.cls = itab.data_ptr(), rtab.data_ptr(), M, ptr(d_cls)
+        d.min_size, d.class_mask = spec.min_size, spec.class_mask()
+        o = _lib.ursn_cluster_vtx_out()
+        o.vertex_offsets, o.vtx_itab, o.vtx_rtab, o.cap_vertices = voff.data_ptr(), vi.data_ptr(), vr.data_ptr(), cap_v
+        o.inc_offsets, o.incidence, o.inc_out_cap = ioff.data_ptr(), inc.data_ptr(), inc_cap
+        o.row_vertex, o.cap_rows, o.event, o.status = rv.data_ptr(), rows, ev.data_ptr(), status.data_ptr()
+        _lib.check(lib.ursn_cluster_vertices(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, voff, ioff, vi, vr, inc, rv, ev, status, itab, rtab) + (() if d_cls is None else (d_cls,)):
+            t.record_stream(cur)
+        return voff, ioff, vi, vr, inc, rv, ev, status
+
+    @staticmethod
+    def _fetch_cluster_vertices(vtx, objects):
+        """The vertex tables as per-event dicts (``objects``: what ``_fetch_cluster_features`` returned for the same rows), or None
+        when the incidence table was too small."""
+        from .clusters import VERTEX_EVENT, VERTEX_INT, VERTEX_REAL
+        voff, ioff, vi, vr, inc, rv, ev, status = vtx
+        code = int(status.cpu().numpy()[0])
+        if code & _lib.CLVTX_INC_OVERFLOW:
+            return None
+        if code != 0:
+            raise _lib.UrsnError('cluster_vertices: the ids, table offsets, lists and object records disagree (status %d)' % code)
+        counts = [int(o['n'].shape[0]) for o in objects]
+        voff = voff.cpu().numpy()
+        V = int(voff[-1])
+        assert voff[0] == 0 and V <= vi.shape[0] and sum(counts) <= rv.shape[0], 'cluster_vertices: %d vertices, %d in the table' % (
+            V, vi.shape[0])
+        ioff = ioff[:V + 1].cpu().numpy()
+        total = int(ioff[-1])
+        assert ioff[0] == 0 and total <= inc.shape[0], 'cluster_vertices: %d incidences, %d in the table' % (total, inc.shape[0])
+        vi, vr, inc = vi[:V].cpu().numpy(), vr[:V].cpu().numpy(), inc[:total].cpu().numpy()
+        rv, ev = rv[:sum(counts)].cpu().numpy(), ev.cpu().numpy()
+        res, at = [], 0
+        for i, (o, k) in enumerate(zip(objects, counts)):
+            lo, hi = int(voff[i]), int(voff[i + 1])
+            cols = {name: vi[lo:hi, c].copy() for c, name in enumerate(VERTEX_INT)}
+            cols.update({name: vr[lo:hi, c].copy() for c, name in enumerate(VERTEX_REAL)})
+            res.append({'objects': o, 'vertices': cols, 'incidence': inc[int(ioff[lo]):int(ioff[hi])].copy(),
+                        'inc_offsets': ioff[lo:hi + 1] - ioff[lo], 'row_vertex': rv[at:at + k].copy(),
+                        'event': dict(zip(VERTEX_EVENT, (int(x) for x in ev[i])))})
+            at += k
+        return res
+
+    def _finish_cluster_vertices(self, sess, vtx, objects, voxels_or_lists, res, spec, shape, value=None):
+        """The vertices enqueued with a voxel-score call, or -- the incidence table was too small -- ``cluster_vertices`` on the
+        returned ids."""
+        got = self._fetch_cluster_vertices(vtx, objects)
+        if got is None:
+            got = self.cluster_vertices(sess, voxels_or_lists, value() if callable(value) else value, res, spec, shape=shape)
+        return got
+
+    def cluster_vertices(self, sess, voxels_or_lists, value, clusters, spec, shape=None):
+        """Vertex candidates of clusters already made: ``voxels_or_lists``, ``value``, ``clusters`` and ``shape`` as
+        ``cluster_features`` takes them, ``spec`` a ``clusters.ClusterVertexSpec``.  Runs the object records and then the vertices;
+        the incidence table starts at 4 K + 1024 entries for K clusters and doubles while the device reports more.  Returns per
+        event a dict: ``objects`` (as ``cluster_features``), ``vertices`` (named columns ``clusters.VERTEX_INT`` / ``VERTEX_REAL``,
+        one row per vertex), ``incidence`` int64 [I, 5] (``clusters.VERTEX_INCIDENCE``) with ``inc_offsets`` [V_i + 1], event-local:
+        the incidences of vertex v are ``inc_offsets[v] .. inc_offsets[v + 1]``, ``row_vertex`` int32 [K_i, 2] and ``event`` (a dict
+        over ``clusters.VERTEX_EVENT``).  The record counts ends, bodies and angles; what kind of vertex it is stays the
+        consumer's judgement."""
+        import torch
+        from .clusters import ClusterVertexSpec
+        if not isinstance(spec, ClusterVertexSpec):
+            raise ValueError('cluster_vertices: spec = %r, expected a clusters.ClusterVertexSpec' % (spec,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_vertices: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = voxels_or_lists.value
+        elif isinstance(voxels_or_lists, _DeviceVoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = self._resident_value(voxels_or_lists)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_vertices: %d events outside [1, 65535]' % n)
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_vertices: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids]) if n else np.zeros(0, np.int32)
+        if cluster.size != M or index.size != M or (value is not None and value.size != M):
+            raise ValueError('cluster_vertices: %d list entries, %d indices, %d ids, %s values'
+                             % (M, index.size, cluster.size, 'no' if value is None else value.size))
+        toff = np.concatenate([[0], np.cumsum([int(t['first'].size) for t in tables])]).astype(np.int64)
+        K = int(toff[-1])
+        cls = np.concatenate([np.asarray(t['cls'], np.uint8).reshape(-1) for t in tables] + [np.zeros(1, np.uint8)])
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        d_off, d_index, d_toff, d_cls = up(off, np.int64), up(index, np.int32), up(toff, np.int64), up(cls, np.uint8)
+        d_cluster = up(cluster if M else np.zeros(1, np.int32), np.int32)
+        d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
+        pending = (d_cluster, None, d_toff, M, n, M)
+        dev_objects = self._enqueue_cluster_features(sess, d_off, d_index, d_value, pending, shape)
+        objects = self._fetch_cluster_features(dev_objects, tables)
+        inc_cap = self._vertex_inc_cap(K)
+        while True:
+            vtx = self._enqueue_cluster_vertices(sess, d_off, d_index, pending, dev_objects, d_cls, shape, spec, K, inc_cap)
+            got = self._fetch_cluster_vertices(vtx, objects)
+            if got is not None:
+                return got
+            if inc_cap >= 2 ** 30 - 1:
+                raise _lib.UrsnError('cluster_vertices: more than 2^30 - 1 distinct incidences')
+            inc_cap = min(2 * inc_cap, 2 ** 30 - 1)
 
     # ------------------------------------------------------------------------------------------
     # cluster matching (definition and numpy statement: clusters.cluster_match_numpy, device passes: csrc/cluster_match.hip)
@@ -2106,6 +2297,14 @@ class ssnet_base(object):
                                                pending, big)
             prof = self._enqueue_cluster_profile(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
                                                  pending, prof_objects, big, pspec, self._profile_bin_cap(M, pspec))
+        vspec = getattr(self, '_cluster_vertex_spec', None) if pending is not None else None
+        vtx = None
+        if vspec is not None:                      # the stitched list, in the large shape: a vertex joins ends from two tiles
+            vtx_objects = objects if objects is not None else prof_objects if pspec is not None else \
+                self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
+                                               pending, big)
+            vtx = self._enqueue_cluster_vertices(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, vtx_objects,
+                                                 pending[1], big, vspec, M, self._vertex_inc_cap(M))
         truth = match = None
         if matching:                               # the large batch's own labels under the same spec, then the match
             at = big_batch.ptr['label'] - big_batch.dev.data_ptr()
@@ -2139,6 +2338,11 @@ class ssnet_base(object):
             lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
             res['profiles'] = self._finish_cluster_profile(sess, prof, records, lists, res, pspec, big,
                                                            value=lambda: self._resident_value(big_batch))
+        if vtx is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, res['clusters'])
+            lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
+            res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, lists, res, vspec, big,
+                                                            value=lambda: self._resident_value(big_batch))
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 
