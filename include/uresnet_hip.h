@@ -1278,6 +1278,134 @@ size_t ursn_cluster_profile_scratch_bytes(int32_t n, int64_t m_total, int64_t ca
 int ursn_cluster_profile(const ursn_cluster_prof_desc* d, const ursn_cluster_prof_out* out, void* scratch, size_t scratch_bytes,
                          void* stream);
 
+/* ---- cluster chains: broken track fragments joined end to end (cluster_chain.hip) -----------------------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.  (The section stands here, before the last one, because
+ * existing tests pin that one as the header's end; nothing before or after it moved.)
+ * A connected component is not a particle: a dead wire or a few lost voxels cut one track into collinear fragments.  This call
+ * joins them: end points of different rows that face each other across a gap, with both axes and the gap vector collinear, are
+ * joined when the choice is mutual; rows linked by joins form a CHAIN, and the chains come back as a second clustering of the same
+ * lists in the (cluster, table_offsets, first / size / cls) format of ursn_cluster_voxels, so every call that takes a clustering
+ * runs on the merged objects unchanged.  Input: the lists and ids ursn_cluster_features read, the two tables it wrote for them,
+ * optionally the cluster table's cls.  uresnet_amd/clusters.py (cluster_chains_numpy) states every field operation by operation;
+ * the device gives the same bits.
+ *
+ * A global row r is ELIGIBLE when its object record has n >= min_size and end_lo != end_hi and, with class_mask != 0, bit cls[r] of
+ * class_mask is set.  An eligible row has two END POINTS, at the list positions end_lo and end_hi, with the KEY 2 r + side (side 0 =
+ * end_lo) and the DIRECTION u = +axis at the lo end, -axis at the hi end (it points from the end into the row).  Coordinates x[0..2]
+ * are the row-major coordinates of index[j] in `spatial` (2-D: x[2] = 0).  A CANDIDATE is a pair of end points p < q (by key) of one
+ * event and of DIFFERENT rows whose coordinates differ by at most max_gap on every axis and, with same_class, whose rows have equal
+ * cls.  It is evaluated once, p the lower key, every operation rounded on its own:
+ *   d = x(q) - x(p)     dist2 = d . d  (1 .. 3 * 31^2 = 2883)     s = sqrt((double)dist2)
+ *   c_ax = -((u_p[0] * u_q[0] + u_p[1] * u_q[1]) + u_p[2] * u_q[2])
+ *   c_lo = (-((u_p[0] * d0 + u_p[1] * d1) + u_p[2] * d2)) / s        c_hi = ((u_q[0] * d0 + u_q[1] * d1) + u_q[2] * d2) / s
+ * and ACCEPTED when c_ax >= min_cos && c_lo >= min_cos && c_hi >= min_cos (a NaN rejects).  Every end point counts its accepted
+ * candidates and picks as BEST the one smallest in (dist2, partner key); {p, q} is a JOIN when each is the other's best: an end
+ * point is in at most one join, a row in at most two.  Rows linked by joins are unioned; a CHAIN is a component, numbered per event
+ * by its lowest row: chain_offsets[n + 1].  Every row below the row count is in exactly one chain.
+ * merged[j]: the event-local chain of cluster[j]'s row, -1 where cluster[j] is -1.  Chain table: first = the lowest event-local
+ * list position of a member, size = members, cls = cls of the lowest row (0 without cls).
+ * Chain record, URSN_CLCHAIN_CI int64:
+ *   [0] rows   [1] joins   [2] n, [3] charge   summed over the object records   [4..6] lo, [7..9] hi   the union of their boxes
+ *   [10] first_row  event-local   [11] end_a, [12] end_b   list positions (the walk)   [13] gap2_sum, [14] gap2_max   over the joins'
+ *   dist2   [15] class mask of the rows (0 without cls) | flags << 32; flag bit 0: a ring (no free end); flag bit 1: a member row
+ *   whose object record has flags != 0
+ * Chain record, URSN_CLCHAIN_CR fp64:  [0] path   [1] gaps   [2] span   [3] straightness   [4] min_cos, by THE WALK: START is the
+ *   chain's free end point (an end of a member row that is in no join; a row that is not eligible has two) with the lowest key, a
+ *   ring starts at the lo side of first_row; end_a is START's position; enter the start row at that side, then `rows` times:
+ *   path = path + length[row]; leave at the other side; if that side is in a join and fewer than `joins` joins were taken:
+ *   g = sqrt((double)dist2), path = path + g, gaps = gaps + g, min_cos takes the join's c_ax if it is the first or strictly smaller,
+ *   enter the partner row at the partner's side.  end_b is the position of the end at which the walk leaves its last row;
+ *   span = sqrt((double)(squared distance between the coordinates of end_a and end_b)); straightness = span / path, +0.0 when
+ *   path == 0.0; min_cos and gaps are +0.0 without joins.
+ * Join record, CSR by event (join_offsets[n + 1]), ascending key_a.  URSN_CLCHAIN_JI int64: [0] key_a < [1] key_b (event-local
+ *   keys)   [2] dist2   [3] pos_a, [4] pos_b   list positions   [5] chain (event-local).  URSN_CLCHAIN_JR fp64: [0] c_ax   [1] c_lo
+ *   [2] c_hi   [3] gap = sqrt((double)dist2).
+ * Per row: row_chain int32; row_join int32 [2] = the partner's event-local key at the lo / hi side, -1 for none; row_candidates
+ * int32 [2].  Event record, URSN_CLCHAIN_EV int64: [0] chains   [1] joins   [2] joined (chains with rows >= 2)   [3] longest = the
+ * chain largest in (rows, n), the lowest id among equals; -1 without chains.
+ * What it does not decide: whether a joined pair is one particle stays the consumer's judgement; the cosines and the gap are there
+ * to cut on.
+ *
+ * Bounds with every extent <= 32768, m_total < 2^30 and K rows: at most K joins (an end point is in at most one, a join takes two),
+ * so no table of this call can overflow; the rows of a chain are distinct rows of one event, so n < 2^31 and |charge| <= 2^62;
+ * gap2_sum <= 2883 K.  The packed words fit: dist2 << 32 | key with dist2 <= 2883 and key < 2^31 (m_total is bounded by 2^30 so that
+ * every key 2 r + side is an int32); rows << 32 | n with rows < 2^30 and n < 2^31, below 2^63.
+ *
+ * Method: twelve launches (cluster_chain.hip lists them).  The search does not walk list rows -- the gaps are up to 31 voxels and
+ * there are at most 2 K end points: the end positions of the eligible rows are marked, counted per tile of 64 entries, scanned by one
+ * workgroup and compacted in list order, so the compact array is sorted by event << 32 | index; the end points of plane x0 + d0
+ * with x1 within max_gap are one contiguous range of it (a 2-D list runs as (s0, s1, 1)), found by a lower-bound binary search
+ * (<= 32 halvings) and left at the range's last index, then filtered on x2, row and class.  One wave64 per end point, one lane per
+ * plane (2 max_gap + 1 <= 63 lanes), a wave reduction of ONE packed minimum dist2 << 32 | key and of the accepted count: the wave
+ * owns its end point, no atomics in the search (URSN_CLCHAIN_WAVE=0: one thread per end point takes its planes one after another;
+ * same bits).  A mutual test per end point; a union-find over rows with 32-bit atomicMin to the lower root; one-workgroup scans for
+ * the chain numbers and the join list; per row 64-bit INTEGER atomic adds / min / max / ors at agent scope onto its chain; per entry
+ * merged and an integer atomic minimum for first; one thread per chain walks it and computes every fp64 value in the order above
+ * under contract(off); a packed 64-bit atomic maximum and one minimum find the longest.  No float atomics.  Enqueues only, never
+ * synchronises; the scratch needs no initialisation; every device loop is bounded; the same arguments give the same bits.
+ *
+ * Rows considered: below min(table_offsets[n], feat_cap, m_total).  *status is 0, or: bit 0 an id outside [-1, K_e) or offsets that
+ * are not those of the lists, bit 1 a row without a member, bit 2 an index outside the volume at an entry with an id, bit 3 a bounded
+ * loop ran out, bit 4 a cls >= 32, bit 5 an end position of an otherwise eligible row that is not a member of it, bit 6
+ * table_offsets[n] > feat_cap (such a row is not eligible and stays a chain of one, such an entry gets merged = -1; every entry with
+ * an id and every row is checked, and the bits are the same whenever the arguments are).  Chains, joins and rows at or beyond
+ * cap_chains / cap_joins / cap_rows are never written; everything below them is complete whatever the caps are; chain_offsets,
+ * join_offsets and the event records hold the true counts.  m_total = 0 or no clusters still writes *status, the offsets and the
+ * event records.  Null, misaligned, out-of-domain and too-small arguments are refused with a message that begins "cluster_chains:"
+ * before any launch. */
+#define URSN_CLCHAIN_CI 16   /* int64 columns of a chain record */
+#define URSN_CLCHAIN_CR 5    /* fp64 columns of a chain record */
+#define URSN_CLCHAIN_JI 6    /* int64 columns of a join record */
+#define URSN_CLCHAIN_JR 4    /* fp64 columns of a join record */
+#define URSN_CLCHAIN_EV 4    /* int64 columns of an event record */
+
+typedef struct ursn_cluster_chain_desc { /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t max_gap;                      /* 1..31 */
+  int64_t m_total;                      /* list entries, < 2^30 */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] strictly increasing per event */
+  const int32_t* cluster;               /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets;         /* [n+1] as ursn_cluster_voxels wrote it */
+  const int64_t* itab;                  /* [feat_cap][URSN_CLFEAT_I] as ursn_cluster_features wrote it for these lists */
+  const double* rtab;                   /* [feat_cap][URSN_CLFEAT_R] */
+  int64_t feat_cap;                     /* the cap of those tables */
+  const uint8_t* cls;                   /* [K_total] the cluster table's cls, or null: every class mask is 0 */
+  double min_cos;                       /* [0, 1] */
+  int32_t min_size;                     /* >= 1 */
+  uint32_t class_mask;                  /* 0: rows of every class are eligible; else bit cls[r] decides, and cls must be given */
+  int32_t same_class;                   /* 0 | 1: only rows of equal cls are joined, and cls must be given */
+  int32_t reserved;                     /* 0 */
+} ursn_cluster_chain_desc;
+
+typedef struct ursn_cluster_chain_out { /* DEVICE pointers */
+  int32_t* merged;                      /* [m_total] */
+  int64_t* chain_offsets;               /* [n+1] */
+  int32_t* first;                       /* [cap_chains] the chain table, typed as ursn_cluster_out's */
+  int32_t* size;                        /* [cap_chains] */
+  uint8_t* cls;                         /* [cap_chains] */
+  int64_t* chain_itab;                  /* [cap_chains][URSN_CLCHAIN_CI] */
+  double* chain_rtab;                   /* [cap_chains][URSN_CLCHAIN_CR] */
+  int64_t cap_chains;
+  int64_t* join_offsets;                /* [n+1] */
+  int64_t* join_itab;                   /* [cap_joins][URSN_CLCHAIN_JI] */
+  double* join_rtab;                    /* [cap_joins][URSN_CLCHAIN_JR] */
+  int64_t cap_joins;
+  int32_t* row_chain;                   /* [cap_rows] */
+  int32_t* row_join;                    /* [cap_rows][2] */
+  int32_t* row_candidates;              /* [cap_rows][2] */
+  int64_t cap_rows;
+  int64_t* event;                       /* [n][URSN_CLCHAIN_EV] */
+  int32_t* status;                      /* [1] */
+} ursn_cluster_chain_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535] or m_total outside [0, 2^30).  Host logic only. */
+size_t ursn_cluster_chains_scratch_bytes(int32_t n, int64_t m_total);
+int ursn_cluster_chains(const ursn_cluster_chain_desc* d, const ursn_cluster_chain_out* out, void* scratch, size_t scratch_bytes,
+                        void* stream);
+
 /* ---- vertex candidates: where the end points of the object records meet (cluster_vertex.hip) ----------------------------------------
  * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
  * The step from objects to interactions: which ends meet at one point, how many objects leave it and at what angles, which objects

@@ -196,6 +196,24 @@ class ursn_cluster_vtx_out(C.Structure):
                 ("cap_rows", C.c_int64), ("event", C.c_void_p), ("status", C.c_void_p)]
 
 
+CLCHAIN_CI, CLCHAIN_CR, CLCHAIN_JI, CLCHAIN_JR, CLCHAIN_EV = 16, 5, 6, 4, 4   # URSN_CLCHAIN_*: columns of the chain, join and event records
+
+
+class ursn_cluster_chain_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("max_gap", C.c_int32), ("m_total", C.c_int64),
+                ("offsets", C.c_void_p), ("index", C.c_void_p), ("cluster", C.c_void_p), ("table_offsets", C.c_void_p),
+                ("itab", C.c_void_p), ("rtab", C.c_void_p), ("feat_cap", C.c_int64), ("cls", C.c_void_p), ("min_cos", C.c_double),
+                ("min_size", C.c_int32), ("class_mask", C.c_uint32), ("same_class", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ursn_cluster_chain_out(C.Structure):
+    _fields_ = [("merged", C.c_void_p), ("chain_offsets", C.c_void_p), ("first", C.c_void_p), ("size", C.c_void_p), ("cls", C.c_void_p),
+                ("chain_itab", C.c_void_p), ("chain_rtab", C.c_void_p), ("cap_chains", C.c_int64), ("join_offsets", C.c_void_p),
+                ("join_itab", C.c_void_p), ("join_rtab", C.c_void_p), ("cap_joins", C.c_int64), ("row_chain", C.c_void_p),
+                ("row_join", C.c_void_p), ("row_candidates", C.c_void_p), ("cap_rows", C.c_int64), ("event", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -323,6 +341,9 @@ _SIGS = {
     # cluster_vertex.hip (declared last in the header; an existing test pins the graph's two as the last of this table)
     "ursn_cluster_vertices_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
     "ursn_cluster_vertices": (C.c_int, [C.POINTER(ursn_cluster_vtx_desc), C.POINTER(ursn_cluster_vtx_out), _P, C.c_size_t, _P]),
+    # cluster_chain.hip
+    "ursn_cluster_chains_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "ursn_cluster_chains": (C.c_int, [C.POINTER(ursn_cluster_chain_desc), C.POINTER(ursn_cluster_chain_out), _P, C.c_size_t, _P]),
     "ursn_cluster_graph_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_graph": (C.c_int, [C.POINTER(ursn_cluster_graph_desc), C.POINTER(ursn_cluster_graph_out), _P, C.c_size_t, _P]),
 }

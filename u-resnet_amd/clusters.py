@@ -1039,3 +1039,334 @@ def cluster_vertices_numpy(offsets, index, value, cluster, table_offsets, spatia
     return {'objects': f, 'vertex_offsets': np.array(vertex_offsets, np.int64), 'vertices': vertices,
             'inc_offsets': np.array(inc_offsets, np.int64), 'incidence': np.array(incidence, np.int64).reshape(-1, 5),
             'row_vertex': row_vertex, 'events': np.array(events, np.int64).reshape(-1, 4)}
+
+
+# ---- cluster chains: broken track fragments joined end to end (csrc/cluster_chain.hip does it on the device; this is the statement) --
+CHAIN_INT = ('rows', 'joins', 'n', 'charge', 'lo0', 'lo1', 'lo2', 'hi0', 'hi1', 'hi2', 'first_row', 'end_a', 'end_b', 'gap2_sum',
+             'gap2_max', 'mask_flags')
+CHAIN_REAL = ('path', 'gaps', 'span', 'straightness', 'min_cos')
+JOIN_INT = ('key_a', 'key_b', 'dist2', 'pos_a', 'pos_b', 'chain')
+JOIN_REAL = ('c_ax', 'c_lo', 'c_hi', 'gap')
+CHAIN_EVENT = ('chains', 'joins', 'joined', 'longest')
+CHAIN_MAX_GAP = 31
+
+
+class ClusterChainSpec(object):
+    """``max_gap`` in [1, 31]: two end points can be joined when their coordinates differ by at most ``max_gap`` on every axis;
+    ``min_cos`` a finite float in [0, 1]: the three cosines of a join (axis against axis, gap against either axis) must reach it;
+    ``min_size`` >= 1: clusters with fewer members are not joined; ``classes`` None = clusters of every class, else distinct class
+    numbers in [0, 32): only clusters of these classes are joined (needs the table's cls); ``same_class`` True = only clusters of
+    equal class are joined (needs the table's cls)."""
+
+    def __init__(self, max_gap=6, min_cos=0.9, min_size=3, classes=None, same_class=True):
+        if type(max_gap) is not int or not 1 <= max_gap <= CHAIN_MAX_GAP:
+            raise ValueError('ClusterChainSpec: max_gap = %r, expected an integer in [1, %d]' % (max_gap, CHAIN_MAX_GAP))
+        if type(min_cos) not in (int, float) or not np.isfinite(min_cos) or not 0.0 <= min_cos <= 1.0:
+            raise ValueError('ClusterChainSpec: min_cos = %r, expected a finite float in [0, 1]' % (min_cos,))
+        if type(min_size) is not int or not 1 <= min_size < 2 ** 31:
+            raise ValueError('ClusterChainSpec: min_size = %r, expected an integer >= 1' % (min_size,))
+        if classes is not None:
+            given = classes
+            try:
+                classes = tuple(classes)
+            except TypeError:
+                classes = ()
+            if not classes or any(type(c) is not int or not 0 <= c < 32 for c in classes) or len(set(classes)) != len(classes):
+                raise ValueError('ClusterChainSpec: classes = %r, expected None or distinct integers in [0, 32)' % (given,))
+        if type(same_class) is not bool:
+            raise ValueError('ClusterChainSpec: same_class = %r, expected a bool' % (same_class,))
+        self.max_gap, self.min_cos, self.min_size, self.classes, self.same_class = max_gap, float(min_cos), min_size, classes, same_class
+
+    def class_mask(self):
+        """Bit k set = clusters of class k can be joined; 0 = every class."""
+        m = 0
+        for c in self.classes or ():
+            m |= 1 << c
+        return m
+
+    def __repr__(self):
+        return 'ClusterChainSpec(max_gap=%r, min_cos=%r, min_size=%r, classes=%r, same_class=%r)' % (
+            self.max_gap, self.min_cos, self.min_size, self.classes, self.same_class)
+
+
+def chain_cosines(u_p, u_q, d):
+    """(dist2, c_ax, c_lo, c_hi) of a candidate: ``u_p`` / ``u_q`` the directions of the end points with the lower / higher key,
+    ``d`` = x(q) - x(p) as integers.  Every line is one fp64 operation rounded on its own; the device follows it."""
+    dist2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        s = np.sqrt(np.float64(dist2))
+        f = [np.float64(x) for x in d]
+        c_ax = -((u_p[0] * u_q[0] + u_p[1] * u_q[1]) + u_p[2] * u_q[2])
+        c_lo = (-((u_p[0] * f[0] + u_p[1] * f[1]) + u_p[2] * f[2])) / s
+        c_hi = ((u_q[0] * f[0] + u_q[1] * f[1]) + u_q[2] * f[2]) / s
+    return dist2, c_ax, c_lo, c_hi
+
+
+def cluster_chains_numpy(offsets, index, value, cluster, table_offsets, spatial, spec, cls=None):
+    """The statement of the cluster chains of concatenated per-event lists: which clusters are fragments of one broken track, joined
+    end to end across a gap.  Slow on purpose, in the style of ``cluster_features_numpy``, which it calls first (its result is
+    returned under ``objects``): Python integers, scalar fp64 operations each rounded on its own.
+
+    END POINTS.  A global row r is ELIGIBLE when its object record has n >= ``spec.min_size`` and end_lo != end_hi and, with
+    ``spec.classes``, ``cls[r]`` is one of them.  An eligible row has two end points, at the list positions ``end_lo[r]`` and
+    ``end_hi[r]``; the KEY of an end point is 2 r + side (side 0 = end_lo); its DIRECTION is u = +axis[r] at the lo end and
+    -axis[r] (unary minus) at the hi end: it points from the end into its cluster.  Coordinates are ``np.unravel_index(index,
+    spatial)`` with x[2] = 0 in 2-D.
+
+    CANDIDATES.  Two end points p < q (by key) of one event and of DIFFERENT rows whose coordinates differ by at most
+    ``spec.max_gap`` on every axis and, with ``spec.same_class``, whose rows have equal ``cls``.  Evaluated once, p the lower key
+    (``chain_cosines``): d = x(q) - x(p); dist2 = d . d (1 .. 3 * 31^2 = 2883); s = sqrt(float64(dist2));
+    c_ax = -((u_p[0] * u_q[0] + u_p[1] * u_q[1]) + u_p[2] * u_q[2]); c_lo = (-((u_p[0] * d0 + u_p[1] * d1) + u_p[2] * d2)) / s;
+    c_hi = ((u_q[0] * d0 + u_q[1] * d1) + u_q[2] * d2) / s.  ACCEPTED when c_ax >= min_cos and c_lo >= min_cos and c_hi >= min_cos
+    (a NaN rejects): the two bodies point away from each other and the gap vector leaves p's body and enters q's.
+
+    JOINS.  Every end point counts its accepted candidates (``row_candidates``) and picks as BEST the one smallest in (dist2,
+    partner key); {p, q} is a JOIN when each is the other's best.  An end point is in at most one join, a row in at most two.
+
+    CHAINS.  Rows linked by joins are unioned; a chain is a component, numbered per event by its lowest row, ``chain_offsets``
+    [n + 1]; every row is in exactly one chain (a row without a join is a chain of one).  ``merged[j]`` is the event-local chain
+    of ``cluster[j]``'s row, -1 where ``cluster[j]`` is -1.  ``table``: ``first`` int32 = the lowest event-local list position of a
+    member, ``size`` int32 = members, ``cls`` uint8 = ``cls`` of the lowest row (0 without ``cls``): with ids numbered by lowest
+    position, as ``ursn_cluster_voxels`` numbers them, ``first`` is strictly increasing per event and (merged, chain_offsets,
+    table) is a clustering in that call's format.
+
+    CHAIN_INT: ``rows``; ``joins``; ``n`` / ``charge`` summed over the object records; ``lo0..2`` / ``hi0..2`` the union of their
+    boxes; ``first_row`` (event-local); ``end_a`` / ``end_b`` list positions (the walk); ``gap2_sum`` / ``gap2_max`` over the
+    joins' dist2; ``mask_flags`` = the class mask of the rows (0 without ``cls``) | flags << 32, flag bit 0: a ring (no free end),
+    flag bit 1: a member row whose object record has flags != 0.  CHAIN_REAL: ``path``, ``gaps``, ``span``, ``straightness``,
+    ``min_cos``.  THE WALK fixes the order of the fp64 sums.  START is the chain's free end point (an end of a member row that is
+    in no join; a row that is not eligible counts as having two free ends) with the lowest key; a ring starts at the lo side of
+    ``first_row``.  ``end_a`` is START's position.  Enter the start row at that side, then ``rows`` times: path = path +
+    length[row]; leave at the other side; if that side is in a join and fewer than ``joins`` joins were taken: g =
+    sqrt(float64(dist2)), path = path + g, gaps = gaps + g, min_cos takes the join's c_ax if it is the first or strictly smaller,
+    enter the partner row at the partner's side.  ``end_b`` is the position of the end at which the walk leaves its last row;
+    span = sqrt(float64(squared distance between the coordinates of end_a and end_b)); straightness = span / path, +0.0 when
+    path == 0.0; min_cos and gaps are +0.0 without joins.
+
+    JOINS LIST, CSR by event (``join_offsets`` [n + 1]), ascending key_a.  JOIN_INT: ``key_a`` < ``key_b`` (event-local keys),
+    ``dist2``, ``pos_a``, ``pos_b`` (list positions), ``chain`` (event-local).  JOIN_REAL: ``c_ax``, ``c_lo``, ``c_hi``, ``gap`` =
+    sqrt(float64(dist2)).  Per row: ``row_chain`` int32 [K]; ``row_join`` int32 [K, 2] the partner's event-local key at the lo /
+    hi side, -1 for none; ``row_candidates`` int32 [K, 2].  CHAIN_EVENT: ``chains``, ``joins``, ``joined`` (chains with rows >=
+    2), ``longest`` = the chain largest in (rows, n), the lowest id among equals, -1 without chains.
+
+    Bounds, with every extent <= 32768, fewer than 2^30 entries (m_total < 2^30, so that every key is an int32 below 2^31 and
+    dist2 << 32 | key fits a 64-bit word) and K rows: at most K joins (an end point is in at most one, and a join takes two);
+    n < 2^31 and |charge| <= 2^62 (the rows of a chain are distinct rows of one event); gap2_sum <= 2883 K.
+
+    An id outside its event's rows, a row without a member, an index outside the volume at an entry with an id, an end position
+    of an eligible row that is not a member of it and a cls >= 32 raise ValueError.  Returns a dict: ``objects``;
+    ``chain_offsets`` int64 [n + 1]; ``merged`` int32 [m]; ``table`` {first, size, cls}; ``chains`` {name: [C]} over CHAIN_INT
+    (int64) and CHAIN_REAL (float64); ``join_offsets`` int64 [n + 1]; ``joins`` {name: [J]} over JOIN_INT / JOIN_REAL;
+    ``row_chain``; ``row_join``; ``row_candidates``; ``events`` int64 [n, 4]."""
+    if not isinstance(spec, ClusterChainSpec):
+        raise ValueError('cluster_chains_numpy: spec = %r, expected a ClusterChainSpec' % (spec,))
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or any(not 1 <= s <= MAX_EXTENT for s in spatial):
+        raise ValueError('cluster_chains_numpy: spatial = %r, expected 2 or 3 extents in [1, %d]' % (spatial, MAX_EXTENT))
+    off = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    idx = [int(x) for x in np.asarray(index).reshape(-1)]
+    ids = [int(x) for x in np.asarray(cluster).reshape(-1)]
+    nev, m, ndim, g = len(off) - 1, len(idx), len(spatial), spec.max_gap
+    if nev < 1 or len(toff) != nev + 1 or len(ids) != m or off[0] != 0 or off[-1] != m or toff[0] != 0 \
+            or any(off[e + 1] < off[e] or toff[e + 1] < toff[e] for e in range(nev)):
+        raise ValueError('cluster_chains_numpy: offsets, table offsets and the lists disagree')
+    K = toff[-1]
+    if cls is not None:
+        cls = [int(c) for c in np.asarray(cls).reshape(-1)]
+        if len(cls) != K or any(not 0 <= c < 32 for c in cls):
+            raise ValueError('cluster_chains_numpy: cls must hold %d classes in [0, 32)' % K)
+    if spec.classes is not None and cls is None:
+        raise ValueError('cluster_chains_numpy: spec.classes = %r needs the cluster table\'s cls' % (spec.classes,))
+    if spec.same_class and cls is None:
+        raise ValueError('cluster_chains_numpy: spec.same_class needs the cluster table\'s cls')
+    vox = 1
+    for s in spatial:
+        vox *= s
+
+    def coords_of(j):
+        x = tuple(int(c) for c in np.unravel_index(idx[j], spatial))
+        return x + (0,) * (3 - ndim)
+
+    first_pos = [None] * K                                # the lowest event-local position of a member
+    for e in range(nev):
+        for j in range(off[e], off[e + 1]):
+            if ids[j] < 0:
+                continue
+            if not ids[j] < toff[e + 1] - toff[e]:
+                raise ValueError('cluster_chains_numpy: entry %d has id %d, its event has %d clusters' % (j, ids[j], toff[e + 1] - toff[e]))
+            if not 0 <= idx[j] < vox:
+                raise ValueError('cluster_chains_numpy: entry %d has index %d outside the volume %r' % (j, idx[j], spatial))
+            r = toff[e] + ids[j]
+            if first_pos[r] is None:
+                first_pos[r] = j - off[e]
+    f = cluster_features_numpy(offsets, index, value, cluster, table_offsets, spatial)    # raises on a row without a member
+    event_of = [e for e in range(nev) for _ in range(toff[e + 1] - toff[e])]
+    mask, min_cos = spec.class_mask(), np.float64(spec.min_cos)
+    ends, xs, us = {}, {}, {}                             # key -> list position, coordinates, direction
+    for r in range(K):
+        lo, hi = int(f['end_lo'][r]), int(f['end_hi'][r])
+        if int(f['n'][r]) < spec.min_size or lo == hi or (mask and not (mask >> cls[r]) & 1):
+            continue
+        e = event_of[r]
+        ax = [np.float64(t) for t in f['axis'][r]]
+        for side, p in ((0, lo), (1, hi)):
+            if not off[e] <= p < off[e + 1] or ids[p] != r - toff[e]:
+                raise ValueError('cluster_chains_numpy: the end position %d of row %d is not a member of it' % (p, r))
+            ends[2 * r + side], xs[2 * r + side], us[2 * r + side] = p, coords_of(p), (ax if side == 0 else [-t for t in ax])
+    by_event = [[] for _ in range(nev)]
+    for k in sorted(ends):
+        by_event[event_of[k >> 1]].append(k)
+    accepted = {}                                         # (p, q), p < q -> (dist2, c_ax, c_lo, c_hi)
+    ncand = {k: 0 for k in ends}
+    best = {}                                             # key -> (dist2, partner key)
+
+    def consider(p, q):
+        if p >> 1 == q >> 1 or (spec.same_class and cls[p >> 1] != cls[q >> 1]):
+            return
+        d = [xs[q][a] - xs[p][a] for a in range(3)]
+        if any(abs(t) > g for t in d):
+            return
+        dist2, c_ax, c_lo, c_hi = chain_cosines(us[p], us[q], d)
+        assert 1 <= dist2 <= 3 * CHAIN_MAX_GAP ** 2
+        if c_ax >= min_cos and c_lo >= min_cos and c_hi >= min_cos:
+            accepted[(p, q)] = (dist2, c_ax, c_lo, c_hi)
+            for a, b in ((p, q), (q, p)):
+                ncand[a] += 1
+                if a not in best or (dist2, b) < best[a]:
+                    best[a] = (dist2, b)
+
+    for keys in by_event:
+        if len(keys) <= (2 * g + 1) ** 2:                 # few end points: every pair
+            for i, p in enumerate(keys):
+                for q in keys[i + 1:]:
+                    consider(p, q)
+        else:                                             # many: by column (x0, x1)
+            cols = {}
+            for k in keys:
+                cols.setdefault(xs[k][:2], []).append(k)
+            for p in keys:
+                for d0 in range(-g, g + 1):
+                    for d1 in range(-g, g + 1):
+                        for q in cols.get((xs[p][0] + d0, xs[p][1] + d1), ()):
+                            if q > p:
+                                consider(p, q)
+    partner = {k: best[k][1] for k in best if best.get(best[k][1], (0, -1))[1] == k}
+    assert len(partner) <= 2 * K and len(partner) % 2 == 0
+    parent = list(range(K))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for k in sorted(partner):
+        if k < partner[k]:
+            a, b = find(k >> 1), find(partner[k] >> 1)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    chain_of, chain_offsets, members = [0] * K, [0], []   # members[c]: the rows of global chain c, ascending
+    for e in range(nev):
+        for r in range(toff[e], toff[e + 1]):
+            root = find(r)
+            if root == r:
+                chain_of[r] = len(members)
+                members.append([])
+            chain_of[r] = chain_of[root]                  # a root is the lowest row of its chain: it came first
+            members[chain_of[r]].append(r)
+        chain_offsets.append(len(members))
+    C = len(members)
+    merged = np.full(m, -1, np.int32)
+    for e in range(nev):
+        for j in range(off[e], off[e + 1]):
+            if ids[j] >= 0:
+                merged[j] = chain_of[toff[e] + ids[j]] - chain_offsets[e]
+    row_chain = np.array([chain_of[r] - chain_offsets[event_of[r]] for r in range(K)], np.int32).reshape(K)
+    row_join, row_candidates = np.full((K, 2), -1, np.int32), np.zeros((K, 2), np.int32)
+    for k in ends:
+        row_candidates[k >> 1][k & 1] = ncand[k]
+        if k in partner:
+            row_join[k >> 1][k & 1] = partner[k] - 2 * toff[event_of[k >> 1]]
+    chains = {name: [] for name in CHAIN_INT + CHAIN_REAL}
+    table = {'first': [], 'size': [], 'cls': []}
+    events = [[chain_offsets[e + 1] - chain_offsets[e], 0, 0, -1] for e in range(nev)]
+    longest = [None] * nev
+    zero = np.float64(0.0)
+
+    def cand(a, b):
+        return accepted[(min(a, b), max(a, b))]
+
+    for c in range(C):
+        rows = members[c]
+        e = event_of[rows[0]]
+        n_sum = sum(int(f['n'][r]) for r in rows)
+        q_sum = sum(int(f['charge'][r]) for r in rows)
+        joined = [k for r in rows for k in (2 * r, 2 * r + 1) if k in partner]
+        free = [k for r in rows for k in (2 * r, 2 * r + 1) if k not in partner]
+        njoin = len(joined) // 2
+        d2s = [cand(k, partner[k])[0] for k in joined if k < partner[k]]
+        cmask = flags = 0
+        for r in rows:
+            if cls is not None:
+                cmask |= 1 << cls[r]
+            if int(f['flags'][r]) != 0:
+                flags |= 2
+        if not free:
+            flags |= 1
+        start = min(free) if free else 2 * rows[0]
+        pos = lambda k: int(f['end_hi' if k & 1 else 'end_lo'][k >> 1])
+        path = gaps = zero
+        lowest, taken = None, 0
+        row, side = start >> 1, start & 1
+        out = start
+        for _ in range(len(rows)):
+            path = path + np.float64(f['length'][row])
+            out = 2 * row + (1 - side)
+            if out in partner and taken < njoin:
+                dist2, c_ax, _, _ = cand(out, partner[out])
+                gap = np.sqrt(np.float64(dist2))
+                path = path + gap
+                gaps = gaps + gap
+                if lowest is None or c_ax < lowest:
+                    lowest = c_ax
+                taken += 1
+                row, side = partner[out] >> 1, partner[out] & 1
+        end_a, end_b = pos(start), pos(out)
+        xa, xb = coords_of(end_a), coords_of(end_b)
+        span = np.sqrt(np.float64(sum((xa[a] - xb[a]) ** 2 for a in range(3))))
+        assert n_sum < 2 ** 31 and abs(q_sum) <= 2 ** 62 and taken == njoin <= len(rows)
+        ints = [len(rows), njoin, n_sum, q_sum] + [min(int(f['lo'][r][a]) for r in rows) for a in range(3)] + \
+            [max(int(f['hi'][r][a]) for r in rows) for a in range(3)] + [rows[0] - toff[e], end_a, end_b, sum(d2s), max(d2s + [0]),
+                                                                        cmask | flags << 32]
+        reals = [path, gaps, span, span / path if path != zero else zero, zero if lowest is None else lowest]
+        for name, val in zip(CHAIN_INT + CHAIN_REAL, ints + reals):
+            chains[name].append(val)
+        table['first'].append(min(first_pos[r] for r in rows))
+        table['size'].append(n_sum)
+        table['cls'].append(cls[rows[0]] if cls is not None else 0)
+        events[e][1] += njoin
+        events[e][2] += 1 if len(rows) >= 2 else 0
+        if longest[e] is None or (len(rows), n_sum) > longest[e]:             # ascending id: a strict comparison keeps the lowest
+            longest[e], events[e][3] = (len(rows), n_sum), c - chain_offsets[e]
+    joins = {name: [] for name in JOIN_INT + JOIN_REAL}
+    join_offsets = [0]
+    for e in range(nev):
+        for k in by_event[e]:                             # ascending key
+            if k in partner and k < partner[k]:
+                q = partner[k]
+                dist2, c_ax, c_lo, c_hi = accepted[(k, q)]
+                vals = [k - 2 * toff[e], q - 2 * toff[e], dist2, ends[k], ends[q], chain_of[k >> 1] - chain_offsets[e], c_ax, c_lo, c_hi,
+                        np.sqrt(np.float64(dist2))]
+                for name, val in zip(JOIN_INT + JOIN_REAL, vals):
+                    joins[name].append(val)
+        join_offsets.append(len(joins['key_a']))
+    assert join_offsets[-1] <= K
+    return {'objects': f, 'chain_offsets': np.array(chain_offsets, np.int64), 'merged': merged,
+            'table': {'first': np.array(table['first'], np.int32).reshape(-1), 'size': np.array(table['size'], np.int32).reshape(-1),
+                      'cls': np.array(table['cls'], np.uint8).reshape(-1)},
+            'chains': {k: np.array(chains[k], np.int64 if k in CHAIN_INT else np.float64).reshape(-1) for k in chains},
+            'join_offsets': np.array(join_offsets, np.int64),
+            'joins': {k: np.array(joins[k], np.int64 if k in JOIN_INT else np.float64).reshape(-1) for k in joins},
+            'row_chain': row_chain, 'row_join': row_join, 'row_candidates': row_candidates,
+            'events': np.array(events, np.int64).reshape(-1, 4)}

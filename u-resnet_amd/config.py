@@ -191,6 +191,20 @@ class ssnet_config(object):
     VERTEX_RADIUS = 2
     VERTEX_MIN_SIZE = 3
     VERTEX_CLASSES = []
+    # ANA_CHAINS '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per chain: clusters that are fragments of one broken track,
+    # joined end to end across gaps of at most CHAIN_GAP voxels per axis when both axes and the gap vector are collinear within
+    # CHAIN_MIN_COS and the choice is mutual (ssnet_base.set_cluster_chains; clusters.cluster_chains_numpy holds the definition):
+    # entry, chain, the sixteen chain integers (rows, joins, entries, fixed-point charge, box, first row, the two end positions,
+    # sum and maximum of the squared gaps, class mask | flags << 32) and the five reals (path, gaps, span, straightness, smallest
+    # cosine between joined axes).  '' = off.  Refused without ANA_CLUSTER; ignored with TRAIN, like every ANA_* key.  CHAIN_GAP =
+    # 1 .. 31; CHAIN_MIN_COS = a float in [0, 1]; CHAIN_MIN_SIZE = smaller clusters are not joined; CHAIN_CLASSES = the classes whose
+    # clusters are joined, [] = all; CHAIN_SAME_CLASS = only clusters of equal class are joined
+    ANA_CHAINS = ''
+    CHAIN_GAP = 6
+    CHAIN_MIN_COS = 0.9
+    CHAIN_MIN_SIZE = 3
+    CHAIN_CLASSES = []
+    CHAIN_SAME_CLASS = True
 
     def __init__(self):
         pass
@@ -310,6 +324,18 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'VERTEX_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CHAIN_GAP' and not 1 <= value <= 31:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CHAIN_MIN_COS' and not 0.0 <= value <= 1.0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CHAIN_MIN_SIZE' and value < 1:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CHAIN_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'PROFILE_STEP' and not 0.5 <= value <= 4096.0:

@@ -220,6 +220,20 @@ def profiles_csv_row(entry, k, rows):
                     [repr(float(rows[name][k])) for name in PROFILE_ROW_REAL]) + '\n'
 
 
+def chains_csv_header():
+    """The header line of the ANA_CHAINS file: one row per chain."""
+    from .clusters import CHAIN_INT, CHAIN_REAL
+    return ','.join(('entry', 'chain') + CHAIN_INT + CHAIN_REAL) + '\n'
+
+
+def chains_csv_row(entry, k, chains):
+    """Chain ``k`` of one event's ``chains`` record (a dict of columns) as a CSV row: the integers, then the reals by ``repr``
+    (they parse back to the same bits)."""
+    from .clusters import CHAIN_INT, CHAIN_REAL
+    return ','.join(['%d' % entry, '%d' % k] + ['%d' % int(chains[name][k]) for name in CHAIN_INT] +
+                    [repr(float(chains[name][k])) for name in CHAIN_REAL]) + '\n'
+
+
 def vertices_csv_header():
     """The header line of the ANA_VERTICES file: one row per vertex."""
     from .clusters import VERTEX_INT, VERTEX_REAL
@@ -1137,6 +1151,14 @@ class ssnet_base(object):
                 self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
             vtx = self._enqueue_cluster_vertices(sess, d_offsets, d_index, pending, vtx_objects, pending[1], self._dims[:-1], vspec,
                                                  M, self._vertex_inc_cap(M))
+        cspec = getattr(self, '_cluster_chain_spec', None) if pending is not None else None
+        chain = None
+        if cspec is not None:                      # behind the object records, which run for it in any case
+            chain_objects = objects if objects is not None else prof_objects if pspec is not None else \
+                vtx_objects if vspec is not None else \
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+            chain = self._enqueue_cluster_chains(sess, d_offsets, d_index, pending, chain_objects, pending[1], self._dims[:-1],
+                                                 cspec, M)
         truth = match = None
         if matching:                               # the TRUE classes under the same spec, then the match of the two id arrays
             buf, at, nbytes = self._fed_label
@@ -1172,6 +1194,9 @@ class ssnet_base(object):
         if vtx is not None:
             records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, res['clusters'])
             res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, voxels, res, vspec, self._dims[:-1])
+        if chain is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, res['clusters'])
+            res['chains'] = self._fetch_cluster_chains(chain, records, off)
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1716,6 +1741,156 @@ class ssnet_base(object):
             if inc_cap >= 2 ** 30 - 1:
                 raise _lib.UrsnError('cluster_vertices: more than 2^30 - 1 distinct incidences')
             inc_cap = min(2 * inc_cap, 2 ** 30 - 1)
+
+    # ------------------------------------------------------------------------------------------
+    # cluster chains: broken track fragments joined end to end (definition and numpy statement: clusters.cluster_chains_numpy,
+    # device passes: csrc/cluster_chain.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_chains(self, spec):
+        """A ``clusters.ClusterChainSpec``: while one is set, and a cluster spec is set, and ``'cluster'`` is wanted,
+        ``inference_voxel_scores`` and ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_chains`` behind the cluster passes
+        and the object records (which run for it whether or not ``set_cluster_features`` is on; tiled: on the stitched list in the
+        large shape, so a track cut at a tile seam with lost voxels is joined), and the result gains ``chains``: what
+        ``cluster_chains`` returns.  No table of the call can overflow (there are at most as many chains and joins as clusters),
+        so nothing is ever made again.  None switches it off.  The legal members of ``want`` do not change; never called, the
+        results have the keys they had."""
+        from .clusters import ClusterChainSpec
+        if spec is not None and not isinstance(spec, ClusterChainSpec):
+            raise ValueError('set_cluster_chains: spec = %r, expected a clusters.ClusterChainSpec or None' % (spec,))
+        self._cluster_chain_spec = spec
+
+    def _enqueue_cluster_chains(self, sess, d_offsets, d_index, pending, objects, d_cls, shape, spec, rows):
+        """``ursn_cluster_chains`` behind ``_enqueue_cluster_features`` (whose tables stay on the device); ``rows`` bounds the
+        cluster rows (the list length when the count is still on the device); enqueues only."""
+        import torch
+        lib = _lib.load()
+        ints, _, toff, _, n, M = pending
+        itab, rtab, _ = objects
+        shape = [int(s) for s in shape]
+        rows = int(rows)
+        need = int(lib.ursn_cluster_chains_scratch_bytes(n, M))
+        if need == 0:
+            raise ValueError('cluster_chains: %d events with %d list entries are out of domain' % (n, M))
+        if d_cls is None and (spec.same_class or spec.classes is not None):
+            raise ValueError('cluster_chains: spec = %r needs the cluster table\'s cls' % (spec,))
+        new = lambda shp, dt: torch.empty(shp, dtype=dt, device=self._device)
+        cap = max(rows, 1)
+        scratch = new(need // 8, torch.int64)
+        merged, small = new(max(M, 1), torch.int32), new(2 * cap, torch.int32)                # small: first | size
+        coff, joff, ev, status = new(n + 1, torch.int64), new(n + 1, torch.int64), new((n, _lib.CLCHAIN_EV), torch.int64), \
+            new(1, torch.int32)
+        ccls = new(cap, torch.uint8)
+        ci, cr = new((cap, _lib.CLCHAIN_CI), torch.int64), new((cap, _lib.CLCHAIN_CR), torch.float64)
+        ji, jr = new((cap, _lib.CLCHAIN_JI), torch.int64), new((cap, _lib.CLCHAIN_JR), torch.float64)
+        rc, rj, rn = new(cap, torch.int32), new((cap, 2), torch.int32), new((cap, 2), torch.int32)
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_chain_desc()
+        d.ndim, d.n, d.m_total, d.max_gap = len(shape), n, M, spec.max_gap
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ints.data_ptr(), toff.data_ptr()
+        d.itab, d.rtab, d.feat_cap, d.cls = itab.data_ptr(), rtab.data_ptr(), M, ptr(d_cls)
+        d.min_cos, d.min_size, d.class_mask, d.same_class = spec.min_cos, spec.min_size, spec.class_mask(), int(spec.same_class)
+        o = _lib.ursn_cluster_chain_out()
+        o.merged, o.chain_offsets, o.first, o.size, o.cls = merged.data_ptr(), coff.data_ptr(), small.data_ptr(), \
+            small.data_ptr() + 4 * cap, ccls.data_ptr()
+        o.chain_itab, o.chain_rtab, o.cap_chains = ci.data_ptr(), cr.data_ptr(), rows
+        o.join_offsets, o.join_itab, o.join_rtab, o.cap_joins = joff.data_ptr(), ji.data_ptr(), jr.data_ptr(), rows
+        o.row_chain, o.row_join, o.row_candidates, o.cap_rows = rc.data_ptr(), rj.data_ptr(), rn.data_ptr(), rows
+        o.event, o.status = ev.data_ptr(), status.data_ptr()
+        _lib.check(lib.ursn_cluster_chains(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, merged, small, coff, joff, ev, status, ccls, ci, cr, ji, jr, rc, rj, rn, itab, rtab) + \
+                (() if d_cls is None or not hasattr(d_cls, 'record_stream') else (d_cls,)):
+            t.record_stream(cur)
+        return merged, small, ccls, coff, ci, cr, joff, ji, jr, rc, rj, rn, ev, status, cap, M
+
+    @staticmethod
+    def _fetch_cluster_chains(ch, objects, off):
+        """The chain tables as ``cluster_chains`` returns them (``objects``: what ``_fetch_cluster_features`` returned for the same
+        rows, ``off`` the list offsets)."""
+        from .clusters import CHAIN_EVENT, CHAIN_INT, CHAIN_REAL, JOIN_INT, JOIN_REAL
+        merged, small, ccls, coff, ci, cr, joff, ji, jr, rc, rj, rn, ev, status, cap, M = ch
+        code = int(status.cpu().numpy()[0])
+        if code != 0:
+            raise _lib.UrsnError('cluster_chains: the ids, table offsets, lists and object records disagree (status %d)' % code)
+        counts = [int(o['n'].shape[0]) for o in objects]
+        K = int(sum(counts))
+        coff, joff, ev = coff.cpu().numpy(), joff.cpu().numpy(), ev.cpu().numpy()
+        C, J = int(coff[-1]), int(joff[-1])
+        assert coff[0] == 0 and joff[0] == 0 and C <= K <= cap and J <= K, 'cluster_chains: %d chains and %d joins of %d rows' % (C, J, K)
+        merged, small, ccls = merged[:M].cpu().numpy(), small.cpu().numpy(), ccls[:C].cpu().numpy()
+        ci, cr, ji, jr = ci[:C].cpu().numpy(), cr[:C].cpu().numpy(), ji[:J].cpu().numpy(), jr[:J].cpu().numpy()
+        rc, rj, rn = rc[:K].cpu().numpy(), rj[:K].cpu().numpy(), rn[:K].cpu().numpy()
+        events, ids, tables, at = [], [], [], 0
+        for i, (o, k) in enumerate(zip(objects, counts)):
+            lo, hi, jlo, jhi = int(coff[i]), int(coff[i + 1]), int(joff[i]), int(joff[i + 1])
+            chains = {name: ci[lo:hi, c].copy() for c, name in enumerate(CHAIN_INT)}
+            chains.update({name: cr[lo:hi, c].copy() for c, name in enumerate(CHAIN_REAL)})
+            joins = {name: ji[jlo:jhi, c].copy() for c, name in enumerate(JOIN_INT)}
+            joins.update({name: jr[jlo:jhi, c].copy() for c, name in enumerate(JOIN_REAL)})
+            events.append({'objects': o, 'chains': chains, 'joins': joins, 'row_chain': rc[at:at + k].copy(),
+                           'row_join': rj[at:at + k].copy(), 'row_candidates': rn[at:at + k].copy(),
+                           'event': dict(zip(CHAIN_EVENT, (int(x) for x in ev[i])))})
+            ids.append(merged[off[i]:off[i + 1]].copy())
+            tables.append({'first': small[lo:hi].copy(), 'size': small[cap + lo:cap + hi].copy(), 'cls': ccls[lo:hi].copy()})
+            at += k
+        return {'events': events, 'cluster': ids, 'clusters': tables}
+
+    def cluster_chains(self, sess, voxels_or_lists, value, clusters, spec, shape=None):
+        """Chains of clusters already made: ``voxels_or_lists``, ``value``, ``clusters`` and ``shape`` as ``cluster_features`` takes
+        them, ``spec`` a ``clusters.ClusterChainSpec``.  Runs the object records and then the chains.  Returns ``{'events': [...],
+        'cluster': [...], 'clusters': [...]}``: per event a dict -- ``objects`` (as ``cluster_features``), ``chains`` (named columns
+        ``clusters.CHAIN_INT`` / ``CHAIN_REAL``, one row per chain), ``joins`` (``JOIN_INT`` / ``JOIN_REAL``, one row per join,
+        ascending ``key_a``), ``row_chain`` int32 [K_i], ``row_join`` / ``row_candidates`` int32 [K_i, 2] and ``event`` (a dict over
+        ``clusters.CHAIN_EVENT``) -- and, as ``cluster`` / ``clusters``, the chains as a clustering of the same lists: the merged
+        ids int32 [m_i] and the table ``first`` / ``size`` / ``cls``.  The returned dict is itself a legal ``clusters`` argument
+        of ``cluster_features``, ``cluster_profiles``, ``match_clusters``, ``cluster_graph`` and ``cluster_vertices``."""
+        import torch
+        from .clusters import ClusterChainSpec
+        if not isinstance(spec, ClusterChainSpec):
+            raise ValueError('cluster_chains: spec = %r, expected a clusters.ClusterChainSpec' % (spec,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_chains: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = voxels_or_lists.value
+        elif isinstance(voxels_or_lists, _DeviceVoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = self._resident_value(voxels_or_lists)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_chains: %d events outside [1, 65535]' % n)
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_chains: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids]) if n else np.zeros(0, np.int32)
+        if cluster.size != M or index.size != M or (value is not None and value.size != M):
+            raise ValueError('cluster_chains: %d list entries, %d indices, %d ids, %s values'
+                             % (M, index.size, cluster.size, 'no' if value is None else value.size))
+        toff = np.concatenate([[0], np.cumsum([int(t['first'].size) for t in tables])]).astype(np.int64)
+        K = int(toff[-1])
+        cls = np.concatenate([np.asarray(t['cls'], np.uint8).reshape(-1) for t in tables] + [np.zeros(1, np.uint8)])
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        d_off, d_index, d_toff, d_cls = up(off, np.int64), up(index, np.int32), up(toff, np.int64), up(cls, np.uint8)
+        d_cluster = up(cluster if M else np.zeros(1, np.int32), np.int32)
+        d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
+        pending = (d_cluster, None, d_toff, M, n, M)
+        dev_objects = self._enqueue_cluster_features(sess, d_off, d_index, d_value, pending, shape)
+        objects = self._fetch_cluster_features(dev_objects, tables)
+        ch = self._enqueue_cluster_chains(sess, d_off, d_index, pending, dev_objects, d_cls, shape, spec, K)
+        return self._fetch_cluster_chains(ch, objects, off)
 
     # ------------------------------------------------------------------------------------------
     # cluster matching (definition and numpy statement: clusters.cluster_match_numpy, device passes: csrc/cluster_match.hip)
@@ -2305,6 +2480,15 @@ class ssnet_base(object):
                                                pending, big)
             vtx = self._enqueue_cluster_vertices(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, vtx_objects,
                                                  pending[1], big, vspec, M, self._vertex_inc_cap(M))
+        cspec = getattr(self, '_cluster_chain_spec', None) if pending is not None else None
+        chain = None
+        if cspec is not None:                      # the stitched list, in the large shape: a track cut at a tile seam is joined
+            chain_objects = objects if objects is not None else prof_objects if pspec is not None else \
+                vtx_objects if vspec is not None else \
+                self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
+                                               pending, big)
+            chain = self._enqueue_cluster_chains(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, chain_objects,
+                                                 pending[1], big, cspec, M)
         truth = match = None
         if matching:                               # the large batch's own labels under the same spec, then the match
             at = big_batch.ptr['label'] - big_batch.dev.data_ptr()
@@ -2343,6 +2527,9 @@ class ssnet_base(object):
             lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
             res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, lists, res, vspec, big,
                                                             value=lambda: self._resident_value(big_batch))
+        if chain is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, res['clusters'])
+            res['chains'] = self._fetch_cluster_chains(chain, records, off)
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, profiles_csv_header, profiles_csv_row, vertices_csv_header, vertices_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, chains_csv_header, chains_csv_row, profiles_csv_header, profiles_csv_row, vertices_csv_header, vertices_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -88,6 +88,7 @@ class ssnet_trainval(object):
         self._graph = None
         self._profiles = None
         self._vertices = None
+        self._chains = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -190,6 +191,8 @@ class ssnet_trainval(object):
             raise ValueError('ANA_PROFILES needs ANA_CLUSTER: the charge profiles run along the axes of the clusters')
         if cfg.ANA_VERTICES and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_VERTICES needs ANA_CLUSTER: the vertices are where the end points of the clusters meet')
+        if cfg.ANA_CHAINS and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_CHAINS needs ANA_CLUSTER: the chains join the clusters that are fragments of one track')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -237,6 +240,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._vertices.write(vertices_csv_header())
                 self._vertices.flush()
+        if cfg.ANA_CHAINS and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_CHAINS) or os.path.getsize(cfg.ANA_CHAINS) == 0
+            self._chains = open(cfg.ANA_CHAINS, 'a')
+            if fresh:
+                self._chains.write(chains_csv_header())
+                self._chains.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -266,6 +275,10 @@ class ssnet_trainval(object):
             if self._vertices:               # default off: never called
                 from .clusters import ClusterVertexSpec
                 self._net.set_cluster_vertices(ClusterVertexSpec(cfg.VERTEX_RADIUS, cfg.VERTEX_MIN_SIZE, cfg.VERTEX_CLASSES or None))
+            if self._chains:                 # default off: never called
+                from .clusters import ClusterChainSpec
+                self._net.set_cluster_chains(ClusterChainSpec(cfg.CHAIN_GAP, cfg.CHAIN_MIN_COS, cfg.CHAIN_MIN_SIZE,
+                                                              cfg.CHAIN_CLASSES or None, cfg.CHAIN_SAME_CLASS))
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -616,6 +629,7 @@ class ssnet_trainval(object):
         self._write_graph(r, entries)
         self._write_profiles(r, entries)
         self._write_vertices(r, entries)
+        self._write_chains(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -633,6 +647,9 @@ class ssnet_trainval(object):
                         ev['profiles'] = r['profiles'][i]
                     if 'vertices' in r:
                         ev['vertices'] = r['vertices'][i]
+                    if 'chains' in r:
+                        ev['chains'] = {'merged': r['chains']['cluster'][i], 'table': r['chains']['clusters'][i],
+                                        **r['chains']['events'][i]}
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
             if 'match' in r:
                 result['match'] = r['match']
@@ -687,6 +704,16 @@ class ssnet_trainval(object):
                 self._vertices.write(vertices_csv_row(entries[i], k, cols))
         self._vertices.flush()
 
+    def _write_chains(self, r, entries):
+        """ANA_CHAINS: one CSV row per chain of every event of the result ``r``."""
+        if not getattr(self, '_chains', None) or 'chains' not in r:
+            return
+        for i in range(len(entries)):
+            cols = r['chains']['events'][i]['chains']
+            for k in range(int(cols['rows'].size)):
+                self._chains.write(chains_csv_row(entries[i], k, cols))
+        self._chains.flush()
+
     def _ana_step_tiled(self, vb, entries, batch_mode):
         """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
         (``inference_tiled_voxel_scores``).  Records and the interactive result are those of ``_ana_step_voxel_scores`` with
@@ -715,6 +742,7 @@ class ssnet_trainval(object):
         self._write_graph(r, entries)
         self._write_profiles(r, entries)
         self._write_vertices(r, entries)
+        self._write_chains(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -732,6 +760,9 @@ class ssnet_trainval(object):
                         ev['profiles'] = r['profiles'][i]
                     if 'vertices' in r:
                         ev['vertices'] = r['vertices'][i]
+                    if 'chains' in r:
+                        ev['chains'] = {'merged': r['chains']['cluster'][i], 'table': r['chains']['clusters'][i],
+                                        **r['chains']['events'][i]}
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
             if 'match' in r:
@@ -904,7 +935,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_vertices', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_vertices', '_chains', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
