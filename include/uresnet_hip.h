@@ -1406,6 +1406,133 @@ size_t ursn_cluster_chains_scratch_bytes(int32_t n, int64_t m_total);
 int ursn_cluster_chains(const ursn_cluster_chain_desc* d, const ursn_cluster_chain_out* out, void* scratch, size_t scratch_bytes,
                         void* stream);
 
+/* ---- cluster cones: shower fragments gathered to their primary (cluster_cone.hip) ------------------------------------------------------
+ * Appended functions and two structs only: URSN_ABI_VERSION stays 9.  (The section stands here, before the last one, for the reason
+ * the cluster-chains section gives.)
+ * An electromagnetic shower is one narrow start fragment with tens of small, disconnected fragments downstream of it: no axis to
+ * speak of, no end that faces anything, up to a radiation length away.  This call gathers them: every fragment (CHILD) looks for the
+ * end point (APEX) of a larger row inside whose cone it lies and LINKS to the nearest; the links form a forest, a SHOWER is a tree,
+ * and the showers come back as one more clustering of the same lists in the (cluster, table_offsets, first / size / cls) format of
+ * ursn_cluster_voxels, so every call that takes a clustering runs on them unchanged.  Input: as ursn_cluster_chains.
+ * uresnet_amd/clusters.py (cluster_cones_numpy) states every field operation by operation; the device gives the same bits.
+ *
+ * A global row C is CHILD-eligible when its object record has n >= min_size and, with class_mask != 0, bit cls[C] of class_mask is
+ * set.  A global row P is PARENT-eligible when n >= seed_size and end_lo != end_hi under the same class condition; it has two
+ * APEXES, at the list positions end_lo and end_hi, with the KEY 2 P + side (side 0 = end_lo) and the DIRECTION u = +axis at the lo
+ * end, -axis at the hi end (from the end into the row): the chains' end points.  A child is represented by its anchor m (itab[11..13]
+ * of its object record, the centroid rounded to a voxel).  Coordinates x[0..2] are the row-major coordinates of index[j] in `spatial`
+ * (2-D: x[2] = 0).  P OUTRANKS C when n_P > n_C, or n_P == n_C and P < C: a strict total order, so links never form a cycle.
+ * A CANDIDATE is a child C and an apex (P, side) of different rows of one event, P outranking C and, with same_class, of equal cls,
+ * with d = m_C - x(apex) as integers, every fp64 operation rounded on its own:
+ *   |d_a| <= reach on every axis   and   1 <= dist2 = d . d <= reach^2          s = sqrt((double)dist2)
+ *   t = (u[0] * d0 + u[1] * d1) + u[2] * d2          c_cone = t / s
+ *   c_ax = fabs((u[0] * a0 + u[1] * a1) + u[2] * a2)   a = axis of C; formed only when C is itself PARENT-eligible
+ * and ACCEPTED when c_cone >= min_cos and, where c_ax is formed, c_ax >= min_cos (a NaN rejects).  Every child counts its accepted
+ * candidates and takes as its PARENT apex the one smallest in (dist2, apex key): a LINK.  No mutual test: a parent may have many
+ * children, a row at most one parent.  The PRIMARY of a shower is its tree's root; a row's depth is its number of links to the root.
+ * Showers are numbered per event by their lowest row: shower_offsets[n + 1].  Every row below the row count is in exactly one shower.
+ * merged[j]: the event-local shower of cluster[j]'s row, -1 where cluster[j] is -1.  Shower table: first = the lowest event-local
+ * list position of a member, size = members, cls = cls of the PRIMARY (0 without cls).
+ * Shower record, URSN_CLCONE_SI int64:
+ *   [0] rows   [1] n, [2] charge   summed over the object records   [3..5] lo, [6..8] hi   the union of their boxes
+ *   [9] first_row, [10] primary   event-local rows   [11] start = the list position of the primary's apex on the START side: the side
+ *   with the larger summed n of its DIRECT children, among equals the side with more direct children, then side 0 (a primary that
+ *   is not parent-eligible: end_lo)   [12] depth   the largest of a row   [13] dist2_max   over the links   [14] primary_n
+ *   [15] class mask of the rows (0 without cls) | flags << 32; flag bit 0: the primary has direct children at both apexes; flag bit
+ *   1: a member row whose object record has flags != 0
+ * Shower record, URSN_CLCONE_SR fp64:  [0] primary_fraction = (double)primary_n / (double)n   [1] min_cos = the smallest c_cone,
+ *   [2] t_max = the largest t over the links, both +0.0 without links   [3] r_max = sqrt((double)dist2_max).
+ * Link record, CSR by event (link_offsets[n + 1]), ascending child row.  URSN_CLCONE_LI int64: [0] child (event-local row)
+ *   [1] apex (event-local key)   [2] dist2   [3] pos = list position of the apex   [4] shower (event-local)   [5] depth of the child.
+ *   URSN_CLCONE_LR fp64: [0] c_cone   [1] t   [2] r = s   [3] c_ax (+0.0 where it was not formed).
+ * Per row: row_shower int32; row_parent int32 = the event-local apex key, -1 for none; row_candidates int32; row_children int32 [2]
+ * = direct children at the lo / hi apex; row_depth int32.  Event record, URSN_CLCONE_EV int64: [0] showers   [1] links   [2] grouped
+ * (showers with rows >= 2)   [3] largest = the shower largest in (rows, n), the lowest id among equals; -1 without showers.
+ * What it does not decide: whether a linked fragment belongs to the shower stays the consumer's judgement; c_cone, t and r are there
+ * to cut on.
+ *
+ * Bounds with every extent <= 32768, m_total < 2^30 and K rows: at most K links (a row has at most one parent), so no table of
+ * this call can overflow; dist2 <= 127^2 = 16129; the packed word dist2 << 32 | apex key needs keys below 2^31, hence m_total < 2^30;
+ * the rows of a shower are distinct rows of one event, so n < 2^31 and |charge| <= 2^62; rows << 32 | n is below 2^63.
+ *
+ * Method: twelve launches (cluster_cone.hip lists them).  The apexes of the parent-eligible rows are marked, counted per tile of
+ * 64 entries, scanned by one workgroup and compacted in list order, so the compact array is sorted by event << 32 | index; for a
+ * child with anchor (m0, m1, m2) the apexes of plane m0 + d0 with x1 within reach are one contiguous range of it (a 2-D list runs as
+ * (s0, s1, 1)), found by a lower-bound binary search and filtered on x2, row, rank, class and the Euclidean bound.  One wave64 per
+ * child row, the lanes striding the 2 reach + 1 <= 255 planes (up to four trips), then a butterfly reduction of ONE packed minimum
+ * dist2 << 32 | apex key and of the accepted count: the wave owns its child, no atomics in the search (URSN_CLCONE_WAVE=0: one
+ * thread per child row takes its planes one after another; same bits).  Per row a walk up the parents for the root and the depth
+ * (rank strictly rises; capped at the row count) and an integer atomic minimum for the tree's lowest row; one-workgroup scans for
+ * the shower numbers and the link list; per row 64-bit INTEGER atomic adds / min / max / ors at agent scope onto its shower and its
+ * parent's counters (min_cos and t_max are strictly positive doubles: integer min / max on their bit patterns); per entry merged and
+ * an integer atomic minimum for first; one thread per shower and per link for the fp64 columns, under contract(off).  No float
+ * atomics.  Enqueues only, never synchronises; the scratch needs no initialisation; every device loop is bounded; the same arguments
+ * give the same bits.
+ *
+ * Rows considered: below min(table_offsets[n], feat_cap, m_total).  *status is 0, or: bit 0 an id outside [-1, K_e) or offsets that
+ * are not those of the lists, bit 1 a row without a member, bit 2 an index outside the volume at an entry with an id, bit 3 a bounded
+ * loop ran out, bit 4 a cls >= 32, bit 5 an end position of an otherwise parent-eligible row that is not a member of it or an anchor
+ * outside the volume, bit 6 table_offsets[n] > feat_cap (such a row takes no part and stays a shower of one, such an entry gets
+ * merged = -1; every entry with an id and every row is checked, and the bits are the same whenever the arguments are).  Showers,
+ * links and rows at or beyond cap_showers / cap_links / cap_rows are never written; everything below them is complete whatever the
+ * caps are; shower_offsets, link_offsets and the event records hold the true counts.  m_total = 0 or no clusters still writes
+ * *status, the offsets and the event records.  Null, misaligned, out-of-domain and too-small arguments are refused with a message
+ * that begins "cluster_cones:" before any launch. */
+#define URSN_CLCONE_SI 16   /* int64 columns of a shower record */
+#define URSN_CLCONE_SR 4    /* fp64 columns of a shower record */
+#define URSN_CLCONE_LI 6    /* int64 columns of a link record */
+#define URSN_CLCONE_LR 4    /* fp64 columns of a link record */
+#define URSN_CLCONE_EV 4    /* int64 columns of an event record */
+
+typedef struct ursn_cluster_cone_desc { /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t reach;                        /* 1..127 */
+  int64_t m_total;                      /* list entries, < 2^30 */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] strictly increasing per event */
+  const int32_t* cluster;               /* [m_total] as ursn_cluster_voxels wrote it */
+  const int64_t* table_offsets;         /* [n+1] as ursn_cluster_voxels wrote it */
+  const int64_t* itab;                  /* [feat_cap][URSN_CLFEAT_I] as ursn_cluster_features wrote it for these lists */
+  const double* rtab;                   /* [feat_cap][URSN_CLFEAT_R] */
+  int64_t feat_cap;                     /* the cap of those tables */
+  const uint8_t* cls;                   /* [K_total] the cluster table's cls, or null: every class mask is 0 */
+  double min_cos;                       /* (0, 1] */
+  int32_t min_size;                     /* >= 1: fewest members of a child */
+  uint32_t class_mask;                  /* 0: rows of every class take part; else bit cls[r] decides, and cls must be given */
+  int32_t same_class;                   /* 0 | 1: only rows of equal cls are linked, and cls must be given */
+  int32_t seed_size;                    /* >= 2: fewest members of a parent */
+} ursn_cluster_cone_desc;
+
+typedef struct ursn_cluster_cone_out { /* DEVICE pointers */
+  int32_t* merged;                      /* [m_total] */
+  int64_t* shower_offsets;              /* [n+1] */
+  int32_t* first;                       /* [cap_showers] the shower table, typed as ursn_cluster_out's */
+  int32_t* size;                        /* [cap_showers] */
+  uint8_t* cls;                         /* [cap_showers] */
+  int64_t* shower_itab;                 /* [cap_showers][URSN_CLCONE_SI] */
+  double* shower_rtab;                  /* [cap_showers][URSN_CLCONE_SR] */
+  int64_t cap_showers;
+  int64_t* link_offsets;                /* [n+1] */
+  int64_t* link_itab;                   /* [cap_links][URSN_CLCONE_LI] */
+  double* link_rtab;                    /* [cap_links][URSN_CLCONE_LR] */
+  int64_t cap_links;
+  int32_t* row_shower;                  /* [cap_rows] */
+  int32_t* row_parent;                  /* [cap_rows] */
+  int32_t* row_candidates;              /* [cap_rows] */
+  int32_t* row_children;                /* [cap_rows][2] */
+  int32_t* row_depth;                   /* [cap_rows] */
+  int64_t cap_rows;
+  int64_t* event;                       /* [n][URSN_CLCONE_EV] */
+  int32_t* status;                      /* [1] */
+} ursn_cluster_cone_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535] or m_total outside [0, 2^30).  Host logic only. */
+size_t ursn_cluster_cones_scratch_bytes(int32_t n, int64_t m_total);
+int ursn_cluster_cones(const ursn_cluster_cone_desc* d, const ursn_cluster_cone_out* out, void* scratch, size_t scratch_bytes,
+                       void* stream);
+
 /* ---- vertex candidates: where the end points of the object records meet (cluster_vertex.hip) ----------------------------------------
  * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
  * The step from objects to interactions: which ends meet at one point, how many objects leave it and at what angles, which objects

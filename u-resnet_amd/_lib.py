@@ -214,6 +214,24 @@ class ursn_cluster_chain_out(C.Structure):
                 ("status", C.c_void_p)]
 
 
+CLCONE_SI, CLCONE_SR, CLCONE_LI, CLCONE_LR, CLCONE_EV = 16, 4, 6, 4, 4   # URSN_CLCONE_*: columns of the shower, link and event records
+
+
+class ursn_cluster_cone_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("reach", C.c_int32), ("m_total", C.c_int64),
+                ("offsets", C.c_void_p), ("index", C.c_void_p), ("cluster", C.c_void_p), ("table_offsets", C.c_void_p),
+                ("itab", C.c_void_p), ("rtab", C.c_void_p), ("feat_cap", C.c_int64), ("cls", C.c_void_p), ("min_cos", C.c_double),
+                ("min_size", C.c_int32), ("class_mask", C.c_uint32), ("same_class", C.c_int32), ("seed_size", C.c_int32)]
+
+
+class ursn_cluster_cone_out(C.Structure):
+    _fields_ = [("merged", C.c_void_p), ("shower_offsets", C.c_void_p), ("first", C.c_void_p), ("size", C.c_void_p), ("cls", C.c_void_p),
+                ("shower_itab", C.c_void_p), ("shower_rtab", C.c_void_p), ("cap_showers", C.c_int64), ("link_offsets", C.c_void_p),
+                ("link_itab", C.c_void_p), ("link_rtab", C.c_void_p), ("cap_links", C.c_int64), ("row_shower", C.c_void_p),
+                ("row_parent", C.c_void_p), ("row_candidates", C.c_void_p), ("row_children", C.c_void_p), ("row_depth", C.c_void_p),
+                ("cap_rows", C.c_int64), ("event", C.c_void_p), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -344,6 +362,9 @@ _SIGS = {
     # cluster_chain.hip
     "ursn_cluster_chains_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "ursn_cluster_chains": (C.c_int, [C.POINTER(ursn_cluster_chain_desc), C.POINTER(ursn_cluster_chain_out), _P, C.c_size_t, _P]),
+    # cluster_cone.hip
+    "ursn_cluster_cones_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "ursn_cluster_cones": (C.c_int, [C.POINTER(ursn_cluster_cone_desc), C.POINTER(ursn_cluster_cone_out), _P, C.c_size_t, _P]),
     "ursn_cluster_graph_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_graph": (C.c_int, [C.POINTER(ursn_cluster_graph_desc), C.POINTER(ursn_cluster_graph_out), _P, C.c_size_t, _P]),
 }

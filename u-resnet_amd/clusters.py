@@ -1370,3 +1370,309 @@ def cluster_chains_numpy(offsets, index, value, cluster, table_offsets, spatial,
             'joins': {k: np.array(joins[k], np.int64 if k in JOIN_INT else np.float64).reshape(-1) for k in joins},
             'row_chain': row_chain, 'row_join': row_join, 'row_candidates': row_candidates,
             'events': np.array(events, np.int64).reshape(-1, 4)}
+
+
+# ---- cluster cones: shower fragments gathered to their primary (csrc/cluster_cone.hip does it on the device; this is the statement) --
+CONE_INT = ('rows', 'n', 'charge', 'lo0', 'lo1', 'lo2', 'hi0', 'hi1', 'hi2', 'first_row', 'primary', 'start', 'depth', 'dist2_max',
+            'primary_n', 'mask_flags')
+CONE_REAL = ('primary_fraction', 'min_cos', 't_max', 'r_max')
+LINK_INT = ('child', 'apex', 'dist2', 'pos', 'shower', 'depth')
+LINK_REAL = ('c_cone', 't', 'r', 'c_ax')
+CONE_EVENT = ('showers', 'links', 'grouped', 'largest')
+CONE_MAX_REACH = 127
+
+
+class ClusterConeSpec(object):
+    """``reach`` in [1, 127]: the largest distance from an apex to a child's anchor (per axis and Euclidean); ``min_cos`` a finite
+    float in (0, 1]: the smallest accepted cosine, of the cone and, for a child with an axis of its own, of the two axes;
+    ``seed_size`` >= 2: rows with fewer members are no parent; ``min_size`` >= 1: rows with fewer members are no child;
+    ``classes`` None = rows of every class, else distinct class numbers in [0, 32): only rows of these classes take part (needs the
+    table's cls); ``same_class`` True = only rows of equal class are linked (needs the table's cls)."""
+
+    def __init__(self, reach=48, min_cos=0.8, seed_size=8, min_size=1, classes=None, same_class=True):
+        if type(reach) is not int or not 1 <= reach <= CONE_MAX_REACH:
+            raise ValueError('ClusterConeSpec: reach = %r, expected an integer in [1, %d]' % (reach, CONE_MAX_REACH))
+        if type(min_cos) not in (int, float) or not np.isfinite(min_cos) or not 0.0 < min_cos <= 1.0:
+            raise ValueError('ClusterConeSpec: min_cos = %r, expected a finite float in (0, 1]' % (min_cos,))
+        if type(seed_size) is not int or not 2 <= seed_size < 2 ** 31:
+            raise ValueError('ClusterConeSpec: seed_size = %r, expected an integer >= 2' % (seed_size,))
+        if type(min_size) is not int or not 1 <= min_size < 2 ** 31:
+            raise ValueError('ClusterConeSpec: min_size = %r, expected an integer >= 1' % (min_size,))
+        if classes is not None:
+            given = classes
+            try:
+                classes = tuple(classes)
+            except TypeError:
+                classes = ()
+            if not classes or any(type(c) is not int or not 0 <= c < 32 for c in classes) or len(set(classes)) != len(classes):
+                raise ValueError('ClusterConeSpec: classes = %r, expected None or distinct integers in [0, 32)' % (given,))
+        if type(same_class) is not bool:
+            raise ValueError('ClusterConeSpec: same_class = %r, expected a bool' % (same_class,))
+        self.reach, self.min_cos, self.seed_size, self.min_size = reach, float(min_cos), seed_size, min_size
+        self.classes, self.same_class = classes, same_class
+
+    def class_mask(self):
+        """Bit k set = rows of class k take part; 0 = every class."""
+        m = 0
+        for c in self.classes or ():
+            m |= 1 << c
+        return m
+
+    def __repr__(self):
+        return 'ClusterConeSpec(reach=%r, min_cos=%r, seed_size=%r, min_size=%r, classes=%r, same_class=%r)' % (
+            self.reach, self.min_cos, self.seed_size, self.min_size, self.classes, self.same_class)
+
+
+def cone_link(u, a, d):
+    """(t, c_cone, c_ax) of a candidate: ``u`` the direction of the apex, ``a`` the axis of the child or None when the child has
+    none to speak of (c_ax is then +0.0), ``d`` = anchor(child) - x(apex) as integers.  Every line is one fp64 operation rounded on
+    its own; the device follows it."""
+    dist2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        s = np.sqrt(np.float64(dist2))
+        f = [np.float64(x) for x in d]
+        t = (u[0] * f[0] + u[1] * f[1]) + u[2] * f[2]
+        c_cone = t / s
+        c_ax = np.float64(0.0) if a is None else np.fabs((u[0] * a[0] + u[1] * a[1]) + u[2] * a[2])
+    return t, c_cone, c_ax
+
+
+def cluster_cones_numpy(offsets, index, value, cluster, table_offsets, spatial, spec, cls=None):
+    """The statement of the shower cones of concatenated per-event lists: which clusters are fragments of one electromagnetic
+    shower, gathered to the cluster they came from.  Slow on purpose, in the style of ``cluster_chains_numpy``: it calls
+    ``cluster_features_numpy`` first (returned under ``objects``); Python integers, scalar fp64 operations each rounded on its own.
+
+    ELIGIBILITY.  A global row C is CHILD-eligible when its object record has n >= ``spec.min_size`` and, with ``spec.classes``,
+    ``cls[C]`` is one of them.  A global row P is PARENT-eligible when n >= ``spec.seed_size`` and end_lo != end_hi under the same
+    class condition.  A parent has two APEXES, at the list positions ``end_lo[P]`` and ``end_hi[P]``, with the KEY 2 P + side (side
+    0 = end_lo) and the DIRECTION u = +axis[P] at the lo end, -axis[P] (unary minus) at the hi end: from the end into the row.  A
+    child is represented by its anchor ``m[C]``.  Coordinates are ``np.unravel_index(index, spatial)`` with x[2] = 0 in 2-D.
+
+    RANK.  P OUTRANKS C when n_P > n_C, or n_P == n_C and P < C: a strict total order, so links never form a cycle.
+
+    CANDIDATES.  A child C and an apex (P, side) of different rows of one event, P outranking C and, with ``spec.same_class``, of
+    equal ``cls``; d = m[C] - x(apex) as integers with |d_a| <= reach on every axis and 1 <= dist2 = d . d <= reach^2.
+    ``cone_link``: s = sqrt(float64(dist2)); t = (u[0] * d0 + u[1] * d1) + u[2] * d2; c_cone = t / s; c_ax = fabs((u[0] * a0 +
+    u[1] * a1) + u[2] * a2) with a = axis[C], formed only when C is itself PARENT-eligible.  ACCEPTED when c_cone >= min_cos and,
+    where c_ax is formed, c_ax >= min_cos (a NaN rejects).
+
+    LINKS.  Every child counts its accepted candidates (``row_candidates``) and takes as its PARENT apex the accepted candidate
+    smallest in (dist2, apex key): a LINK.  No mutual test: a parent may have many children; a row has at most one parent.
+
+    SHOWERS.  The links form a forest; a SHOWER is a tree, its PRIMARY the root, a row's ``depth`` its links to the root.  Showers
+    are numbered per event by their lowest row, ``shower_offsets`` [n + 1]; a row with no link at all is a shower of one.
+    ``merged[j]`` is the event-local shower of ``cluster[j]``'s row, -1 where ``cluster[j]`` is -1.  ``table``: ``first`` int32 =
+    the lowest event-local list position of a member, ``size`` int32 = members, ``cls`` uint8 = ``cls`` of the PRIMARY (0 without
+    ``cls``): (merged, shower_offsets, table) is a clustering in the format ``ursn_cluster_voxels`` writes.
+
+    CONE_INT: ``rows``; ``n`` / ``charge`` summed over the object records; ``lo0..2`` / ``hi0..2`` the union of their boxes;
+    ``first_row`` (event-local lowest row); ``primary`` (event-local); ``start`` = the list position of the primary's apex on the
+    START side: the side with the larger summed n of its DIRECT children, among equals the side with more direct children, then
+    side 0 (a primary that is not parent-eligible: end_lo); ``depth`` the largest of a row; ``dist2_max`` over the links;
+    ``primary_n``; ``mask_flags`` = the class mask of the rows (0 without ``cls``) | flags << 32, flag bit 0: the primary has direct
+    children at both apexes, flag bit 1: a member row whose object record has flags != 0.  CONE_REAL: ``primary_fraction`` =
+    float64(primary_n) / float64(n); ``min_cos`` the smallest c_cone and ``t_max`` the largest t over the links, +0.0 without;
+    ``r_max`` = sqrt(float64(dist2_max)).
+
+    LINK LIST, CSR by event (``link_offsets`` [n + 1]), ascending child row.  LINK_INT: ``child`` (event-local row), ``apex``
+    (event-local key), ``dist2``, ``pos`` (list position of the apex), ``shower`` (event-local), ``depth`` (of the child).
+    LINK_REAL: ``c_cone``, ``t``, ``r`` = s, ``c_ax`` (+0.0 where it was not formed).  Per row: ``row_shower`` int32 [K];
+    ``row_parent`` int32 [K] the event-local apex key, -1 for none; ``row_candidates`` int32 [K]; ``row_children`` int32 [K, 2]
+    direct children at the lo / hi apex; ``row_depth`` int32 [K].  CONE_EVENT: ``showers``, ``links``, ``grouped`` (showers with
+    rows >= 2), ``largest`` = the shower largest in (rows, n), the lowest id among equals, -1 without showers.
+
+    Bounds, with K rows: at most K links (a row has at most one parent); dist2 <= 127^2 = 16129; fewer than 2^30 entries so that
+    dist2 << 32 | apex key fits a 64-bit word with keys below 2^31; n < 2^31 and |charge| <= 2^62.
+
+    An id outside its event's rows, a row without a member, an index outside the volume at an entry with an id, an end position of
+    a parent-eligible row that is not a member of it and a cls >= 32 raise ValueError.  Returns a dict: ``objects``;
+    ``shower_offsets`` int64 [n + 1]; ``merged`` int32 [m]; ``table`` {first, size, cls}; ``showers`` {name: [S]} over CONE_INT
+    (int64) and CONE_REAL (float64); ``link_offsets`` int64 [n + 1]; ``links`` {name: [L]} over LINK_INT / LINK_REAL;
+    ``row_shower``; ``row_parent``; ``row_candidates``; ``row_children``; ``row_depth``; ``events`` int64 [n, 4]."""
+    if not isinstance(spec, ClusterConeSpec):
+        raise ValueError('cluster_cones_numpy: spec = %r, expected a ClusterConeSpec' % (spec,))
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or any(not 1 <= s <= MAX_EXTENT for s in spatial):
+        raise ValueError('cluster_cones_numpy: spatial = %r, expected 2 or 3 extents in [1, %d]' % (spatial, MAX_EXTENT))
+    off = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    idx = [int(x) for x in np.asarray(index).reshape(-1)]
+    ids = [int(x) for x in np.asarray(cluster).reshape(-1)]
+    nev, m, ndim, reach = len(off) - 1, len(idx), len(spatial), spec.reach
+    if nev < 1 or len(toff) != nev + 1 or len(ids) != m or off[0] != 0 or off[-1] != m or toff[0] != 0 \
+            or any(off[e + 1] < off[e] or toff[e + 1] < toff[e] for e in range(nev)):
+        raise ValueError('cluster_cones_numpy: offsets, table offsets and the lists disagree')
+    K = toff[-1]
+    if cls is not None:
+        cls = [int(c) for c in np.asarray(cls).reshape(-1)]
+        if len(cls) != K or any(not 0 <= c < 32 for c in cls):
+            raise ValueError('cluster_cones_numpy: cls must hold %d classes in [0, 32)' % K)
+    if spec.classes is not None and cls is None:
+        raise ValueError('cluster_cones_numpy: spec.classes = %r needs the cluster table\'s cls' % (spec.classes,))
+    if spec.same_class and cls is None:
+        raise ValueError('cluster_cones_numpy: spec.same_class needs the cluster table\'s cls')
+    vox = 1
+    for s in spatial:
+        vox *= s
+
+    def coords_of(j):
+        x = tuple(int(c) for c in np.unravel_index(idx[j], spatial))
+        return x + (0,) * (3 - ndim)
+
+    first_pos = [None] * K                                # the lowest event-local position of a member
+    for e in range(nev):
+        for j in range(off[e], off[e + 1]):
+            if ids[j] < 0:
+                continue
+            if not ids[j] < toff[e + 1] - toff[e]:
+                raise ValueError('cluster_cones_numpy: entry %d has id %d, its event has %d clusters' % (j, ids[j], toff[e + 1] - toff[e]))
+            if not 0 <= idx[j] < vox:
+                raise ValueError('cluster_cones_numpy: entry %d has index %d outside the volume %r' % (j, idx[j], spatial))
+            r = toff[e] + ids[j]
+            if first_pos[r] is None:
+                first_pos[r] = j - off[e]
+    f = cluster_features_numpy(offsets, index, value, cluster, table_offsets, spatial)    # raises on a row without a member
+    event_of = [e for e in range(nev) for _ in range(toff[e + 1] - toff[e])]
+    mask, min_cos = spec.class_mask(), np.float64(spec.min_cos)
+    size = [int(f['n'][r]) for r in range(K)]
+    anchor = [tuple(int(t) for t in f['m'][r]) for r in range(K)]
+    in_class = [not mask or bool((mask >> cls[r]) & 1) for r in range(K)]
+    child_ok = [size[r] >= spec.min_size and in_class[r] for r in range(K)]
+    parent_ok = [size[r] >= spec.seed_size and int(f['end_lo'][r]) != int(f['end_hi'][r]) and in_class[r] for r in range(K)]
+    axis = [[np.float64(t) for t in f['axis'][r]] for r in range(K)]
+    pos_of, xs, us = {}, {}, {}                           # apex key -> list position, coordinates, direction
+    cells = [{} for _ in range(nev)]                      # per event: (x // reach on every axis) -> apex keys, ascending
+    for r in range(K):
+        if not parent_ok[r]:
+            continue
+        e = event_of[r]
+        for side, p in ((0, int(f['end_lo'][r])), (1, int(f['end_hi'][r]))):
+            if not off[e] <= p < off[e + 1] or ids[p] != r - toff[e]:
+                raise ValueError('cluster_cones_numpy: the end position %d of row %d is not a member of it' % (p, r))
+            k = 2 * r + side
+            pos_of[k], xs[k], us[k] = p, coords_of(p), (axis[r] if side == 0 else [-t for t in axis[r]])
+            cells[e].setdefault(tuple(c // reach for c in xs[k]), []).append(k)
+    ncand = [0] * K
+    link = [None] * K                                     # child row -> (dist2, apex key, t, c_cone, c_ax)
+    for c in range(K):
+        if not child_ok[c]:
+            continue
+        e, mc = event_of[c], anchor[c]
+        home = tuple(t // reach for t in mc)
+        for g0 in (home[0] - 1, home[0], home[0] + 1):
+            for g1 in (home[1] - 1, home[1], home[1] + 1):
+                for g2 in (home[2] - 1, home[2], home[2] + 1):
+                    for k in cells[e].get((g0, g1, g2), ()):
+                        p = k >> 1
+                        if p == c or not (size[p] > size[c] or (size[p] == size[c] and p < c)):
+                            continue
+                        if spec.same_class and cls[p] != cls[c]:
+                            continue
+                        d = [mc[a] - xs[k][a] for a in range(3)]
+                        dist2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+                        if any(abs(t) > reach for t in d) or not 1 <= dist2 <= reach * reach:
+                            continue
+                        t, c_cone, c_ax = cone_link(us[k], axis[c] if parent_ok[c] else None, d)
+                        if not c_cone >= min_cos or (parent_ok[c] and not c_ax >= min_cos):
+                            continue
+                        ncand[c] += 1
+                        if link[c] is None or (dist2, k) < link[c][:2]:
+                            link[c] = (dist2, k, t, c_cone, c_ax)
+    assert all(lk is None or 1 <= lk[0] <= CONE_MAX_REACH ** 2 for lk in link)
+    root, depth = [0] * K, [0] * K
+    for r in range(K):
+        x, h = r, 0
+        while link[x] is not None:                        # rank strictly rises: the walk ends
+            x, h = link[x][1] >> 1, h + 1
+            assert h <= K
+        root[r], depth[r] = x, h
+    lowest = {}                                           # root -> the lowest row of its tree
+    for r in range(K):
+        lowest.setdefault(root[r], r)
+    shower_of, shower_offsets, members = [0] * K, [0], []  # members[s]: the rows of global shower s, ascending
+    for e in range(nev):
+        for r in range(toff[e], toff[e + 1]):
+            if lowest[root[r]] == r:
+                lowest[root[r]] = -1 - len(members)       # from now on: the shower's number
+                members.append([])
+            shower_of[r] = -1 - lowest[root[r]]
+            members[shower_of[r]].append(r)
+        shower_offsets.append(len(members))
+    S = len(members)
+    merged = np.full(m, -1, np.int32)
+    for e in range(nev):
+        for j in range(off[e], off[e + 1]):
+            if ids[j] >= 0:
+                merged[j] = shower_of[toff[e] + ids[j]] - shower_offsets[e]
+    row_shower = np.array([shower_of[r] - shower_offsets[event_of[r]] for r in range(K)], np.int32).reshape(K)
+    row_parent = np.array([-1 if link[r] is None else link[r][1] - 2 * toff[event_of[r]] for r in range(K)], np.int32).reshape(K)
+    row_candidates = np.array(ncand, np.int32).reshape(K)
+    row_depth = np.array(depth, np.int32).reshape(K)
+    row_children = np.zeros((K, 2), np.int32)
+    child_n = [[0, 0] for _ in range(K)]                  # summed n of the direct children at the lo / hi apex
+    for r in range(K):
+        if link[r] is not None:
+            k = link[r][1]
+            row_children[k >> 1][k & 1] += 1
+            child_n[k >> 1][k & 1] += size[r]
+    showers = {name: [] for name in CONE_INT + CONE_REAL}
+    table = {'first': [], 'size': [], 'cls': []}
+    events = [[shower_offsets[e + 1] - shower_offsets[e], 0, 0, -1] for e in range(nev)]
+    largest = [None] * nev
+    zero = np.float64(0.0)
+    for s in range(S):
+        rows = members[s]
+        e, prim = event_of[rows[0]], root[rows[0]]
+        n_sum = sum(size[r] for r in rows)
+        q_sum = sum(int(f['charge'][r]) for r in rows)
+        links = [link[r] for r in rows if link[r] is not None]
+        cmask = flags = 0
+        for r in rows:
+            if cls is not None:
+                cmask |= 1 << cls[r]
+            if int(f['flags'][r]) != 0:
+                flags |= 2
+        kids = row_children[prim]
+        if kids[0] > 0 and kids[1] > 0:
+            flags |= 1
+        side = 0
+        if parent_ok[prim]:
+            if child_n[prim][1] > child_n[prim][0] or (child_n[prim][1] == child_n[prim][0] and kids[1] > kids[0]):
+                side = 1
+        start = int(f['end_hi' if side else 'end_lo'][prim])
+        d2max = max([lk[0] for lk in links] + [0])
+        assert n_sum < 2 ** 31 and abs(q_sum) <= 2 ** 62 and len(links) == len(rows) - 1
+        ints = [len(rows), n_sum, q_sum] + [min(int(f['lo'][r][a]) for r in rows) for a in range(3)] + \
+            [max(int(f['hi'][r][a]) for r in rows) for a in range(3)] + \
+            [rows[0] - toff[e], prim - toff[e], start, max(depth[r] for r in rows), d2max, size[prim], cmask | flags << 32]
+        reals = [np.float64(size[prim]) / np.float64(n_sum), min([lk[3] for lk in links]) if links else zero,
+                 max([lk[2] for lk in links]) if links else zero, np.sqrt(np.float64(d2max))]
+        for name, val in zip(CONE_INT + CONE_REAL, ints + reals):
+            showers[name].append(val)
+        table['first'].append(min(first_pos[r] for r in rows))
+        table['size'].append(n_sum)
+        table['cls'].append(cls[prim] if cls is not None else 0)
+        events[e][1] += len(links)
+        events[e][2] += 1 if len(rows) >= 2 else 0
+        if largest[e] is None or (len(rows), n_sum) > largest[e]:             # ascending id: a strict comparison keeps the lowest
+            largest[e], events[e][3] = (len(rows), n_sum), s - shower_offsets[e]
+    links = {name: [] for name in LINK_INT + LINK_REAL}
+    link_offsets = [0]
+    for e in range(nev):
+        for r in range(toff[e], toff[e + 1]):             # ascending child row
+            if link[r] is not None:
+                dist2, k, t, c_cone, c_ax = link[r]
+                vals = [r - toff[e], k - 2 * toff[e], dist2, pos_of[k], shower_of[r] - shower_offsets[e], depth[r], c_cone, t,
+                        np.sqrt(np.float64(dist2)), c_ax]
+                for name, val in zip(LINK_INT + LINK_REAL, vals):
+                    links[name].append(val)
+        link_offsets.append(len(links['child']))
+    assert link_offsets[-1] <= K
+    return {'objects': f, 'shower_offsets': np.array(shower_offsets, np.int64), 'merged': merged,
+            'table': {'first': np.array(table['first'], np.int32).reshape(-1), 'size': np.array(table['size'], np.int32).reshape(-1),
+                      'cls': np.array(table['cls'], np.uint8).reshape(-1)},
+            'showers': {k: np.array(showers[k], np.int64 if k in CONE_INT else np.float64).reshape(-1) for k in showers},
+            'link_offsets': np.array(link_offsets, np.int64),
+            'links': {k: np.array(links[k], np.int64 if k in LINK_INT else np.float64).reshape(-1) for k in links},
+            'row_shower': row_shower, 'row_parent': row_parent, 'row_candidates': row_candidates, 'row_children': row_children,
+            'row_depth': row_depth, 'events': np.array(events, np.int64).reshape(-1, 4)}

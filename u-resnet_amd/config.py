@@ -205,6 +205,22 @@ class ssnet_config(object):
     CHAIN_MIN_SIZE = 3
     CHAIN_CLASSES = []
     CHAIN_SAME_CLASS = True
+    # ANA_CONES '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per shower: clusters that are fragments of one
+    # electromagnetic shower, each linked to the nearest end point of a larger cluster within CONE_REACH voxels inside whose cone
+    # of cosine CONE_MIN_COS it lies (ssnet_base.set_cluster_cones; clusters.cluster_cones_numpy holds the definition): entry,
+    # shower, the sixteen shower integers (rows, entries, fixed-point charge, box, first row, primary, start position, depth,
+    # largest squared distance, entries of the primary, class mask | flags << 32) and the four reals (primary fraction, smallest
+    # cone cosine, largest axial distance, largest distance).  '' = off.  Refused without ANA_CLUSTER; ignored with TRAIN, like
+    # every ANA_* key.  CONE_REACH = 1 .. 127; CONE_MIN_COS = a float in (0, 1]; CONE_SEED_SIZE = smaller clusters are no parent
+    # (>= 2); CONE_MIN_SIZE = smaller clusters are no child; CONE_CLASSES = the classes whose clusters take part, [] = all;
+    # CONE_SAME_CLASS = only clusters of equal class are linked
+    ANA_CONES = ''
+    CONE_REACH = 48
+    CONE_MIN_COS = 0.8
+    CONE_SEED_SIZE = 8
+    CONE_MIN_SIZE = 1
+    CONE_CLASSES = []
+    CONE_SAME_CLASS = True
 
     def __init__(self):
         pass
@@ -336,6 +352,21 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'CHAIN_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CONE_REACH' and not 1 <= value <= 127:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CONE_MIN_COS' and not 0.0 < value <= 1.0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CONE_SEED_SIZE' and value < 2:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CONE_MIN_SIZE' and value < 1:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'CONE_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'PROFILE_STEP' and not 0.5 <= value <= 4096.0:

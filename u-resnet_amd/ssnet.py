@@ -234,6 +234,20 @@ def chains_csv_row(entry, k, chains):
                     [repr(float(chains[name][k])) for name in CHAIN_REAL]) + '\n'
 
 
+def cones_csv_header():
+    """The header line of the ANA_CONES file: one row per shower."""
+    from .clusters import CONE_INT, CONE_REAL
+    return ','.join(('entry', 'shower') + CONE_INT + CONE_REAL) + '\n'
+
+
+def cones_csv_row(entry, k, showers):
+    """Shower ``k`` of one event's ``showers`` record (a dict of columns) as a CSV row: the integers, then the reals by ``repr``
+    (which parses back to the same double)."""
+    from .clusters import CONE_INT, CONE_REAL
+    return ','.join(['%d' % entry, '%d' % k] + ['%d' % int(showers[name][k]) for name in CONE_INT] +
+                    [repr(float(showers[name][k])) for name in CONE_REAL]) + '\n'
+
+
 def vertices_csv_header():
     """The header line of the ANA_VERTICES file: one row per vertex."""
     from .clusters import VERTEX_INT, VERTEX_REAL
@@ -1159,6 +1173,14 @@ class ssnet_base(object):
                 self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
             chain = self._enqueue_cluster_chains(sess, d_offsets, d_index, pending, chain_objects, pending[1], self._dims[:-1],
                                                  cspec, M)
+        nspec = getattr(self, '_cluster_cone_spec', None) if pending is not None else None
+        cone = None
+        if nspec is not None:                      # behind the object records, which run for it in any case
+            cone_objects = objects if objects is not None else prof_objects if pspec is not None else \
+                vtx_objects if vspec is not None else chain_objects if cspec is not None else \
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+            cone = self._enqueue_cluster_cones(sess, d_offsets, d_index, pending, cone_objects, pending[1], self._dims[:-1],
+                                               nspec, M)
         truth = match = None
         if matching:                               # the TRUE classes under the same spec, then the match of the two id arrays
             buf, at, nbytes = self._fed_label
@@ -1197,6 +1219,9 @@ class ssnet_base(object):
         if chain is not None:
             records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, res['clusters'])
             res['chains'] = self._fetch_cluster_chains(chain, records, off)
+        if cone is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(cone_objects, res['clusters'])
+            res['cones'] = self._fetch_cluster_cones(cone, records, off)
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
         return res
@@ -1893,6 +1918,162 @@ class ssnet_base(object):
         return self._fetch_cluster_chains(ch, objects, off)
 
     # ------------------------------------------------------------------------------------------
+    # cluster cones: shower fragments gathered to their primary (definition and numpy statement: clusters.cluster_cones_numpy,
+    # device passes: csrc/cluster_cone.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_cones(self, spec):
+        """A ``clusters.ClusterConeSpec``: while one is set, and a cluster spec is set, and ``'cluster'`` is wanted,
+        ``inference_voxel_scores`` and ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_cones`` behind the cluster passes
+        and the object records (which run for it whether or not ``set_cluster_features`` is on; tiled: on the stitched list in the
+        large shape, so a shower crosses tile seams), and the result gains ``cones``: what ``cluster_cones`` returns.  No table of
+        the call can overflow (there are at most as many showers and links as clusters), so nothing is ever made again.  None
+        switches it off.  The legal members of ``want`` do not change; never called, the results have the keys they had."""
+        from .clusters import ClusterConeSpec
+        if spec is not None and not isinstance(spec, ClusterConeSpec):
+            raise ValueError('set_cluster_cones: spec = %r, expected a clusters.ClusterConeSpec or None' % (spec,))
+        self._cluster_cone_spec = spec
+
+    def _enqueue_cluster_cones(self, sess, d_offsets, d_index, pending, objects, d_cls, shape, spec, rows):
+        """``ursn_cluster_cones`` behind ``_enqueue_cluster_features`` (whose tables stay on the device); ``rows`` bounds the
+        cluster rows (the list length when the count is still on the device); enqueues only."""
+        import torch
+        lib = _lib.load()
+        ints, _, toff, _, n, M = pending
+        itab, rtab, _ = objects
+        shape = [int(s) for s in shape]
+        rows = int(rows)
+        need = int(lib.ursn_cluster_cones_scratch_bytes(n, M))
+        if need == 0:
+            raise ValueError('cluster_cones: %d events with %d list entries are out of domain' % (n, M))
+        if d_cls is None and (spec.same_class or spec.classes is not None):
+            raise ValueError('cluster_cones: spec = %r needs the cluster table\'s cls' % (spec,))
+        new = lambda shp, dt: torch.empty(shp, dtype=dt, device=self._device)
+        cap = max(rows, 1)
+        scratch = new(need // 8, torch.int64)
+        merged, small = new(max(M, 1), torch.int32), new(2 * cap, torch.int32)                # small: first | size
+        soff, loff, ev, status = new(n + 1, torch.int64), new(n + 1, torch.int64), new((n, _lib.CLCONE_EV), torch.int64), \
+            new(1, torch.int32)
+        scls = new(cap, torch.uint8)
+        si, sr = new((cap, _lib.CLCONE_SI), torch.int64), new((cap, _lib.CLCONE_SR), torch.float64)
+        li, lr = new((cap, _lib.CLCONE_LI), torch.int64), new((cap, _lib.CLCONE_LR), torch.float64)
+        rows5 = new((6, cap), torch.int32)                 # row_shower | row_parent | row_candidates | row_depth | row_children [cap, 2]
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_cone_desc()
+        d.ndim, d.n, d.m_total, d.reach = len(shape), n, M, spec.reach
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ints.data_ptr(), toff.data_ptr()
+        d.itab, d.rtab, d.feat_cap, d.cls = itab.data_ptr(), rtab.data_ptr(), M, ptr(d_cls)
+        d.min_cos, d.min_size, d.class_mask, d.same_class = spec.min_cos, spec.min_size, spec.class_mask(), int(spec.same_class)
+        d.seed_size = spec.seed_size
+        o = _lib.ursn_cluster_cone_out()
+        o.merged, o.shower_offsets, o.first, o.size, o.cls = merged.data_ptr(), soff.data_ptr(), small.data_ptr(), \
+            small.data_ptr() + 4 * cap, scls.data_ptr()
+        o.shower_itab, o.shower_rtab, o.cap_showers = si.data_ptr(), sr.data_ptr(), rows
+        o.link_offsets, o.link_itab, o.link_rtab, o.cap_links = loff.data_ptr(), li.data_ptr(), lr.data_ptr(), rows
+        at = rows5.data_ptr()
+        o.row_shower, o.row_parent, o.row_candidates, o.row_depth, o.row_children = at, at + 4 * cap, at + 8 * cap, at + 12 * cap, \
+            at + 16 * cap
+        o.cap_rows = rows
+        o.event, o.status = ev.data_ptr(), status.data_ptr()
+        _lib.check(lib.ursn_cluster_cones(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, merged, small, soff, loff, ev, status, scls, si, sr, li, lr, rows5, itab, rtab) + \
+                (() if d_cls is None or not hasattr(d_cls, 'record_stream') else (d_cls,)):
+            t.record_stream(cur)
+        return merged, small, scls, soff, si, sr, loff, li, lr, rows5, ev, status, cap, M
+
+    @staticmethod
+    def _fetch_cluster_cones(cn, objects, off):
+        """The shower tables as ``cluster_cones`` returns them (``objects``: what ``_fetch_cluster_features`` returned for the same
+        rows, ``off`` the list offsets)."""
+        from .clusters import CONE_EVENT, CONE_INT, CONE_REAL, LINK_INT, LINK_REAL
+        merged, small, scls, soff, si, sr, loff, li, lr, rows5, ev, status, cap, M = cn
+        code = int(status.cpu().numpy()[0])
+        if code != 0:
+            raise _lib.UrsnError('cluster_cones: the ids, table offsets, lists and object records disagree (status %d)' % code)
+        counts = [int(o['n'].shape[0]) for o in objects]
+        K = int(sum(counts))
+        soff, loff, ev = soff.cpu().numpy(), loff.cpu().numpy(), ev.cpu().numpy()
+        S, L = int(soff[-1]), int(loff[-1])
+        assert soff[0] == 0 and loff[0] == 0 and S <= K <= cap and L <= K, 'cluster_cones: %d showers and %d links of %d rows' % (S, L, K)
+        merged, small, scls = merged[:M].cpu().numpy(), small.cpu().numpy(), scls[:S].cpu().numpy()
+        si, sr, li, lr = si[:S].cpu().numpy(), sr[:S].cpu().numpy(), li[:L].cpu().numpy(), lr[:L].cpu().numpy()
+        rows5 = rows5.cpu().numpy()
+        kids = rows5[4:].reshape(cap, 2)
+        events, ids, tables, at = [], [], [], 0
+        for i, (o, k) in enumerate(zip(objects, counts)):
+            lo, hi, llo, lhi = int(soff[i]), int(soff[i + 1]), int(loff[i]), int(loff[i + 1])
+            showers = {name: si[lo:hi, c].copy() for c, name in enumerate(CONE_INT)}
+            showers.update({name: sr[lo:hi, c].copy() for c, name in enumerate(CONE_REAL)})
+            links = {name: li[llo:lhi, c].copy() for c, name in enumerate(LINK_INT)}
+            links.update({name: lr[llo:lhi, c].copy() for c, name in enumerate(LINK_REAL)})
+            events.append({'objects': o, 'showers': showers, 'links': links, 'row_shower': rows5[0, at:at + k].copy(),
+                           'row_parent': rows5[1, at:at + k].copy(), 'row_candidates': rows5[2, at:at + k].copy(),
+                           'row_depth': rows5[3, at:at + k].copy(), 'row_children': kids[at:at + k].copy(),
+                           'event': dict(zip(CONE_EVENT, (int(x) for x in ev[i])))})
+            ids.append(merged[off[i]:off[i + 1]].copy())
+            tables.append({'first': small[lo:hi].copy(), 'size': small[cap + lo:cap + hi].copy(), 'cls': scls[lo:hi].copy()})
+            at += k
+        return {'events': events, 'cluster': ids, 'clusters': tables}
+
+    def cluster_cones(self, sess, voxels_or_lists, value, clusters, spec, shape=None):
+        """Showers of clusters already made: ``voxels_or_lists``, ``value``, ``clusters`` and ``shape`` as ``cluster_features`` takes
+        them (``clusters`` may be the dict ``cluster_chains`` returned: cones on chains), ``spec`` a ``clusters.ClusterConeSpec``.
+        Runs the object records and then the cones.  Returns ``{'events': [...], 'cluster': [...], 'clusters': [...]}``: per event a
+        dict -- ``objects`` (as ``cluster_features``), ``showers`` (named columns ``clusters.CONE_INT`` / ``CONE_REAL``, one row per
+        shower), ``links`` (``LINK_INT`` / ``LINK_REAL``, one row per link, ascending child row), ``row_shower`` / ``row_parent`` /
+        ``row_candidates`` / ``row_depth`` int32 [K_i], ``row_children`` int32 [K_i, 2] and ``event`` (a dict over
+        ``clusters.CONE_EVENT``) -- and, as ``cluster`` / ``clusters``, the showers as a clustering of the same lists: the merged
+        ids int32 [m_i] and the table ``first`` / ``size`` / ``cls``.  The returned dict is itself a legal ``clusters`` argument
+        of the other cluster calls."""
+        import torch
+        from .clusters import ClusterConeSpec
+        if not isinstance(spec, ClusterConeSpec):
+            raise ValueError('cluster_cones: spec = %r, expected a clusters.ClusterConeSpec' % (spec,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_cones: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, VoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = voxels_or_lists.value
+        elif isinstance(voxels_or_lists, _DeviceVoxelBatch):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+            if value is None:
+                value = self._resident_value(voxels_or_lists)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_cones: %d events outside [1, 65535]' % n)
+        if isinstance(value, (list, tuple)):
+            value = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in value]) if len(value) else np.zeros(0, np.float32)
+        if value is not None:
+            value = np.asarray(value, np.float32).reshape(-1)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_cones: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids]) if n else np.zeros(0, np.int32)
+        if cluster.size != M or index.size != M or (value is not None and value.size != M):
+            raise ValueError('cluster_cones: %d list entries, %d indices, %d ids, %s values'
+                             % (M, index.size, cluster.size, 'no' if value is None else value.size))
+        toff = np.concatenate([[0], np.cumsum([int(t['first'].size) for t in tables])]).astype(np.int64)
+        K = int(toff[-1])
+        cls = np.concatenate([np.asarray(t['cls'], np.uint8).reshape(-1) for t in tables] + [np.zeros(1, np.uint8)])
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self._device)
+        d_off, d_index, d_toff, d_cls = up(off, np.int64), up(index, np.int32), up(toff, np.int64), up(cls, np.uint8)
+        d_cluster = up(cluster if M else np.zeros(1, np.int32), np.int32)
+        d_value = None if value is None else up(value if M else np.zeros(1, np.float32), np.float32)
+        pending = (d_cluster, None, d_toff, M, n, M)
+        dev_objects = self._enqueue_cluster_features(sess, d_off, d_index, d_value, pending, shape)
+        objects = self._fetch_cluster_features(dev_objects, tables)
+        cn = self._enqueue_cluster_cones(sess, d_off, d_index, pending, dev_objects, d_cls, shape, spec, K)
+        return self._fetch_cluster_cones(cn, objects, off)
+
+    # ------------------------------------------------------------------------------------------
     # cluster matching (definition and numpy statement: clusters.cluster_match_numpy, device passes: csrc/cluster_match.hip)
     # ------------------------------------------------------------------------------------------
     def set_cluster_matching(self, on):
@@ -2489,6 +2670,15 @@ class ssnet_base(object):
                                                pending, big)
             chain = self._enqueue_cluster_chains(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, chain_objects,
                                                  pending[1], big, cspec, M)
+        nspec = getattr(self, '_cluster_cone_spec', None) if pending is not None else None
+        cone = None
+        if nspec is not None:                      # the stitched list, in the large shape: a shower crosses tile seams
+            cone_objects = objects if objects is not None else prof_objects if pspec is not None else \
+                vtx_objects if vspec is not None else chain_objects if cspec is not None else \
+                self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
+                                               pending, big)
+            cone = self._enqueue_cluster_cones(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, cone_objects,
+                                               pending[1], big, nspec, M)
         truth = match = None
         if matching:                               # the large batch's own labels under the same spec, then the match
             at = big_batch.ptr['label'] - big_batch.dev.data_ptr()
@@ -2530,6 +2720,9 @@ class ssnet_base(object):
         if chain is not None:
             records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, res['clusters'])
             res['chains'] = self._fetch_cluster_chains(chain, records, off)
+        if cone is not None:
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(cone_objects, res['clusters'])
+            res['cones'] = self._fetch_cluster_cones(cone, records, off)
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res
 

@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, chains_csv_header, chains_csv_row, profiles_csv_header, profiles_csv_row, vertices_csv_header, vertices_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, chains_csv_header, chains_csv_row, cones_csv_header, cones_csv_row, profiles_csv_header, profiles_csv_row, vertices_csv_header, vertices_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -89,6 +89,7 @@ class ssnet_trainval(object):
         self._profiles = None
         self._vertices = None
         self._chains = None
+        self._cones = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -193,6 +194,8 @@ class ssnet_trainval(object):
             raise ValueError('ANA_VERTICES needs ANA_CLUSTER: the vertices are where the end points of the clusters meet')
         if cfg.ANA_CHAINS and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_CHAINS needs ANA_CLUSTER: the chains join the clusters that are fragments of one track')
+        if cfg.ANA_CONES and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_CONES needs ANA_CLUSTER: the cones gather the clusters that are fragments of one shower')
         self._weight_spec = None
         if cfg.DEVICE_WEIGHTS and cfg.TRAIN:
             if not cfg.USE_WEIGHTS:
@@ -246,6 +249,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._chains.write(chains_csv_header())
                 self._chains.flush()
+        if cfg.ANA_CONES and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_CONES) or os.path.getsize(cfg.ANA_CONES) == 0
+            self._cones = open(cfg.ANA_CONES, 'a')
+            if fresh:
+                self._cones.write(cones_csv_header())
+                self._cones.flush()
 
         # image dimensions come from the first batch, not from the cfg (lib/ssnet_trainval.py:89-93)
         self._advance_main()
@@ -279,6 +288,10 @@ class ssnet_trainval(object):
                 from .clusters import ClusterChainSpec
                 self._net.set_cluster_chains(ClusterChainSpec(cfg.CHAIN_GAP, cfg.CHAIN_MIN_COS, cfg.CHAIN_MIN_SIZE,
                                                               cfg.CHAIN_CLASSES or None, cfg.CHAIN_SAME_CLASS))
+            if self._cones:                  # default off: never called
+                from .clusters import ClusterConeSpec
+                self._net.set_cluster_cones(ClusterConeSpec(cfg.CONE_REACH, cfg.CONE_MIN_COS, cfg.CONE_SEED_SIZE, cfg.CONE_MIN_SIZE,
+                                                            cfg.CONE_CLASSES or None, cfg.CONE_SAME_CLASS))
         if cfg.TRAIN and (cfg.CLIP_GRAD_NORM > 0 or cfg.WEIGHT_DECAY > 0 or cfg.SKIP_NONFINITE):   # default off: never called
             self._net.set_optimizer(clip_norm=cfg.CLIP_GRAD_NORM, weight_decay=cfg.WEIGHT_DECAY, skip_nonfinite=cfg.SKIP_NONFINITE)
         bad = [code for code in cfg.ANA_TTA if not symmetry.valid(dims[:-1], code)]
@@ -630,6 +643,7 @@ class ssnet_trainval(object):
         self._write_profiles(r, entries)
         self._write_vertices(r, entries)
         self._write_chains(r, entries)
+        self._write_cones(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -650,6 +664,9 @@ class ssnet_trainval(object):
                     if 'chains' in r:
                         ev['chains'] = {'merged': r['chains']['cluster'][i], 'table': r['chains']['clusters'][i],
                                         **r['chains']['events'][i]}
+                    if 'cones' in r:
+                        ev['cones'] = {'merged': r['cones']['cluster'][i], 'table': r['cones']['clusters'][i],
+                                       **r['cones']['events'][i]}
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
             if 'match' in r:
                 result['match'] = r['match']
@@ -714,6 +731,16 @@ class ssnet_trainval(object):
                 self._chains.write(chains_csv_row(entries[i], k, cols))
         self._chains.flush()
 
+    def _write_cones(self, r, entries):
+        """ANA_CONES: one CSV row per shower of every event of the result ``r``."""
+        if not getattr(self, '_cones', None) or 'cones' not in r:
+            return
+        for i in range(len(entries)):
+            cols = r['cones']['events'][i]['showers']
+            for k in range(int(cols['rows'].size)):
+                self._cones.write(cones_csv_row(entries[i], k, cols))
+        self._cones.flush()
+
     def _ana_step_tiled(self, vb, entries, batch_mode):
         """ANA_TILE: the batch holds events of the large shape; it goes up once and is analysed tile by tile
         (``inference_tiled_voxel_scores``).  Records and the interactive result are those of ``_ana_step_voxel_scores`` with
@@ -743,6 +770,7 @@ class ssnet_trainval(object):
         self._write_profiles(r, entries)
         self._write_vertices(r, entries)
         self._write_chains(r, entries)
+        self._write_cones(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -763,6 +791,9 @@ class ssnet_trainval(object):
                     if 'chains' in r:
                         ev['chains'] = {'merged': r['chains']['cluster'][i], 'table': r['chains']['clusters'][i],
                                         **r['chains']['events'][i]}
+                    if 'cones' in r:
+                        ev['cones'] = {'merged': r['cones']['cluster'][i], 'table': r['cones']['clusters'][i],
+                                       **r['cones']['events'][i]}
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
             if 'match' in r:
@@ -935,7 +966,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_vertices', '_chains', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_vertices', '_chains', '_cones', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
