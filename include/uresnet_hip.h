@@ -1533,6 +1533,115 @@ size_t ursn_cluster_cones_scratch_bytes(int32_t n, int64_t m_total);
 int ursn_cluster_cones(const ursn_cluster_cone_desc* d, const ursn_cluster_cone_out* out, void* scratch, size_t scratch_bytes,
                        void* stream);
 
+/* ---- cluster splits: a component of several particles cut at its junctions and kinks (cluster_split.hip) ---------------------------
+ * Every call above takes a connected component for an object.  The chain and cone calls repair one way that fails (one particle in
+ * several components); this call repairs the other: several particles in ONE component -- the prongs of a vertex, two tracks that
+ * cross, a track with a hard kink.  It returns one more clustering of the same lists, in the format ursn_cluster_voxels writes
+ * (split ids, piece_offsets, first / size / cls), so every call that takes a clustering runs on the pieces unchanged; the intended
+ * order is components -> split -> chains -> cones.  uresnet_amd/clusters.py (cluster_split_numpy) is the definition, operation by
+ * operation; this call gives its bits.
+ *
+ * ADJACENT: two different entries of one event whose coordinates differ by at most 1 on every axis (full adjacency, whatever
+ * connectivity made the clustering; decided on coordinates, never on linear indices; cells outside the volume are empty; a 2-D list
+ * has x2 = 0).  ELIGIBLE: a global row r with size[r] >= min_size and, with class_mask, bit cls[r] of it set.
+ *
+ * ARMS, for every member j of an eligible row R.  BALL(j) = the members of R within Chebyshev distance radius of x(j); REACH(j) = the
+ * entries of BALL(j) joined to j by a path of adjacent entries inside BALL(j); SHELL(j) = the entries of REACH(j) at distance exactly
+ * radius; the arms are the connected components of SHELL(j) under adjacency among shell entries, arms(j) = min(their number, 15).  An
+ * end sees 1 arm, a body 2, a junction 3 or more; a stub shorter than radius makes none.  KINK (only with exactly 2 arms and
+ * kink_cos < 1): s_a = the integer sum of x(q) - x(j) over arm a, dot = s_1 . s_2, q_a = s_a . s_a, and with both q_a > 0
+ * c = (double)dot / (sqrt((double)q_1) * sqrt((double)q_2)); KINK iff c > kink_cos.  j is CUT when arms(j) >= 3 or KINK.
+ *
+ * PIECES: among the entries of eligible rows, adjacent entries of one row with equal cut status are joined; uncut components are
+ * pieces of kind 1, cut components are JUNCTIONS; a row that is not eligible is one piece of kind 0, whole, connected or not (an
+ * eligible row that is itself disconnected falls into its components: split BEFORE chaining).  ATTACHMENT, rounds t = 1 .. grow: a
+ * cut entry without a piece looks at its adjacent entries of the same row that are uncut or were attached in a round before t and
+ * takes the piece of the one at the lowest list position; a round reads only what earlier rounds wrote.  What a junction still holds
+ * after the last round is one piece of kind 2.  Pieces are numbered per event by ascending KEY (kinds 0 and 1: the lowest list
+ * position of the original members; kind 2: the lowest position of the junction's entries before attachment), junctions per event
+ * by their lowest position.  With attachment `first` need not ascend with the piece id; no call of this header relies on that.
+ * A CONTACT is an ordered pair (cut entry, adjacent uncut entry of its row), taken before attachment.
+ *
+ * mark[j] = arms | cut << 4 | kink << 5 | attached << 6, 0 where the entry was not evaluated.
+ * Piece record, URSN_CLSPLIT_PI int64: [0] row (event-local)   [1] n final members   [2] attached (of them)   [3] kind
+ *   [4] key (a list position)   [5] contacts whose uncut entry is an original member   [6] junction_lo, [7] junction_hi the smallest
+ *   / largest event-local junction of those contacts, -1 for none (a piece of kind 2: contacts 0 and its own junction in both).
+ * Junction record, URSN_CLSPLIT_JI int64: [0] row   [1] entries   [2] attached   [3] arms_max   [4] kink entries   [5..7] coordinate
+ *   sums   [8..10] box lo   [11..13] box hi   [14] first position   [15] contacts   [16] piece_lo, [17] piece_hi the smallest / largest
+ *   event-local piece among its contacts' uncut entries, -1 for none.  URSN_CLSPLIT_JR fp64: [0..2] centroid = (double)sum /
+ *   (double)entries -- the vertex position that ursn_cluster_vertices cannot see inside one component.
+ * Per row, URSN_CLSPLIT_ROW int32: pieces, junctions, cut entries.  Event record, URSN_CLSPLIT_EV int64: [0] pieces   [1] junctions
+ *   [2] rows with a junction   [3] cut entries.
+ *
+ * Method (cluster_split.hip lists the launches).  The hot pass is the arms count: the entries of eligible rows are compacted in list
+ * order.  The list row (x0 - radius + a, x1 - radius + b) of an entry's ball is found by ONE lower-bound binary search confined to
+ * the event's range (<= 32 halvings); at most 7 consecutive entries are read and a 7-bit mask of the members of R kept; the masks
+ * make the ball's bitmap, seven 64-bit words, one per x2 and bit 8 a + b inside.  REACH is an iterated dilation of the centre bit
+ * inside the bitmap (shifts by 1, 8 and a word), the arms the same flood from successive lowest seeds inside the shell mask.  The
+ * default (and URSN_CLSPLIT_WAVE=0) is the plain form, one thread per entry, its seven words in registers; URSN_CLSPLIT_WAVE=1 is
+ * the wave form, one wave64 per entry, lane 8 a + b < 56 owns one list row and seven ballots make the words (same bits; slower as
+ * measured, because its flood is uniform and runs on the scalar unit).  Then a union-find over the equal-status adjacency with 32-bit atomicMin to the lower position, `grow` attachment
+ * launches whose round stamp only its owner writes, ballot counts per tile of 64 entries and one-workgroup scans for the two
+ * numberings, and 64-bit INTEGER atomic adds / min / max at agent scope for the records; each centroid is one thread's three
+ * divisions under contract(off).  No float atomics.  Enqueues only, never synchronises; the scratch needs no initialisation; every
+ * device loop is bounded; the same arguments give the same bits.
+ *
+ * *status is 0, or: bit 0 an id outside [-1, K_e), offsets that are not those of the lists or table_offsets[n] > m_total, bit 1 a
+ * list that does not increase strictly inside an event, bit 2 an index outside the volume at an entry with an id, bit 3 a bounded
+ * loop ran out, bit 4 a cls >= 32 (such an entry or row takes no part: split = -1, mark = 0; every entry and row is checked and the
+ * bits are the same whenever the arguments are).  Pieces, junctions and rows at or beyond cap_pieces / cap_junctions / cap_rows are
+ * never written; everything below them is complete whatever the caps are; piece_offsets, junction_offsets and the event records
+ * hold the true counts.  m_total = 0 still writes *status, the offsets and the event records.  Null, misaligned, out-of-domain and
+ * too-small arguments are refused with a message that begins "cluster_split:" before any launch. */
+#define URSN_CLSPLIT_PI 8    /* int64 columns of a piece record */
+#define URSN_CLSPLIT_JI 18   /* int64 columns of a junction record */
+#define URSN_CLSPLIT_JR 3    /* fp64 columns of a junction record */
+#define URSN_CLSPLIT_ROW 3   /* int32 columns per row */
+#define URSN_CLSPLIT_EV 4    /* int64 columns of an event record */
+
+typedef struct ursn_cluster_split_desc { /* every pointer is a DEVICE pointer */
+  int32_t ndim;                         /* 2 | 3 */
+  int32_t spatial[3];                   /* extents in [1, 32768], prod < 2^31 (spatial[2] unused in 2-D) */
+  int32_t n;                            /* events, 1..65535 */
+  int32_t radius;                       /* 1..3 */
+  int64_t m_total;                      /* list entries, < 2^30 */
+  const int64_t* offsets;               /* [n+1] */
+  const int32_t* index;                 /* [m_total] strictly increasing per event */
+  const int32_t* cluster;               /* [m_total] event-local ids, -1 for none */
+  const int64_t* table_offsets;         /* [n+1] */
+  const int32_t* size;                  /* [K_total] the cluster table's size */
+  const uint8_t* cls;                   /* [K_total] the cluster table's cls, or null: every cls written is 0 */
+  double kink_cos;                      /* [-1, 1]; >= 1: no kinks */
+  int32_t min_size;                     /* >= 1 */
+  uint32_t class_mask;                  /* 0: rows of every class are eligible; else bit cls[r] decides, and cls must be given */
+  int32_t grow;                         /* 0..8 attachment rounds */
+  int32_t reserved;                     /* 0 */
+} ursn_cluster_split_desc;
+
+typedef struct ursn_cluster_split_out { /* DEVICE pointers */
+  int32_t* split;                       /* [m_total] */
+  uint8_t* mark;                        /* [m_total] */
+  int64_t* piece_offsets;               /* [n+1] */
+  int32_t* first;                       /* [cap_pieces] the piece table, typed as ursn_cluster_out's */
+  int32_t* size;                        /* [cap_pieces] */
+  uint8_t* cls;                         /* [cap_pieces] */
+  int64_t* piece_itab;                  /* [cap_pieces][URSN_CLSPLIT_PI] */
+  int64_t cap_pieces;
+  int64_t* junction_offsets;            /* [n+1] */
+  int64_t* junction_itab;               /* [cap_junctions][URSN_CLSPLIT_JI] */
+  double* junction_rtab;                /* [cap_junctions][URSN_CLSPLIT_JR] */
+  int64_t cap_junctions;
+  int32_t* rows;                        /* [cap_rows][URSN_CLSPLIT_ROW] */
+  int64_t cap_rows;
+  int64_t* event;                       /* [n][URSN_CLSPLIT_EV] */
+  int32_t* status;                      /* [1] */
+} ursn_cluster_split_out;
+
+/* Bytes of scratch: 8-byte aligned, at least 8; 0 for n outside [1, 65535] or m_total outside [0, 2^30).  Host logic only. */
+size_t ursn_cluster_split_scratch_bytes(int32_t n, int64_t m_total);
+int ursn_cluster_split(const ursn_cluster_split_desc* d, const ursn_cluster_split_out* out, void* scratch, size_t scratch_bytes,
+                       void* stream);
+
 /* ---- vertex candidates: where the end points of the object records meet (cluster_vertex.hip) ----------------------------------------
  * Appended functions and two structs only: URSN_ABI_VERSION stays 9.
  * The step from objects to interactions: which ends meet at one point, how many objects leave it and at what angles, which objects

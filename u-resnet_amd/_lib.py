@@ -232,6 +232,23 @@ class ursn_cluster_cone_out(C.Structure):
                 ("cap_rows", C.c_int64), ("event", C.c_void_p), ("status", C.c_void_p)]
 
 
+CLSPLIT_PI, CLSPLIT_JI, CLSPLIT_JR, CLSPLIT_ROW, CLSPLIT_EV = 8, 18, 3, 3, 4   # URSN_CLSPLIT_*: columns of the piece, junction, row and event records
+
+
+class ursn_cluster_split_desc(C.Structure):
+    _fields_ = [("ndim", C.c_int32), ("spatial", C.c_int32 * 3), ("n", C.c_int32), ("radius", C.c_int32), ("m_total", C.c_int64),
+                ("offsets", C.c_void_p), ("index", C.c_void_p), ("cluster", C.c_void_p), ("table_offsets", C.c_void_p),
+                ("size", C.c_void_p), ("cls", C.c_void_p), ("kink_cos", C.c_double), ("min_size", C.c_int32), ("class_mask", C.c_uint32),
+                ("grow", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ursn_cluster_split_out(C.Structure):
+    _fields_ = [("split", C.c_void_p), ("mark", C.c_void_p), ("piece_offsets", C.c_void_p), ("first", C.c_void_p), ("size", C.c_void_p),
+                ("cls", C.c_void_p), ("piece_itab", C.c_void_p), ("cap_pieces", C.c_int64), ("junction_offsets", C.c_void_p),
+                ("junction_itab", C.c_void_p), ("junction_rtab", C.c_void_p), ("cap_junctions", C.c_int64), ("rows", C.c_void_p),
+                ("cap_rows", C.c_int64), ("event", C.c_void_p), ("status", C.c_void_p)]
+
+
 class ursn_loss_desc(C.Structure):
     _fields_ = [("gamma", C.c_double), ("smoothing", C.c_double), ("dice_weight", C.c_double), ("dice_eps", C.c_double),
                 ("ignore_label", C.c_int32)]
@@ -365,6 +382,9 @@ _SIGS = {
     # cluster_cone.hip
     "ursn_cluster_cones_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "ursn_cluster_cones": (C.c_int, [C.POINTER(ursn_cluster_cone_desc), C.POINTER(ursn_cluster_cone_out), _P, C.c_size_t, _P]),
+    # cluster_split.hip
+    "ursn_cluster_split_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "ursn_cluster_split": (C.c_int, [C.POINTER(ursn_cluster_split_desc), C.POINTER(ursn_cluster_split_out), _P, C.c_size_t, _P]),
     "ursn_cluster_graph_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "ursn_cluster_graph": (C.c_int, [C.POINTER(ursn_cluster_graph_desc), C.POINTER(ursn_cluster_graph_out), _P, C.c_size_t, _P]),
 }

@@ -1676,3 +1676,344 @@ def cluster_cones_numpy(offsets, index, value, cluster, table_offsets, spatial, 
             'links': {k: np.array(links[k], np.int64 if k in LINK_INT else np.float64).reshape(-1) for k in links},
             'row_shower': row_shower, 'row_parent': row_parent, 'row_candidates': row_candidates, 'row_children': row_children,
             'row_depth': row_depth, 'events': np.array(events, np.int64).reshape(-1, 4)}
+
+
+# ---- cluster splits: a component of several particles cut at its junctions and kinks (csrc/cluster_split.hip does it on the
+# device; this is the statement) --------------------------------------------------------------------------------------------------
+SPLIT_PIECE = ('row', 'n', 'attached', 'kind', 'key', 'contacts', 'junction_lo', 'junction_hi')
+SPLIT_JUNCTION_INT = ('row', 'entries', 'attached', 'arms_max', 'kinks', 's0', 's1', 's2', 'lo0', 'lo1', 'lo2', 'hi0', 'hi1', 'hi2',
+                      'first_pos', 'contacts', 'piece_lo', 'piece_hi')
+SPLIT_JUNCTION_REAL = ('c0', 'c1', 'c2')
+SPLIT_ROW = ('pieces', 'junctions', 'cut')
+SPLIT_EVENT = ('pieces', 'junctions', 'rows_cut', 'cut')
+SPLIT_MAX_RADIUS = 3
+SPLIT_MAX_GROW = 8
+SPLIT_MAX_ARMS = 15
+_SPLIT_NEIGHBOURS = tuple((a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1) if (a, b, c) != (0, 0, 0))
+
+
+class ClusterSplitSpec(object):
+    """``radius`` in [1, 3]: the Chebyshev radius of the ball in which the arms of a voxel are counted; ``kink_cos`` a float in
+    [-1, 1]: a voxel with exactly two arms is cut when the cosine between them exceeds it (straight is -1), a value >= 1 switches
+    kinks off; ``min_size`` >= 1: rows whose table ``size`` is smaller stay whole; ``classes`` None = rows of every class, else
+    distinct class numbers in [0, 32): only rows of these classes are split (needs the table's cls); ``grow`` in [0, 8]: the
+    rounds in which the cut voxels are handed back to the pieces that touch them, None = 2 * radius."""
+
+    def __init__(self, radius=2, kink_cos=-0.7, min_size=8, classes=None, grow=None):
+        if type(radius) is not int or not 1 <= radius <= SPLIT_MAX_RADIUS:
+            raise ValueError('ClusterSplitSpec: radius = %r, expected an integer in [1, %d]' % (radius, SPLIT_MAX_RADIUS))
+        if type(kink_cos) not in (int, float) or not np.isfinite(kink_cos) or not -1.0 <= kink_cos <= 1.0:
+            raise ValueError('ClusterSplitSpec: kink_cos = %r, expected a finite float in [-1, 1]' % (kink_cos,))
+        if type(min_size) is not int or not 1 <= min_size < 2 ** 31:
+            raise ValueError('ClusterSplitSpec: min_size = %r, expected an integer >= 1' % (min_size,))
+        if classes is not None:
+            given = classes
+            try:
+                classes = tuple(classes)
+            except TypeError:
+                classes = ()
+            if not classes or any(type(c) is not int or not 0 <= c < 32 for c in classes) or len(set(classes)) != len(classes):
+                raise ValueError('ClusterSplitSpec: classes = %r, expected None or distinct integers in [0, 32)' % (given,))
+        if grow is None:
+            grow = 2 * radius
+        if type(grow) is not int or not 0 <= grow <= SPLIT_MAX_GROW:
+            raise ValueError('ClusterSplitSpec: grow = %r, expected None or an integer in [0, %d]' % (grow, SPLIT_MAX_GROW))
+        self.radius, self.kink_cos, self.min_size, self.classes, self.grow = radius, float(kink_cos), min_size, classes, grow
+
+    def class_mask(self):
+        """Bit k set = rows of class k are split; 0 = every class."""
+        m = 0
+        for c in self.classes or ():
+            m |= 1 << c
+        return m
+
+    def __repr__(self):
+        return 'ClusterSplitSpec(radius=%r, kink_cos=%r, min_size=%r, classes=%r, grow=%r)' % (
+            self.radius, self.kink_cos, self.min_size, self.classes, self.grow)
+
+
+def cluster_split_numpy(offsets, index, cluster, table_offsets, size, spatial, spec, cls=None):
+    """The statement of the cluster split of concatenated per-event lists: a connected component that holds several particles
+    (prongs of one vertex, crossing tracks, a kinked track) is cut where it branches or bends, and the pieces come back as one more
+    clustering of the same lists.  Slow on purpose, in the style of ``cluster_chains_numpy``: Python integers, scalar fp64
+    operations each rounded on its own.  Lists are row-major in ``spatial`` and strictly increasing per event; coordinates are
+    ``np.unravel_index(index, spatial)`` with x[2] = 0 in 2-D.  A POSITION is a place in the concatenated list.
+
+    ADJACENT.  Two different entries of one event whose coordinates differ by at most 1 on every axis: full adjacency, whatever
+    connectivity made the clustering, decided on coordinates (never on linear indices: the last voxel of a row and the first of
+    the next are not adjacent); cells outside the volume are empty.
+
+    ELIGIBLE.  A global row r with ``size[r] >= spec.min_size`` and, with ``spec.classes``, ``cls[r]`` one of them.
+
+    ARMS, for every member j of an eligible row R.  BALL(j): the members of R within Chebyshev distance ``radius`` of x(j).
+    REACH(j): the entries of BALL(j) joined to j by a path of adjacent entries inside BALL(j) (a parallel limb of R that merely
+    passes within ``radius`` is not reached).  SHELL(j): the entries of REACH(j) at Chebyshev distance exactly ``radius``.  The
+    ARMS are the connected components of SHELL(j) under adjacency among shell entries; arms(j) = min(their number, 15).  An end
+    sees 1 arm, a body 2, a junction 3 or more; a stub shorter than ``radius`` reaches no shell and makes no arm.
+
+    KINK, evaluated only with exactly 2 arms and kink_cos < 1.  s_a = the integer sum of x(q) - x(j) over arm a; dot = s_1 . s_2,
+    q_a = s_a . s_a; with both q_a > 0: c = float64(dot) / (sqrt(float64(q_1)) * sqrt(float64(q_2))) and KINK iff c > kink_cos (the
+    product of the two roots commutes, so the order of the arms does not matter).
+
+    CUT.  j is cut when arms(j) >= 3 or KINK.
+
+    PIECES AND JUNCTIONS.  Among the entries of eligible rows, adjacent entries of the same row with the same cut status are
+    joined.  Uncut components are PIECES of kind 1, cut components are JUNCTIONS.  A row that is not eligible is ONE piece of kind
+    0, whole, connected or not.  An eligible row that is itself disconnected (a chain of ``cluster_chains``, say) falls into its
+    components: the split belongs BEFORE the chains and cones.
+
+    ATTACHMENT, in rounds t = 1 .. ``grow``.  A cut entry that has no piece yet looks at its adjacent entries of the same row that
+    are uncut or were attached in a round before t; if there are any it takes the piece of the one at the lowest position.  Round t
+    reads only what earlier rounds wrote.  What a junction still holds after the last round is one piece of kind 2 (connected or
+    not).
+
+    NUMBERING.  Pieces are numbered per event in ascending KEY: for kinds 0 and 1 the lowest position of the original members (for
+    kind 1 the uncut component), for kind 2 the lowest position of the junction's entries before attachment.  Junctions are
+    numbered per event by their lowest position.  With attachment a piece's ``first`` need not ascend with its id.
+
+    CONTACT.  An ordered pair (cut entry, adjacent uncut entry of its row), taken before attachment.
+
+    Outputs.  ``split`` int32 [m]: the event-local piece, -1 where ``cluster`` is -1.  ``piece_offsets`` / ``junction_offsets``
+    int64 [n + 1].  ``table``: ``first`` int32 = the lowest event-local position of the final members, ``size`` int32 = the final
+    members, ``cls`` uint8 = the row's cls (0 without cls).  ``mark`` uint8 [m] = arms | junction << 4 | kink << 5 | attached << 6,
+    0 for entries that were not evaluated (junction: the entry is cut).  SPLIT_PIECE int64: ``row`` (event-local), ``n`` (final
+    members), ``attached`` (of them, attached cut entries), ``kind``, ``key`` (a position), ``contacts`` (contacts whose uncut
+    entry is an original member), ``junction_lo`` / ``junction_hi`` the smallest / largest event-local junction among those
+    contacts, -1 for none; a piece of kind 2 has contacts 0 and names its own junction in both.  SPLIT_JUNCTION_INT int64: ``row``,
+    ``entries``, ``attached`` (entries handed to pieces), ``arms_max``, ``kinks`` (entries with KINK), ``s0..2`` the coordinate
+    sums, ``lo0..2`` / ``hi0..2`` the box, ``first_pos`` (its lowest position), ``contacts``, ``piece_lo`` / ``piece_hi`` the
+    smallest / largest event-local piece among its contacts' uncut entries, -1 for none.  SPLIT_JUNCTION_REAL: ``c0..2`` =
+    float64(s) / float64(entries): the vertex position that ``cluster_vertices`` cannot see.  ``rows`` int32 [K, 3] over
+    SPLIT_ROW: pieces, junctions, cut entries.  ``events`` int64 [n, 4] over SPLIT_EVENT: pieces, junctions, rows with a junction,
+    cut entries.
+
+    An id outside its event's rows, an index outside the volume at an entry with an id, a list that does not increase strictly
+    inside an event and a cls >= 32 raise ValueError."""
+    if not isinstance(spec, ClusterSplitSpec):
+        raise ValueError('cluster_split_numpy: spec = %r, expected a ClusterSplitSpec' % (spec,))
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or any(not 1 <= s <= MAX_EXTENT for s in spatial):
+        raise ValueError('cluster_split_numpy: spatial = %r, expected 2 or 3 extents in [1, %d]' % (spatial, MAX_EXTENT))
+    off = [int(x) for x in np.asarray(offsets).reshape(-1)]
+    toff = [int(x) for x in np.asarray(table_offsets).reshape(-1)]
+    idx = [int(x) for x in np.asarray(index).reshape(-1)]
+    ids = [int(x) for x in np.asarray(cluster).reshape(-1)]
+    sizes = [int(x) for x in np.asarray(size).reshape(-1)]
+    nev, m, ndim, rad = len(off) - 1, len(idx), len(spatial), spec.radius
+    if nev < 1 or len(toff) != nev + 1 or len(ids) != m or off[0] != 0 or off[-1] != m or toff[0] != 0 \
+            or any(off[e + 1] < off[e] or toff[e + 1] < toff[e] for e in range(nev)):
+        raise ValueError('cluster_split_numpy: offsets, table offsets and the lists disagree')
+    K = toff[-1]
+    if len(sizes) != K:
+        raise ValueError('cluster_split_numpy: size must hold %d rows' % K)
+    if cls is not None:
+        cls = [int(c) for c in np.asarray(cls).reshape(-1)]
+        if len(cls) != K or any(not 0 <= c < 32 for c in cls):
+            raise ValueError('cluster_split_numpy: cls must hold %d classes in [0, 32)' % K)
+    if spec.classes is not None and cls is None:
+        raise ValueError('cluster_split_numpy: spec.classes = %r needs the cluster table\'s cls' % (spec.classes,))
+    vox = 1
+    for s in spatial:
+        vox *= s
+    ext = spatial + (1,) * (3 - ndim)
+    mask, kink_cos = spec.class_mask(), np.float64(spec.kink_cos)
+    eligible = [sizes[r] >= spec.min_size and (not mask or bool((mask >> cls[r]) & 1)) for r in range(K)]
+    event_of_row = [e for e in range(nev) for _ in range(toff[e + 1] - toff[e])]
+    row_of, xs, event_of = [-1] * m, [None] * m, [0] * m
+    at = [{} for _ in range(nev)]                         # per event: coordinates -> position, entries with an id only
+    for e in range(nev):
+        for j in range(off[e], off[e + 1]):
+            event_of[j] = e
+            if j > off[e] and idx[j] <= idx[j - 1]:
+                raise ValueError('cluster_split_numpy: entry %d does not increase the list of event %d' % (j, e))
+            if ids[j] < 0:
+                continue
+            if not ids[j] < toff[e + 1] - toff[e]:
+                raise ValueError('cluster_split_numpy: entry %d has id %d, its event has %d clusters' % (j, ids[j], toff[e + 1] - toff[e]))
+            if not 0 <= idx[j] < vox:
+                raise ValueError('cluster_split_numpy: entry %d has index %d outside the volume %r' % (j, idx[j], spatial))
+            row_of[j] = toff[e] + ids[j]
+            x = tuple(int(c) for c in np.unravel_index(idx[j], spatial)) + (0,) * (3 - ndim)
+            xs[j] = x
+            at[e][x] = j
+
+    def neighbours(j):
+        """The adjacent entries of j's row, ascending position (= ascending coordinates, the lists being sorted)."""
+        x, out = xs[j], []
+        for d in _SPLIT_NEIGHBOURS:
+            y = (x[0] + d[0], x[1] + d[1], x[2] + d[2])
+            if all(0 <= y[a] < ext[a] for a in range(3)):
+                q = at[event_of[j]].get(y)
+                if q is not None and row_of[q] == row_of[j]:
+                    out.append(q)
+        return sorted(out)
+
+    def flood(seed, allowed):
+        """The offsets of ``allowed`` joined to ``seed`` by steps of adjacency inside ``allowed``."""
+        seen, todo = {seed}, [seed]
+        while todo:
+            d = todo.pop()
+            for s in _SPLIT_NEIGHBOURS:
+                y = (d[0] + s[0], d[1] + s[1], d[2] + s[2])
+                if y in allowed and y not in seen:
+                    seen.add(y)
+                    todo.append(y)
+        return seen
+
+    mark = np.zeros(m, np.uint8)
+    arms_of, cut, kink = [0] * m, [False] * m, [False] * m
+    for j in range(m):
+        r = row_of[j]
+        if r < 0 or not eligible[r]:
+            continue
+        x, e = xs[j], event_of[j]
+        # REACH by a search from j that never leaves the ball: the same set as the flood of BALL(j) from j
+        reach, todo = {(0, 0, 0)}, [(0, 0, 0)]
+        while todo:
+            d = todo.pop()
+            for s in _SPLIT_NEIGHBOURS:
+                y = (d[0] + s[0], d[1] + s[1], d[2] + s[2])
+                if y in reach or max(abs(y[0]), abs(y[1]), abs(y[2])) > rad:
+                    continue
+                c = (x[0] + y[0], x[1] + y[1], x[2] + y[2])
+                if not all(0 <= c[a] < ext[a] for a in range(3)):
+                    continue
+                q = at[e].get(c)
+                if q is not None and row_of[q] == r:
+                    reach.add(y)
+                    todo.append(y)
+        shell = set(d for d in reach if max(abs(d[0]), abs(d[1]), abs(d[2])) == rad)
+        arms = []
+        while shell:
+            arm = flood(min(shell), shell)
+            arms.append(arm)
+            shell -= arm
+        arms_of[j] = min(len(arms), SPLIT_MAX_ARMS)
+        if len(arms) == 2 and spec.kink_cos < 1.0:
+            s1 = [sum(d[a] for d in arms[0]) for a in range(3)]
+            s2 = [sum(d[a] for d in arms[1]) for a in range(3)]
+            dot = s1[0] * s2[0] + s1[1] * s2[1] + s1[2] * s2[2]
+            q1 = s1[0] * s1[0] + s1[1] * s1[1] + s1[2] * s1[2]
+            q2 = s2[0] * s2[0] + s2[1] * s2[1] + s2[2] * s2[2]
+            if q1 > 0 and q2 > 0:
+                c = np.float64(dot) / (np.sqrt(np.float64(q1)) * np.sqrt(np.float64(q2)))
+                kink[j] = bool(c > kink_cos)
+        cut[j] = arms_of[j] >= 3 or kink[j]
+    # components of equal cut status inside the eligible rows; the root of a component is its lowest position
+    parent = list(range(m))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    nbrs = [None] * m
+    for j in range(m):
+        if row_of[j] >= 0 and eligible[row_of[j]]:
+            nbrs[j] = neighbours(j)
+            for q in nbrs[j]:
+                if q < j and cut[q] == cut[j]:
+                    a, b = find(j), find(q)
+                    if a != b:
+                        parent[max(a, b)] = min(a, b)
+    row_first = [None] * K
+    for j in range(m):
+        if row_of[j] >= 0 and row_first[row_of[j]] is None:
+            row_first[row_of[j]] = j
+    root = [find(j) if nbrs[j] is not None else -1 for j in range(m)]
+    # attachment
+    piece_key, stamp = [-1] * m, [0] * m                   # the key of the piece an entry ends in; the round that attached it
+    for j in range(m):
+        r = row_of[j]
+        if r >= 0:
+            piece_key[j] = row_first[r] if not eligible[r] else root[j] if not cut[j] else -1
+    for t in range(1, spec.grow + 1):
+        taken = []
+        for j in range(m):
+            if nbrs[j] is not None and cut[j] and stamp[j] == 0:
+                for q in nbrs[j]:                         # ascending position
+                    if not cut[q] or 0 < stamp[q] < t:
+                        taken.append((j, piece_key[q]))
+                        break
+        for j, key in taken:                              # written after the round has read
+            piece_key[j], stamp[j] = key, t
+    for j in range(m):
+        if nbrs[j] is not None and cut[j] and stamp[j] == 0:
+            piece_key[j] = root[j]                        # the remainder of its junction: kind 2
+    # numbering
+    piece_id, junction_id = {}, {}                        # key -> global number
+    piece_offsets, junction_offsets = [0], [0]
+    for e in range(nev):
+        for key in sorted(set(piece_key[j] for j in range(off[e], off[e + 1]) if piece_key[j] >= 0)):
+            piece_id[key] = len(piece_id)
+        for key in sorted(set(root[j] for j in range(off[e], off[e + 1]) if root[j] >= 0 and cut[j])):
+            junction_id[key] = len(junction_id)
+        piece_offsets.append(len(piece_id))
+        junction_offsets.append(len(junction_id))
+    P, J = len(piece_id), len(junction_id)
+    split = np.full(m, -1, np.int32)
+    pieces = [[0] * len(SPLIT_PIECE) for _ in range(P)]
+    junctions = [[0] * len(SPLIT_JUNCTION_INT) for _ in range(J)]
+    first = [None] * P
+    rows = np.zeros((K, 3), np.int32)
+    events = [[piece_offsets[e + 1] - piece_offsets[e], junction_offsets[e + 1] - junction_offsets[e], 0, 0] for e in range(nev)]
+    for key, g in piece_id.items():
+        r = row_of[key]
+        e = event_of_row[r]
+        pieces[g][0], pieces[g][3], pieces[g][4] = r - toff[e], 0 if not eligible[r] else 2 if cut[key] else 1, key
+        pieces[g][6] = pieces[g][7] = junction_id[key] - junction_offsets[e] if eligible[r] and cut[key] else -1
+        rows[r][0] += 1
+    for key, g in junction_id.items():
+        r = row_of[key]
+        e = event_of_row[r]
+        t = junctions[g]
+        t[0], t[14], t[16], t[17] = r - toff[e], key, -1, -1
+        t[8:11], t[11:14] = list(xs[key]), list(xs[key])
+        rows[r][1] += 1
+        if rows[r][1] == 1:
+            events[e][2] += 1
+    for j in range(m):
+        if row_of[j] < 0:
+            continue
+        e, r = event_of[j], row_of[j]
+        g = piece_id[piece_key[j]]
+        split[j] = g - piece_offsets[e]
+        pieces[g][1] += 1
+        pieces[g][2] += 1 if stamp[j] > 0 else 0
+        if first[g] is None:
+            first[g] = j - off[e]
+        mark[j] = arms_of[j] | (16 if cut[j] else 0) | (32 if kink[j] else 0) | (64 if stamp[j] > 0 else 0)
+        if not cut[j]:
+            continue
+        jg = junction_id[root[j]]
+        t = junctions[jg]
+        t[1] += 1
+        t[2] += 1 if stamp[j] > 0 else 0
+        t[3] = max(t[3], arms_of[j])
+        t[4] += 1 if kink[j] else 0
+        for a in range(3):
+            t[5 + a] += xs[j][a]
+            t[8 + a], t[11 + a] = min(t[8 + a], xs[j][a]), max(t[11 + a], xs[j][a])
+        rows[r][2] += 1
+        events[e][3] += 1
+        for q in nbrs[j]:
+            if cut[q]:
+                continue
+            pg = piece_id[root[q]]                        # the piece q was a member of before attachment
+            pl, jl = pg - piece_offsets[e], jg - junction_offsets[e]
+            t[15] += 1
+            t[16], t[17] = pl if t[16] < 0 else min(t[16], pl), max(t[17], pl)
+            u = pieces[pg]
+            u[5] += 1
+            u[6], u[7] = jl if u[6] < 0 else min(u[6], jl), max(u[7], jl)
+    centroid = [[np.float64(t[5 + a]) / np.float64(t[1]) for a in range(3)] for t in junctions]
+    prow = [toff[event_of[p[4]]] + p[0] for p in pieces]
+    return {'split': split, 'mark': mark, 'piece_offsets': np.array(piece_offsets, np.int64),
+            'junction_offsets': np.array(junction_offsets, np.int64),
+            'table': {'first': np.array(first, np.int32).reshape(-1), 'size': np.array([p[1] for p in pieces], np.int32).reshape(-1),
+                      'cls': np.array([cls[r] if cls is not None else 0 for r in prow], np.uint8).reshape(-1)},
+            'pieces': {k: np.array([p[c] for p in pieces], np.int64).reshape(-1) for c, k in enumerate(SPLIT_PIECE)},
+            'junctions': dict([(k, np.array([t[c] for t in junctions], np.int64).reshape(-1)) for c, k in enumerate(SPLIT_JUNCTION_INT)] +
+                              [(k, np.array([c3[a] for c3 in centroid], np.float64).reshape(-1)) for a, k in enumerate(SPLIT_JUNCTION_REAL)]),
+            'rows': rows, 'events': np.array(events, np.int64).reshape(-1, 4)}

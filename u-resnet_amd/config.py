@@ -221,6 +221,21 @@ class ssnet_config(object):
     CONE_MIN_SIZE = 1
     CONE_CLASSES = []
     CONE_SAME_CLASS = True
+    # ANA_SPLIT '<file>' (with TRAIN False and ANA_CLUSTER) = one CSV row per junction: the places where a cluster that holds several
+    # particles is cut -- voxels that see three or more arms inside a ball of SPLIT_RADIUS, or two arms whose cosine exceeds
+    # SPLIT_KINK_COS (ssnet_base.set_cluster_split; clusters.cluster_split_numpy holds the definition): entry, junction, the
+    # eighteen junction integers (row, entries, attached, largest arm count, kink entries, coordinate sums, box, first position,
+    # contacts, lowest and highest piece it touches) and the centroid.  '' = off.  Refused without ANA_CLUSTER; ignored with TRAIN,
+    # like every ANA_* key.  SPLIT_RADIUS = 1 .. 3; SPLIT_KINK_COS = a float in [-1, 1], 1 = no kinks; SPLIT_MIN_SIZE = smaller
+    # clusters stay whole; SPLIT_CLASSES = the classes whose clusters are split, [] = all; SPLIT_GROW = 0 .. 8 attachment rounds,
+    # -1 = twice the radius; SPLIT_DOWNSTREAM = the object, profile, vertex, chain, cone and graph records describe the pieces
+    ANA_SPLIT = ''
+    SPLIT_RADIUS = 2
+    SPLIT_KINK_COS = -0.7
+    SPLIT_MIN_SIZE = 8
+    SPLIT_CLASSES = []
+    SPLIT_GROW = -1
+    SPLIT_DOWNSTREAM = False
 
     def __init__(self):
         pass
@@ -340,6 +355,21 @@ class ssnet_config(object):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'VERTEX_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'SPLIT_RADIUS' and not 1 <= value <= 3:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'SPLIT_KINK_COS' and not -1.0 <= value <= 1.0:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'SPLIT_MIN_SIZE' and value < 1:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'SPLIT_GROW' and not -1 <= value <= 8:
+                print('Incompatible value: %s' % line)
+                raise TypeError(line)
+            if key == 'SPLIT_CLASSES' and not (all(type(c) is int and 0 <= c < 32 for c in value) and len(set(value)) == len(value)):
                 print('Incompatible value: %s' % line)
                 raise TypeError(line)
             if key == 'CHAIN_GAP' and not 1 <= value <= 31:

@@ -220,6 +220,20 @@ def profiles_csv_row(entry, k, rows):
                     [repr(float(rows[name][k])) for name in PROFILE_ROW_REAL]) + '\n'
 
 
+def split_csv_header():
+    """The header line of the ANA_SPLIT file: one row per junction."""
+    from .clusters import SPLIT_JUNCTION_INT, SPLIT_JUNCTION_REAL
+    return ','.join(('entry', 'junction') + SPLIT_JUNCTION_INT + SPLIT_JUNCTION_REAL) + '\n'
+
+
+def split_csv_row(entry, k, junctions):
+    """Junction ``k`` of one event's ``junctions`` record (a dict of columns) as a CSV row: the integers, then the reals by
+    ``repr`` (which round-trips a float64)."""
+    from .clusters import SPLIT_JUNCTION_INT, SPLIT_JUNCTION_REAL
+    return ','.join(['%d' % entry, '%d' % k] + ['%d' % int(junctions[name][k]) for name in SPLIT_JUNCTION_INT] +
+                    [repr(float(junctions[name][k])) for name in SPLIT_JUNCTION_REAL]) + '\n'
+
+
 def chains_csv_header():
     """The header line of the ANA_CHAINS file: one row per chain."""
     from .clusters import CHAIN_INT, CHAIN_REAL
@@ -1148,38 +1162,45 @@ class ssnet_base(object):
         pending = None
         if spec is not None:                       # behind the gather head, on the list it read
             pending = self._enqueue_clusters(sess, d_offsets, d_index, dev[spec.on], n, M, self._dims[:-1], spec)
+        sspec = getattr(self, '_cluster_split_spec', None) if pending is not None else None
+        split, base = None, pending                # base: the clustering the records below run on
+        if sspec is not None:                      # behind the cluster passes, same lists; no table can overflow at M rows
+            split = self._enqueue_cluster_split(sess, d_offsets, d_index, pending[0].data_ptr(), pending[2],
+                                                pending[0].data_ptr() + 8 * pending[3], pending[1], n, M, self._dims[:-1], sspec, M, M, M)
+            if getattr(self, '_cluster_split_downstream', False):
+                base = (split[0], split[3], split[8], max(M, 1), n, M)
         objects = None
         if pending is not None and getattr(self, '_cluster_features_on', False):   # behind the cluster passes, same lists
-            objects = self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
+            objects = self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, base, self._dims[:-1])
         pspec = getattr(self, '_cluster_profile_spec', None) if pending is not None else None
         prof = None
         if pspec is not None:                      # behind the object records, which run for it in any case
             prof_objects = objects if objects is not None else \
-                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
-            prof = self._enqueue_cluster_profile(sess, d_offsets, d_index, self._fed_value, pending, prof_objects, self._dims[:-1],
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, base, self._dims[:-1])
+            prof = self._enqueue_cluster_profile(sess, d_offsets, d_index, self._fed_value, base, prof_objects, self._dims[:-1],
                                                  pspec, self._profile_bin_cap(M, pspec))
         vspec = getattr(self, '_cluster_vertex_spec', None) if pending is not None else None
         vtx = None
         if vspec is not None:                      # behind the object records, which run for it in any case
             vtx_objects = objects if objects is not None else prof_objects if pspec is not None else \
-                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
-            vtx = self._enqueue_cluster_vertices(sess, d_offsets, d_index, pending, vtx_objects, pending[1], self._dims[:-1], vspec,
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, base, self._dims[:-1])
+            vtx = self._enqueue_cluster_vertices(sess, d_offsets, d_index, base, vtx_objects, base[1], self._dims[:-1], vspec,
                                                  M, self._vertex_inc_cap(M))
         cspec = getattr(self, '_cluster_chain_spec', None) if pending is not None else None
         chain = None
         if cspec is not None:                      # behind the object records, which run for it in any case
             chain_objects = objects if objects is not None else prof_objects if pspec is not None else \
                 vtx_objects if vspec is not None else \
-                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
-            chain = self._enqueue_cluster_chains(sess, d_offsets, d_index, pending, chain_objects, pending[1], self._dims[:-1],
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, base, self._dims[:-1])
+            chain = self._enqueue_cluster_chains(sess, d_offsets, d_index, base, chain_objects, base[1], self._dims[:-1],
                                                  cspec, M)
         nspec = getattr(self, '_cluster_cone_spec', None) if pending is not None else None
         cone = None
         if nspec is not None:                      # behind the object records, which run for it in any case
             cone_objects = objects if objects is not None else prof_objects if pspec is not None else \
                 vtx_objects if vspec is not None else chain_objects if cspec is not None else \
-                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, pending, self._dims[:-1])
-            cone = self._enqueue_cluster_cones(sess, d_offsets, d_index, pending, cone_objects, pending[1], self._dims[:-1],
+                self._enqueue_cluster_features(sess, d_offsets, d_index, self._fed_value, base, self._dims[:-1])
+            cone = self._enqueue_cluster_cones(sess, d_offsets, d_index, base, cone_objects, base[1], self._dims[:-1],
                                                nspec, M)
         truth = match = None
         if matching:                               # the TRUE classes under the same spec, then the match of the two id arrays
@@ -1190,7 +1211,7 @@ class ssnet_base(object):
         gspec = getattr(self, '_cluster_graph_spec', None) if pending is not None else None
         graph = None
         if gspec is not None:                      # behind the cluster passes, same lists
-            graph = self._enqueue_cluster_graph(sess, d_offsets, d_index, self._fed_value, pending[0], pending[2], pending[1], n, M,
+            graph = self._enqueue_cluster_graph(sess, d_offsets, d_index, self._fed_value, base[0], base[2], base[1], n, M,
                                                 self._dims[:-1], gspec, M + 1024, True)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self._device))
@@ -1203,24 +1224,27 @@ class ssnet_base(object):
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
         if pending is not None:
             res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
+        if split is not None:
+            res['split'] = self._fetch_cluster_split(split, off, [int(t['first'].size) for t in res['clusters']])
+        src = res['split'] if base is not pending else res      # what the records below describe: the pieces or the components
         if objects is not None:
-            res['objects'] = self._fetch_cluster_features(objects, res['clusters'])
+            res['objects'] = self._fetch_cluster_features(objects, src['clusters'])
         if match is not None:
             res['true_cluster'], res['true_clusters'] = self._fetch_clusters(truth, off)
             res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
         if graph is not None:
-            res['graph'] = self._finish_cluster_graph(sess, graph, voxels, res, gspec, self._dims[:-1])
+            res['graph'] = self._finish_cluster_graph(sess, graph, voxels, src, gspec, self._dims[:-1])
         if prof is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, res['clusters'])
-            res['profiles'] = self._finish_cluster_profile(sess, prof, records, voxels, res, pspec, self._dims[:-1])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, src['clusters'])
+            res['profiles'] = self._finish_cluster_profile(sess, prof, records, voxels, src, pspec, self._dims[:-1])
         if vtx is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, res['clusters'])
-            res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, voxels, res, vspec, self._dims[:-1])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, src['clusters'])
+            res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, voxels, src, vspec, self._dims[:-1])
         if chain is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, res['clusters'])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, src['clusters'])
             res['chains'] = self._fetch_cluster_chains(chain, records, off)
         if cone is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(cone_objects, res['clusters'])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(cone_objects, src['clusters'])
             res['cones'] = self._fetch_cluster_cones(cone, records, off)
         if with_labels:
             res['acc_all'], res['acc_nonzero'] = float(acc[0]), float(acc[1])
@@ -2392,6 +2416,148 @@ class ssnet_base(object):
             edge_cap = min(2 * edge_cap, max(most, 1), 2 ** 30 - 1)
 
     # ------------------------------------------------------------------------------------------
+    # cluster splits: a component of several particles cut at its junctions and kinks (definition and numpy statement:
+    # clusters.cluster_split_numpy, device passes: csrc/cluster_split.hip)
+    # ------------------------------------------------------------------------------------------
+    def set_cluster_split(self, spec, downstream=False):
+        """A ``clusters.ClusterSplitSpec``: while one is set, and a cluster spec is set, and ``'cluster'`` is wanted,
+        ``inference_voxel_scores`` and ``inference_tiled_voxel_scores`` enqueue ``ursn_cluster_split`` behind the cluster passes
+        (tiled: on the stitched list in the large shape) and the result gains ``split``: what ``cluster_split`` returns.  With
+        ``downstream`` the object records, profiles, vertices, chains, cones and graph of those calls run on the pieces instead of
+        the components; ``cluster`` / ``clusters`` and matching stay on the components.  None switches it off; never called, the
+        results are what they were."""
+        from .clusters import ClusterSplitSpec
+        if spec is not None and not isinstance(spec, ClusterSplitSpec):
+            raise ValueError('set_cluster_split: spec = %r, expected a clusters.ClusterSplitSpec or None' % (spec,))
+        if type(downstream) is not bool:
+            raise ValueError('set_cluster_split: downstream = %r, expected a bool' % (downstream,))
+        self._cluster_split_spec, self._cluster_split_downstream = spec, bool(downstream and spec is not None)
+
+    def _enqueue_cluster_split(self, sess, d_offsets, d_index, d_cluster, d_toff, d_size, d_cls, n, M, shape, spec, cap_pieces,
+                               cap_junctions, cap_rows):
+        """``ursn_cluster_split`` on device lists, ids, table offsets and the table's size / cls (raw pointers or tensors); enqueues
+        only.  The piece table it writes stays on the device for the calls that run on the pieces."""
+        import torch
+        lib = _lib.load()
+        shape = [int(s) for s in shape]
+        need = int(lib.ursn_cluster_split_scratch_bytes(n, M))
+        if need == 0:
+            raise ValueError('cluster_split: %d events with %d list entries are out of domain' % (n, M))
+        if d_cls is None and spec.classes is not None:
+            raise ValueError('cluster_split: spec = %r needs the cluster table\'s cls' % (spec,))
+        new = lambda shp, dt: torch.empty(shp, dtype=dt, device=self._device)
+        cp, cj, cr = (int(min(max(c, 0), max(M, 0))) for c in (cap_pieces, cap_junctions, cap_rows))
+        scratch = new(need // 8, torch.int64)
+        split, mark, small = new(max(M, 1), torch.int32), new(max(M, 1), torch.uint8), new(2 * max(cp, 1), torch.int32)   # first | size
+        pcls, pi = new(max(cp, 1), torch.uint8), new((max(cp, 1), _lib.CLSPLIT_PI), torch.int64)
+        ji, jr = new((max(cj, 1), _lib.CLSPLIT_JI), torch.int64), new((max(cj, 1), _lib.CLSPLIT_JR), torch.float64)
+        rows = new((max(cr, 1), _lib.CLSPLIT_ROW), torch.int32)
+        poff, joff, ev, status = new(n + 1, torch.int64), new(n + 1, torch.int64), new((n, _lib.CLSPLIT_EV), torch.int64), \
+            new(1, torch.int32)
+        ptr = lambda x: None if x is None else x.data_ptr() if hasattr(x, 'data_ptr') else int(x)
+        d = _lib.ursn_cluster_split_desc()
+        d.ndim, d.n, d.m_total, d.radius = len(shape), n, M, spec.radius
+        for i, s in enumerate(shape):
+            d.spatial[i] = s
+        d.offsets, d.index, d.cluster, d.table_offsets = ptr(d_offsets), ptr(d_index), ptr(d_cluster), ptr(d_toff)
+        d.size, d.cls = ptr(d_size), ptr(d_cls)
+        d.kink_cos, d.min_size, d.class_mask, d.grow = spec.kink_cos, spec.min_size, spec.class_mask(), spec.grow
+        o = _lib.ursn_cluster_split_out()
+        o.split, o.mark, o.piece_offsets = split.data_ptr(), mark.data_ptr(), poff.data_ptr()
+        o.first, o.size, o.cls = small.data_ptr(), small.data_ptr() + 4 * max(cp, 1), pcls.data_ptr()
+        o.piece_itab, o.cap_pieces = pi.data_ptr(), cp
+        o.junction_offsets, o.junction_itab, o.junction_rtab, o.cap_junctions = joff.data_ptr(), ji.data_ptr(), jr.data_ptr(), cj
+        o.rows, o.cap_rows, o.event, o.status = rows.data_ptr(), cr, ev.data_ptr(), status.data_ptr()
+        _lib.check(lib.ursn_cluster_split(ctypes.byref(d), ctypes.byref(o), self._ptr(scratch), need, self._stream(sess)))
+        cur = torch.cuda.current_stream(self._device)
+        for t in (scratch, split, mark, small, pcls, pi, ji, jr, rows, poff, joff, ev, status) + \
+                tuple(x for x in (d_cluster, d_toff, d_size, d_cls) if hasattr(x, 'record_stream')):
+            t.record_stream(cur)
+        return split, mark, small, pcls, pi, ji, jr, rows, poff, joff, ev, status, cp, cj, cr, n, M
+
+    @staticmethod
+    def _fetch_cluster_split(sp, off, counts):
+        """The tables as ``cluster_split`` returns them (``counts``: cluster rows per event), or the true (pieces, junctions) when a
+        table was too small; raises on a status."""
+        from .clusters import SPLIT_EVENT, SPLIT_JUNCTION_INT, SPLIT_JUNCTION_REAL, SPLIT_PIECE, SPLIT_ROW
+        split, mark, small, pcls, pi, ji, jr, rows, poff, joff, ev, status, cp, cj, cr, n, M = sp
+        code = int(status.cpu().numpy()[0])
+        if code != 0:
+            raise _lib.UrsnError('cluster_split: the ids, table offsets and lists disagree (status %d)' % code)
+        poff, joff, ev = poff.cpu().numpy(), joff.cpu().numpy(), ev.cpu().numpy()
+        P, J, K = int(poff[-1]), int(joff[-1]), int(sum(counts))
+        if P > cp or J > cj:
+            return P, J
+        assert K <= cr or K == 0, 'cluster_split: %d rows, room for %d' % (K, cr)
+        split, mark, small, pcls = split[:M].cpu().numpy(), mark[:M].cpu().numpy(), small.cpu().numpy(), pcls[:P].cpu().numpy()
+        pi, ji, jr, rows = pi[:P].cpu().numpy(), ji[:J].cpu().numpy(), jr[:J].cpu().numpy(), rows[:K].cpu().numpy()
+        events, ids, tables, at, width = [], [], [], 0, max(cp, 1)
+        for i, k in enumerate(counts):
+            lo, hi, jlo, jhi = int(poff[i]), int(poff[i + 1]), int(joff[i]), int(joff[i + 1])
+            junctions = {name: ji[jlo:jhi, c].copy() for c, name in enumerate(SPLIT_JUNCTION_INT)}
+            junctions.update({name: jr[jlo:jhi, c].copy() for c, name in enumerate(SPLIT_JUNCTION_REAL)})
+            events.append({'pieces': {name: pi[lo:hi, c].copy() for c, name in enumerate(SPLIT_PIECE)}, 'junctions': junctions,
+                           'rows': {name: rows[at:at + k, c].copy() for c, name in enumerate(SPLIT_ROW)},
+                           'mark': mark[off[i]:off[i + 1]].copy(), 'event': dict(zip(SPLIT_EVENT, (int(x) for x in ev[i])))})
+            ids.append(split[off[i]:off[i + 1]].copy())
+            tables.append({'first': small[lo:hi].copy(), 'size': small[width + lo:width + hi].copy(), 'cls': pcls[lo:hi].copy()})
+            at += k
+        return {'events': events, 'cluster': ids, 'clusters': tables}
+
+    def cluster_split(self, sess, voxels_or_lists, clusters, spec, shape=None):
+        """The split of clusters already made: ``voxels_or_lists`` and ``shape`` as ``cluster_voxels`` took them, ``clusters`` the
+        dict it returned (or a result's ``cluster`` / ``clusters`` under those keys), ``spec`` a ``clusters.ClusterSplitSpec``.
+        Returns ``{'events': [...], 'cluster': [...], 'clusters': [...]}``: per event a dict -- ``pieces`` (named columns
+        ``clusters.SPLIT_PIECE``, one row per piece), ``junctions`` (``SPLIT_JUNCTION_INT`` / ``SPLIT_JUNCTION_REAL``, one row per
+        junction), ``rows`` (``SPLIT_ROW``, one row per cluster), ``mark`` uint8 [m_i] and ``event`` (a dict over ``SPLIT_EVENT``)
+        -- and, as ``cluster`` / ``clusters``, the pieces as a clustering of the same lists: the piece ids int32 [m_i] and the table
+        ``first`` / ``size`` / ``cls``.  The returned dict is itself a legal ``clusters`` argument of every call that takes one
+        (none of them needs ``first`` to ascend).  The piece and junction tables start at an estimate (4 K + 1024 and K + 1024
+        rows); when the device counts more, the call runs once more with the true counts."""
+        import torch
+        from .clusters import ClusterSplitSpec
+        if not isinstance(spec, ClusterSplitSpec):
+            raise ValueError('cluster_split: spec = %r, expected a clusters.ClusterSplitSpec' % (spec,))
+        shape = [int(s) for s in (self._dims[:-1] if shape is None else shape)]
+        if len(shape) not in (2, 3) or any(not 1 <= s <= 32768 for s in shape) or int(np.prod(shape, dtype=np.int64)) >= 2 ** 31:
+            raise ValueError('cluster_split: shape = %r, expected 2 or 3 extents in [1, 32768] with a product below 2^31' % (shape,))
+        if isinstance(voxels_or_lists, (VoxelBatch, _DeviceVoxelBatch)):
+            off, index = np.asarray(voxels_or_lists.offsets, np.int64), np.asarray(voxels_or_lists.index, np.int32)
+        else:
+            lists = [np.asarray(a, np.int32).reshape(-1) for a in voxels_or_lists]
+            off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+            index = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        n, M = off.size - 1, int(off[-1])
+        if not 1 <= n <= 65535:
+            raise ValueError('cluster_split: %d events outside [1, 65535]' % n)
+        ids, tables = clusters['cluster'], clusters['clusters']
+        if len(ids) != n or len(tables) != n:
+            raise ValueError('cluster_split: %d events, clusters of %d / %d' % (n, len(ids), len(tables)))
+        cluster = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in ids])
+        if cluster.size != M or index.size != M:
+            raise ValueError('cluster_split: %d list entries, %d indices, %d ids' % (M, index.size, cluster.size))
+        counts = [int(t['first'].size) for t in tables]
+        toff = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        K = int(toff[-1])
+        cls = np.concatenate([np.asarray(t['cls'], np.uint8).reshape(-1) for t in tables])
+        size = np.concatenate([np.asarray(t['size'], np.int32).reshape(-1) for t in tables])
+        if cls.size != K or size.size != K:
+            raise ValueError('cluster_split: %d rows, %d sizes, %d classes' % (K, size.size, cls.size))
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a if a.size else np.zeros(1, dt), dtype=dt)).to(self._device)
+        d_off, d_index, d_toff, d_cluster = up(off, np.int64), up(index, np.int32), up(toff, np.int64), up(cluster, np.int32)
+        d_size, d_cls = up(size, np.int32), up(cls, np.uint8)
+        est = getattr(self, '_cluster_split_estimate', (4, 1024, 1, 1024))
+        cap_pieces, cap_junctions = est[0] * K + est[1], est[2] * K + est[3]
+        for _ in range(2):
+            sp = self._enqueue_cluster_split(sess, d_off, d_index, d_cluster, d_toff, d_size, d_cls, n, M, shape, spec, cap_pieces,
+                                             cap_junctions, K)
+            got = self._fetch_cluster_split(sp, off, counts)
+            if isinstance(got, dict):
+                return got
+            cap_pieces, cap_junctions = got
+        raise _lib.UrsnError('cluster_split: %d pieces and %d junctions did not fit the tables made for them' % got)
+
+    # ------------------------------------------------------------------------------------------
     # tiling: volumes larger than the network (not in the reference, whose events have the network's size; boxes, their
     # cores and the numpy statement of the device passes: tiling.py)
     # ------------------------------------------------------------------------------------------
@@ -2641,44 +2807,51 @@ class ssnet_base(object):
         pending = None
         if spec is not None:                       # behind the last scatter, on the stitched list in the large shape
             pending = self._enqueue_clusters(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], out[spec.on], n, M, big, spec)
+        sspec = getattr(self, '_cluster_split_spec', None) if pending is not None else None
+        split, base = None, pending                # base: the clustering the records below run on
+        if sspec is not None:                      # the stitched list, in the large shape; no table can overflow at M rows
+            split = self._enqueue_cluster_split(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending[0].data_ptr(), pending[2],
+                                                pending[0].data_ptr() + 8 * pending[3], pending[1], n, M, big, sspec, M, M, M)
+            if getattr(self, '_cluster_split_downstream', False):
+                base = (split[0], split[3], split[8], max(M, 1), n, M)
         objects = None
         if pending is not None and getattr(self, '_cluster_features_on', False):   # the stitched list, in the large shape
             objects = self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'],
-                                                     big_batch.ptr['value'], pending, big)
+                                                     big_batch.ptr['value'], base, big)
         pspec = getattr(self, '_cluster_profile_spec', None) if pending is not None else None
         prof = None
         if pspec is not None:                      # the stitched list, in the large shape, behind the object records
             prof_objects = objects if objects is not None else \
                 self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
-                                               pending, big)
+                                               base, big)
             prof = self._enqueue_cluster_profile(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
-                                                 pending, prof_objects, big, pspec, self._profile_bin_cap(M, pspec))
+                                                 base, prof_objects, big, pspec, self._profile_bin_cap(M, pspec))
         vspec = getattr(self, '_cluster_vertex_spec', None) if pending is not None else None
         vtx = None
         if vspec is not None:                      # the stitched list, in the large shape: a vertex joins ends from two tiles
             vtx_objects = objects if objects is not None else prof_objects if pspec is not None else \
                 self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
-                                               pending, big)
-            vtx = self._enqueue_cluster_vertices(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, vtx_objects,
-                                                 pending[1], big, vspec, M, self._vertex_inc_cap(M))
+                                               base, big)
+            vtx = self._enqueue_cluster_vertices(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], base, vtx_objects,
+                                                 base[1], big, vspec, M, self._vertex_inc_cap(M))
         cspec = getattr(self, '_cluster_chain_spec', None) if pending is not None else None
         chain = None
         if cspec is not None:                      # the stitched list, in the large shape: a track cut at a tile seam is joined
             chain_objects = objects if objects is not None else prof_objects if pspec is not None else \
                 vtx_objects if vspec is not None else \
                 self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
-                                               pending, big)
-            chain = self._enqueue_cluster_chains(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, chain_objects,
-                                                 pending[1], big, cspec, M)
+                                               base, big)
+            chain = self._enqueue_cluster_chains(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], base, chain_objects,
+                                                 base[1], big, cspec, M)
         nspec = getattr(self, '_cluster_cone_spec', None) if pending is not None else None
         cone = None
         if nspec is not None:                      # the stitched list, in the large shape: a shower crosses tile seams
             cone_objects = objects if objects is not None else prof_objects if pspec is not None else \
                 vtx_objects if vspec is not None else chain_objects if cspec is not None else \
                 self._enqueue_cluster_features(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
-                                               pending, big)
-            cone = self._enqueue_cluster_cones(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], pending, cone_objects,
-                                               pending[1], big, nspec, M)
+                                               base, big)
+            cone = self._enqueue_cluster_cones(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], base, cone_objects,
+                                               base[1], big, nspec, M)
         truth = match = None
         if matching:                               # the large batch's own labels under the same spec, then the match
             at = big_batch.ptr['label'] - big_batch.dev.data_ptr()
@@ -2690,7 +2863,7 @@ class ssnet_base(object):
         graph = None
         if gspec is not None:                      # the stitched list, in the large shape: groups cross tile borders
             graph = self._enqueue_cluster_graph(sess, big_batch.ptr['offsets'], big_batch.ptr['index'], big_batch.ptr['value'],
-                                                pending[0], pending[2], pending[1], n, M, big, gspec, M + 1024, True)
+                                                base[0], base[2], base[1], n, M, big, gspec, M + 1024, True)
         res = {'index': [big_batch.index[off[i]:off[i + 1]].copy() for i in range(n)]}
         for w in want:
             if w == 'cluster':
@@ -2699,29 +2872,32 @@ class ssnet_base(object):
             res[w] = [host[off[i]:off[i + 1]].copy() for i in range(n)]
         if pending is not None:
             res['cluster'], res['clusters'] = self._fetch_clusters(pending, off)
+        if split is not None:
+            res['split'] = self._fetch_cluster_split(split, off, [int(t['first'].size) for t in res['clusters']])
+        src = res['split'] if base is not pending else res      # what the records below describe: the pieces or the components
         if objects is not None:
-            res['objects'] = self._fetch_cluster_features(objects, res['clusters'])
+            res['objects'] = self._fetch_cluster_features(objects, src['clusters'])
         if match is not None:
             res['true_cluster'], res['true_clusters'] = self._fetch_clusters(truth, off)
             res['match'] = self._fetch_cluster_match(match, res['clusters'], res['true_clusters'])
         if graph is not None:
             lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
-            res['graph'] = self._finish_cluster_graph(sess, graph, lists, res, gspec, big, value=lambda: self._resident_value(big_batch))
+            res['graph'] = self._finish_cluster_graph(sess, graph, lists, src, gspec, big, value=lambda: self._resident_value(big_batch))
         if prof is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, res['clusters'])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(prof_objects, src['clusters'])
             lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
-            res['profiles'] = self._finish_cluster_profile(sess, prof, records, lists, res, pspec, big,
+            res['profiles'] = self._finish_cluster_profile(sess, prof, records, lists, src, pspec, big,
                                                            value=lambda: self._resident_value(big_batch))
         if vtx is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, res['clusters'])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(vtx_objects, src['clusters'])
             lists = [big_batch.index[off[i]:off[i + 1]] for i in range(n)]
-            res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, lists, res, vspec, big,
+            res['vertices'] = self._finish_cluster_vertices(sess, vtx, records, lists, src, vspec, big,
                                                             value=lambda: self._resident_value(big_batch))
         if chain is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, res['clusters'])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(chain_objects, src['clusters'])
             res['chains'] = self._fetch_cluster_chains(chain, records, off)
         if cone is not None:
-            records = res['objects'] if objects is not None else self._fetch_cluster_features(cone_objects, res['clusters'])
+            records = res['objects'] if objects is not None else self._fetch_cluster_features(cone_objects, src['clusters'])
             res['cones'] = self._fetch_cluster_cones(cone, records, off)
         res['tiles_total'], res['tiles_run'], res['forwards'] = len(boxes), int(keep.size), forwards
         return res

@@ -34,7 +34,7 @@ import numpy as np
 
 from . import optim, symmetry, tiling
 from .config import ssnet_config
-from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, chains_csv_header, chains_csv_row, cones_csv_header, cones_csv_row, profiles_csv_header, profiles_csv_row, vertices_csv_header, vertices_csv_row
+from .ssnet import HipSession, ana_csv_header, ana_csv_row, graph_csv_header, graph_csv_row, match_csv_header, match_csv_row, objects_csv_header, objects_csv_row, chains_csv_header, chains_csv_row, cones_csv_header, cones_csv_row, split_csv_header, split_csv_row, profiles_csv_header, profiles_csv_row, vertices_csv_header, vertices_csv_row
 from .synthetic_io import synthetic_threadio
 from .uresnet import uresnet
 from .weights import WeightSpec
@@ -90,6 +90,7 @@ class ssnet_trainval(object):
         self._vertices = None
         self._chains = None
         self._cones = None
+        self._split = None
         self._iteration = -1
         self._sess = None
         self._net = None
@@ -194,6 +195,8 @@ class ssnet_trainval(object):
             raise ValueError('ANA_VERTICES needs ANA_CLUSTER: the vertices are where the end points of the clusters meet')
         if cfg.ANA_CHAINS and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_CHAINS needs ANA_CLUSTER: the chains join the clusters that are fragments of one track')
+        if cfg.ANA_SPLIT and not cfg.TRAIN and not cfg.ANA_CLUSTER:
+            raise ValueError('ANA_SPLIT needs ANA_CLUSTER: the split cuts the clusters at their junctions and kinks')
         if cfg.ANA_CONES and not cfg.TRAIN and not cfg.ANA_CLUSTER:
             raise ValueError('ANA_CONES needs ANA_CLUSTER: the cones gather the clusters that are fragments of one shower')
         self._weight_spec = None
@@ -249,6 +252,12 @@ class ssnet_trainval(object):
             if fresh:
                 self._chains.write(chains_csv_header())
                 self._chains.flush()
+        if cfg.ANA_SPLIT and not cfg.TRAIN:
+            fresh = not os.path.isfile(cfg.ANA_SPLIT) or os.path.getsize(cfg.ANA_SPLIT) == 0
+            self._split = open(cfg.ANA_SPLIT, 'a')
+            if fresh:
+                self._split.write(split_csv_header())
+                self._split.flush()
         if cfg.ANA_CONES and not cfg.TRAIN:
             fresh = not os.path.isfile(cfg.ANA_CONES) or os.path.getsize(cfg.ANA_CONES) == 0
             self._cones = open(cfg.ANA_CONES, 'a')
@@ -288,6 +297,11 @@ class ssnet_trainval(object):
                 from .clusters import ClusterChainSpec
                 self._net.set_cluster_chains(ClusterChainSpec(cfg.CHAIN_GAP, cfg.CHAIN_MIN_COS, cfg.CHAIN_MIN_SIZE,
                                                               cfg.CHAIN_CLASSES or None, cfg.CHAIN_SAME_CLASS))
+            if self._split:                  # default off: never called
+                from .clusters import ClusterSplitSpec
+                self._net.set_cluster_split(ClusterSplitSpec(cfg.SPLIT_RADIUS, cfg.SPLIT_KINK_COS, cfg.SPLIT_MIN_SIZE,
+                                                             cfg.SPLIT_CLASSES or None, None if cfg.SPLIT_GROW < 0 else cfg.SPLIT_GROW),
+                                            downstream=cfg.SPLIT_DOWNSTREAM)
             if self._cones:                  # default off: never called
                 from .clusters import ClusterConeSpec
                 self._net.set_cluster_cones(ClusterConeSpec(cfg.CONE_REACH, cfg.CONE_MIN_COS, cfg.CONE_SEED_SIZE, cfg.CONE_MIN_SIZE,
@@ -644,6 +658,7 @@ class ssnet_trainval(object):
         self._write_vertices(r, entries)
         self._write_chains(r, entries)
         self._write_cones(r, entries)
+        self._write_split(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -667,6 +682,9 @@ class ssnet_trainval(object):
                     if 'cones' in r:
                         ev['cones'] = {'merged': r['cones']['cluster'][i], 'table': r['cones']['clusters'][i],
                                        **r['cones']['events'][i]}
+                    if 'split' in r:
+                        ev['split'] = {'split': r['split']['cluster'][i], 'table': r['split']['clusters'][i],
+                                       **r['split']['events'][i]}
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events}
             if 'match' in r:
                 result['match'] = r['match']
@@ -731,6 +749,16 @@ class ssnet_trainval(object):
                 self._chains.write(chains_csv_row(entries[i], k, cols))
         self._chains.flush()
 
+    def _write_split(self, r, entries):
+        """ANA_SPLIT: one CSV row per junction of every event of the result ``r``."""
+        if not getattr(self, '_split', None) or 'split' not in r:
+            return
+        for i in range(len(entries)):
+            cols = r['split']['events'][i]['junctions']
+            for k in range(int(cols['row'].size)):
+                self._split.write(split_csv_row(entries[i], k, cols))
+        self._split.flush()
+
     def _write_cones(self, r, entries):
         """ANA_CONES: one CSV row per shower of every event of the result ``r``."""
         if not getattr(self, '_cones', None) or 'cones' not in r:
@@ -771,6 +799,7 @@ class ssnet_trainval(object):
         self._write_vertices(r, entries)
         self._write_chains(r, entries)
         self._write_cones(r, entries)
+        self._write_split(r, entries)
         result = None
         if not batch_mode:
             off = vb.offsets
@@ -794,6 +823,9 @@ class ssnet_trainval(object):
                     if 'cones' in r:
                         ev['cones'] = {'merged': r['cones']['cluster'][i], 'table': r['cones']['clusters'][i],
                                        **r['cones']['events'][i]}
+                    if 'split' in r:
+                        ev['split'] = {'split': r['split']['cluster'][i], 'table': r['split']['clusters'][i],
+                                       **r['split']['events'][i]}
             result = {'entries': np.array(entries), 'acc_all': acc_all, 'acc_nonzero': acc_nonzero, 'voxels': events,
                       'tiles': (r['tiles_run'], r['tiles_total'])}
             if 'match' in r:
@@ -966,7 +998,7 @@ class ssnet_trainval(object):
             if io is not None:
                 io.reset()
                 setattr(self, attr, None)
-        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_vertices', '_chains', '_cones', '_writer_train', '_writer_test'):
+        for attr in ('_output', '_csv', '_objects', '_match', '_graph', '_profiles', '_vertices', '_chains', '_cones', '_split', '_writer_train', '_writer_test'):
             f = getattr(self, attr, None)
             if f is not None:
                 f.close()
