@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import _chain_cases as cases
+import _far_corner as far
 from _guard import Guarded
 from uresnet_amd import _lib, uresnet
 from uresnet_amd import synthetic_io as sio
@@ -279,6 +280,27 @@ def test_no_entries_and_no_clusters(lib):
     want = _check(lib, [0, 4, 6], np.array([1, 5, 9, 200, 3, 4]), None, np.full(6, -1), [0, 0, 0], shape, spec, cap_rows=6, cap_chains=6,
                   cap_joins=6)
     assert want["events"].tolist() == [[0, 0, 0, -1], [0, 0, 0, -1]] and want["merged"].tolist() == [-1] * 6
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_CAPPED, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The fixtures, the ring and the line against the far faces, at the origin and across index 2^30, at max_gap 31: search windows
+    that a far face clips (tests/test_far_corner_host.py asserts that joins are accepted through such windows)."""
+    b = far.far_batch("chain", shape).big
+    for same_class in (True, False):
+        want = _check(lib, b.off, b.index, b.value, b.cluster, b.toff, shape, ClusterChainSpec(31, 0.7, 2, None, same_class), cls=b.tcls)
+        assert want["join_offsets"][-1] > 0
+        assert all(want["chains"]["hi%d" % a].max() == shape[a] - 1 for a in range(len(shape)))
+    _check(lib, b.off, b.index, None, b.cluster, b.toff, shape, ClusterChainSpec(3, 0.9, 3, None, False), cls=None)
+
+
+@pytest.mark.parametrize("axis", sorted(far.LONG_TRACK))
+def test_a_track_across_the_longest_axis(lib, axis):
+    """One cluster of 32,768 members from corner to corner: one chain of one row, whose end points have nothing to search."""
+    s = far.long_track(far.LONG_TRACK[axis])
+    want = _check(lib, s.off, s.index, s.value, s.cluster, s.toff, s.shape, far.WIDEST["chain"], cls=s.tcls)
+    assert want["events"][0, :2].tolist() == [1, 0] and want["chains"]["hi%d" % axis].tolist() == [32767]
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

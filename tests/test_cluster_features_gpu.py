@@ -12,6 +12,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _guard import Guarded
 from uresnet_amd import _lib, uresnet
 from uresnet_amd import synthetic_io as sio
@@ -260,6 +261,29 @@ def test_random_lists(lib, conn):
             cluster, toff = _ids(off, index, cls, shape, ClusterSpec(conn, None, same_class, min_size))
             assert toff[-1] > 20
             _check(lib, off, index, value, cluster, toff, shape)
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_CAPPED, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The random lists against the far faces, at the origin and across index 2^30 (tests/test_far_corner_host.py asserts what the
+    batch reaches), under the clustering they come with and under the narrowest one."""
+    b = far.far_batch("random", shape).big
+    want = _check(lib, b.off, b.index, b.value, b.cluster, b.toff, shape)
+    top = np.array(shape + (1,) * (3 - len(shape))) - 1
+    assert (want["hi"].max(axis=0) == top).all()
+    cluster, toff, _ = far.clustered("random", shape, 6 if len(shape) == 3 else 4, False)
+    assert toff[-1] > b.toff[-1]
+    _check(lib, b.off, b.index, None, cluster, toff, shape)
+
+
+@pytest.mark.parametrize("axis", sorted(far.LONG_TRACK))
+def test_a_track_across_the_longest_axis(lib, axis):
+    """One cluster of 32,768 members from the origin corner to the far corner: the largest sums and second moments a row takes."""
+    s = far.long_track(far.LONG_TRACK[axis])
+    want = _check(lib, s.off, s.index, s.value, s.cluster, s.toff, s.shape)
+    assert want["n"].tolist() == [32768] and want["lo"][0].tolist() == [0, 0, 0] and want["hi"][0].tolist() == [d - 1 for d in s.shape]
+    assert want["dd"][0][axis] > 2.9e12 and want["length"][0] > 32767
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

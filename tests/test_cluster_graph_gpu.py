@@ -12,6 +12,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _guard import Guarded
 from uresnet_amd import _lib, uresnet
 from uresnet_amd import synthetic_io as sio
@@ -326,6 +327,21 @@ def test_an_id_outside_its_events_rows_sets_status(lib):
     with pytest.raises(_lib.UrsnError) as e:
         net.cluster_graph(None, lists, broken, ClusterGraphSpec(1), shape=s2)
     assert "cluster_graph" in str(e.value)
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_CAPPED, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The random lists against the far faces, at the origin and across index 2^30 (tests/test_far_corner_host.py asserts what the
+    batch reaches): every box of the search is clipped by a far face somewhere, and the group boxes carry the largest coordinates."""
+    b = far.far_batch("random", shape).big
+    for gap in (3, 1):
+        want = _check(lib, b.off, b.index, b.cluster, b.toff, shape, gap, value=b.value, cls=b.tcls)
+        assert want["edge_offsets"][-1] > 0
+    hi = want["groups"][:, 7:7 + len(shape)]
+    assert (hi.max(axis=0) == np.array(shape) - 1).all()
+    cluster, toff, tcls = far.clustered("random", shape, 6 if len(shape) == 3 else 4, False)
+    _check(lib, b.off, b.index, cluster, toff, shape, 3, value=None, cls=tcls)
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

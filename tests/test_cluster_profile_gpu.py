@@ -13,6 +13,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _guard import Guarded
 from uresnet_amd import _lib, uresnet
 from uresnet_amd import synthetic_io as sio
@@ -251,6 +252,35 @@ def test_no_entries_and_no_clusters(lib):
     _check(lib, [0, 0], z, None, z, [0, 0], shape, spec, cap_rows=5, bin_cap=7, feat_cap=5)
     _check(lib, [0, 4, 6], np.array([1, 5, 9, 200, 3, 4]), np.ones(6, np.float32), np.full(6, -1), [0, 0, 0], shape, spec, cap_rows=6,
            bin_cap=6, feat_cap=6)
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_CAPPED, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The random lists against the far faces, at the origin and across index 2^30 (tests/test_far_corner_host.py asserts what the
+    batch reaches): the bin centroids are positions in the large shape."""
+    b = far.far_batch("random", shape).big
+    want = _check(lib, b.off, b.index, b.value, b.cluster, b.toff, shape, far.WIDEST["profile"])
+    top = max(want["bins"]["c%d" % a].max() / (shape[a] - 1) for a in range(len(shape)))
+    assert top > 0.999 and want["rows"]["bins"].max() >= 8
+    cluster, toff, _ = far.clustered("random", shape, 6 if len(shape) == 3 else 4, False)
+    _check(lib, b.off, b.index, None, cluster, toff, shape, ClusterProfileSpec(1.0, 3, 4096))
+
+
+@pytest.mark.parametrize("axis", sorted(far.LONG_TRACK))
+def test_a_track_across_the_longest_axis(lib, axis):
+    """One cluster of 32,768 members from corner to corner, length 32768.98 along axis 0: at step 0.5 that is 65,538 segments, cut
+    to the record's stated maximum of 65,536 with bit 1 of the flags.  The track that drifts by 150 only has a length in
+    [32767.5, 32768): exactly 65,536 segments and no flag; max_bins 65535 cuts that one too."""
+    s = far.long_track(far.LONG_TRACK[axis])
+    want = _check(lib, s.off, s.index, s.value, s.cluster, s.toff, s.shape, ClusterProfileSpec(0.5, 16, 65536))
+    assert want["rows"]["bins"].tolist() == [65536] and want["rows"]["flags"].tolist() == [2]
+    if axis == 0:
+        s = far.long_track(far.LONG_TRACK[axis], 150)
+        want = _check(lib, s.off, s.index, s.value, s.cluster, s.toff, s.shape, ClusterProfileSpec(0.5, 16, 65536))
+        assert 32767.5 <= want["objects"]["length"][0] < 32768 and want["rows"]["bins"].tolist() == [65536] and want["rows"]["flags"].tolist() == [0]
+        cut = _check(lib, s.off, s.index, s.value, s.cluster, s.toff, s.shape, ClusterProfileSpec(0.5, 16, 65535))
+        assert cut["rows"]["bins"].tolist() == [65535] and cut["rows"]["flags"].tolist() == [2]
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import _far_corner as far
 import _split_cases as cases
 from _guard import Guarded
 from uresnet_amd import _lib, uresnet
@@ -221,6 +222,18 @@ def test_no_entries_and_no_clusters(lib):
     want = _check(lib, empty([0, 4, 6], [0, 0, 0], np.array([1, 5, 9, 200, 3, 4]), np.full(6, -1)), spec, cap_rows=6, cap_pieces=6,
                   cap_junctions=6)
     assert want["events"].tolist() == [[0, 0, 0, 0], [0, 0, 0, 0]] and want["split"].tolist() == [-1] * 6
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_CAPPED, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The cases against the far faces, at the origin and across index 2^30, at radius 3: balls that a far face clips around
+    junctions (tests/test_far_corner_host.py asserts that a junction lies within the radius of a far face)."""
+    b = far.far_batch("split", shape).big
+    want = _check(lib, far.split_case(b), far.WIDEST["split"])
+    j = want["junctions"]
+    assert j["row"].size > 0 and any(j["hi%d" % a].max() >= shape[a] - 4 for a in range(len(shape)))
+    _check(lib, far.split_case(b), ClusterSplitSpec(1, -0.95, 4, None, 1), use_cls=False)
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

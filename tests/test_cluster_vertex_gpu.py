@@ -14,6 +14,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _guard import Guarded
 from uresnet_amd import _lib, uresnet
 from uresnet_amd import synthetic_io as sio
@@ -304,6 +305,28 @@ def test_no_entries_and_no_clusters(lib):
     want = _check(lib, [0, 4, 6], np.array([1, 5, 9, 200, 3, 4]), None, np.full(6, -1), [0, 0, 0], shape, spec, cap_rows=6, cap_vertices=6,
                   inc_cap=6, inc_out_cap=6)
     assert want["events"].tolist() == [[0, 0, 0, -1], [0, 0, 0, -1]]
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_CAPPED, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The random lists against the far faces, at the origin and across index 2^30 (tests/test_far_corner_host.py asserts what the
+    batch reaches): the end points' neighbourhoods are clipped by the far faces and the vertex records carry the largest positions."""
+    b = far.far_batch("random", shape).big
+    want = _check(lib, b.off, b.index, b.value, b.cluster, b.toff, shape, far.WIDEST["vertex"], cls=b.tcls)
+    v = want["vertices"]
+    assert v["n"].size > 0 and all(v["hi%d" % a].max() == shape[a] - 1 for a in range(len(shape)))
+    cluster, toff, tcls = far.clustered("random", shape, 6 if len(shape) == 3 else 4, False)
+    _check(lib, b.off, b.index, None, cluster, toff, shape, ClusterVertexSpec(3, 1, (1, 2)), cls=tcls)
+    _check(lib, b.off, b.index, b.value, b.cluster, b.toff, shape, ClusterVertexSpec(1, 3), cls=None)
+
+
+@pytest.mark.parametrize("axis", sorted(far.LONG_TRACK))
+def test_a_track_across_the_longest_axis(lib, axis):
+    """One cluster of 32,768 members whose two end points are the origin corner and the far corner: two free ends."""
+    s = far.long_track(far.LONG_TRACK[axis])
+    want = _check(lib, s.off, s.index, s.value, s.cluster, s.toff, s.shape, far.WIDEST["vertex"], cls=s.tcls)
+    assert want["events"][0, 0] == 2 and sorted(want["vertices"]["hi%d" % axis].tolist())[-1] == 32767
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _guard import Guarded
 from uresnet_amd import _lib, tiling, uresnet
 from uresnet_amd import synthetic_io as sio
@@ -285,6 +286,37 @@ def test_two_dimensional_lists(lib, conn):
     # x = 23 of one row and x = 0 of the next
     want = _check(lib, [0, 2], [23, 24], [1, 1], shape, ClusterSpec(conn))
     assert list(want["cluster"]) == [0, 1]
+
+
+# ---- the largest legal extents (tests/_far_corner.py) ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", far.SHAPES_VOLUME, ids=far.shape_id)
+def test_far_corner(lib, shape):
+    """The random lists against the far faces, at the origin and across index 2^30 of a shape that has one quantity at its cap
+    (what the batch reaches is asserted in tests/test_far_corner_host.py)."""
+    b = far.far_batch("random", shape).big
+    assert int(b.index.max()) >= far.volume(shape) - far.volume(shape[1:]) and far.FAR in far.far_batch("random", shape).placement
+    wide, narrow = (26, 6) if len(shape) == 3 else (8, 4)
+    for conn, same_class, min_size in ((wide, True, 2), (wide, False, 1), (narrow, True, 1), (narrow, False, 3)):
+        want = _check(lib, b.off, b.index, b.cls, shape, ClusterSpec(conn, (0, 1, 2), same_class, min_size))
+        assert want["table_offsets"][-1] > 0
+        if (conn, same_class, min_size) == (wide, True, 2):                 # the ids the other calls' far-corner tests are given
+            assert np.array_equal(want["cluster"], b.cluster) and np.array_equal(want["table_offsets"], b.toff)
+
+
+@pytest.mark.parametrize("axis", sorted(far.LONG_TRACK))
+def test_a_track_across_the_longest_axis(lib, axis):
+    """32,768 entries, one 26-connected staircase from the origin corner to the far corner along the capped axis; along axis 2 of
+    (255, 256, 32768) the same list is also clustered as runs: at connectivity 6 every step aside ends a cluster."""
+    s = far.long_track(far.LONG_TRACK[axis])
+    want = _check(lib, s.off, s.index, s.cls, s.shape, ClusterSpec(26))
+    assert want["count"].tolist() == [1] and want["size"].tolist() == [32768]
+    if axis == 2:
+        want = _check(lib, s.off, s.index, s.cls, s.shape, ClusterSpec(6))
+        assert int(want["count"][0]) > 1 and int(want["size"].max()) >= 64
+        x = np.zeros(32768, np.int64)                      # one x-run of 32,768: the last row of the volume
+        x[:] = far.volume(s.shape) - 32768 + np.arange(32768)
+        want = _check(lib, [0, 32768], x, s.cls, s.shape, ClusterSpec(6))
+        assert want["count"].tolist() == [1] and want["size"].tolist() == [32768]
 
 
 # ---- net level -----------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import types
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _abi import _Guarded, same_bits
 from uresnet_amd import _lib, uresnet
 from uresnet_amd import symmetry as S
@@ -291,6 +292,59 @@ def test_voxel_index_sym_finds_the_list_in_the_transformed_volume(lib, spatial):
         assert np.array_equal(out[sel], where[index[sel]]), (spatial, e)
         assert len(set(out[sel].tolist())) == len(sel)
         assert same_bits(vol[e][out[sel]], vb.value[sel]), "gathering the transformed volume at index_out gives the value list"
+
+
+def _far_corner_lists(spatial, n, seed):
+    """n events: the corners of the volume, entries on every far face and random ones; two entries of event 0 outside [0, V)."""
+    rng = np.random.default_rng(seed)
+    nd, top = len(spatial), np.array(spatial, np.int64) - 1
+    corners = np.array([[top[a] if (k >> a) & 1 else 0 for a in range(nd)] for k in range(1 << nd)], np.int64)
+    lists = []
+    for e in range(n):
+        x = rng.integers(0, top + 1, (40 + 8 * nd, nd))
+        for a in range(nd):
+            x[40 + 8 * a:48 + 8 * a, a] = top[a]                             # on the far face of axis a
+        lists.append(np.unique(np.concatenate([far.ravel(corners, spatial), far.ravel(x, spatial)])))
+    off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+    index = np.concatenate(lists)
+    V = far.volume(spatial)
+    index[[1, int(off[1]) - 2]] = [V + 5, -1]
+    return off, index.astype(np.int32)
+
+
+@pytest.mark.parametrize("spatial", [far.CUBE, far.WIDEST_2D], ids=far.shape_id)
+def test_voxel_index_sym_at_the_largest_extents(lib, spatial):
+    """Every code, one event each, in a cube of 1290^3 and in 46340^2 voxels (just under 2^31; no dense volume of that size can be
+    made): the expected values are the closed form o[a] = f_a(i[P[a]]) in Python integers (tests/_far_corner.py, proved equal to
+    apply_numpy on small cubes in tests/test_far_corner_host.py).  The inverse code takes the remapped list back."""
+    import torch
+    nd, V = len(spatial), far.volume(spatial)
+    codes = [int(c) for c in S.group("cube", spatial)]
+    n = len(codes)
+    assert n == S.count(nd) == (48 if nd == 3 else 8) and V > 2 ** 31 - 2 ** 20
+    off, index = _far_corner_lists(spatial, n, 17 + nd)
+    M = index.size
+    d_off, d_idx = torch.from_numpy(off).cuda(), torch.from_numpy(index).cuda()
+    remapped, back = _Placed(M * 4, 1), _Placed(M * 4, 3)
+    inverse = [S.inverse(nd, c) for c in codes]
+    assert all(S.compose(nd, c, i) == 0 and S.compose(nd, i, c) == 0 for c, i in zip(codes, inverse))
+    torch.cuda.synchronize()
+    _lib.check(lib.ursn_voxel_index_sym(nd, _i32(*spatial), n, _i32(*codes), ctypes.c_void_p(d_off.data_ptr()),
+                                        ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(remapped.ptr), None))
+    _lib.check(lib.ursn_voxel_index_sym(nd, _i32(*spatial), n, _i32(*inverse), ctypes.c_void_p(d_off.data_ptr()),
+                                        ctypes.c_void_p(remapped.ptr), ctypes.c_void_p(back.ptr), None))
+    torch.cuda.synchronize()
+    remapped.check_surroundings(), back.check_surroundings()
+    out = remapped.view.cpu().numpy().view(np.int32).copy()
+    assert np.array_equal(d_idx.cpu().numpy(), index), "the input list was written"
+    assert out[1] == V + 5 and out[off[1] - 2] == -1
+    top = far.ravel([[s - 1 for s in spatial]], spatial)[0]
+    for e, c in enumerate(codes):
+        a, z = int(off[e]), int(off[e + 1])
+        want = far.remap_closed_form(index[a:z], spatial, S.perms(nd)[c >> nd], [(c >> k) & 1 for k in range(nd)])
+        assert np.array_equal(out[a:z], want), (spatial, c)
+        assert {0, int(top)} <= set(index[a:z].tolist()) and int(want[want < V].max()) == top   # the corners map to corners
+    assert np.array_equal(back.view.cpu().numpy().view(np.int32), index), "the inverse code does not take the list back"
 
 
 # ---- refusals: non-zero, outputs untouched ----------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import _far_corner as far
 from _abi import _Guarded, same_bits
 from _net import max_rel
 from uresnet_amd import _lib, tiling, uresnet
@@ -283,6 +284,75 @@ def test_scatter_equals_stitch_numpy(lib, ncls):
     ref = np.full(rows_out, 0xFF, np.uint8)
     ref[wild[ok]] = pred[ok]
     assert out.guards_intact() == (True, True) and np.array_equal(out.view.cpu().numpy(), ref)
+
+
+# ---- op level: the largest legal extents (tests/_far_corner.py) ----------------------------------------------------
+FAR_BIG = [(far.LARGEST_VOLUME, (16, 16, 16)), (far.AXIS0_CAP, (16, 16, 16)), (far.WIDEST_2D, (32, 32))]
+
+
+def _far_corner_list(big, seed):
+    """Three events, the middle one empty: a few hundred distinct voxels within 40 of the far corner, the far corner itself, and
+    voxel 0 and its neighbours at the origin."""
+    rng = np.random.default_rng(seed)
+    nd, top = len(big), np.array(big, np.int64) - 1
+    lists = []
+    for m in (300, 0, 400):
+        x = np.concatenate([top - rng.integers(0, 40, (m, nd)), rng.integers(0, 3, (m // 20, nd)), top[None, :][:m], 0 * top[None, :][:m]])
+        lists.append(np.unique(far.ravel(x, big)))
+    off = np.concatenate([[0], np.cumsum([a.size for a in lists])]).astype(np.int64)
+    M = int(off[-1])
+    f = lambda: rng.standard_normal(M).astype(np.float32)
+    return VoxelBatch(off, np.concatenate(lists).astype(np.int32), f(), f(), f(), rng.standard_normal(3).astype(np.float32),
+                      far.volume(big)).validate()
+
+
+@pytest.mark.parametrize("big,tile", FAR_BIG, ids=[far.shape_id(b) for b, _ in FAR_BIG])
+def test_crop_and_scatter_in_the_far_corner(lib, big, tile):
+    """Boxes flush with the far corner, overhanging it by half a tile, entirely beyond it and at the origin, in the largest volume,
+    with axis 0 at its cap and in the widest 2-D shape: the crop against crop_numpy, then the scatter of scores computed on the
+    crop against stitch_numpy."""
+    import torch
+    nd, top = len(big), np.array(big, np.int64) - 1
+    T = np.array(tile, np.int64)
+    vb = _far_corner_list(big, 41 + nd)
+    M = int(vb.offsets[-1])
+    assert int(vb.index.max()) == far.volume(big) - 1 and int(vb.index.min()) == 0 and M > 600
+    origin = [top + 1 - T, top + 1 - T, top + 1 - T // 2, top + 1, top + 1 + T, 0 * T, -(T // 2), top + 1 - 2 * T, top - 20]
+    event = [0, 2, 2, 0, 2, 0, 2, 2, 1]                      # the last: an empty event's box
+    lo = [0 * T] * 8 + [0 * T]
+    hi = [T, T // 2, T, T, T, T, T, T - 3, T]
+    boxes = tiling.Boxes(event, [[int(v) for v in o] for o in origin], [[int(v) for v in a] for a in lo], [[int(v) for v in a] for a in hi])
+    for fill in (0xFF, 0x00):
+        got = _device_crop(lib, vb, big, tile, boxes, scratch_fill=fill)
+        crop, src, owned = _check_crop(got, vb, big, tile, boxes, (big, fill))
+    count = got["count"].tolist()
+    assert count[0] > 0 and count[1] > 0 and count[2] > 0 and count[3:5] == [0, 0] and count[5] > 0 and count[6] > 0 and count[8] == 0
+    one = boxes.select(slice(2, 3))                          # the overhanging box on its own
+    _check_crop(_device_crop(lib, vb, big, tile, one), vb, big, tile, one, (big, "overhang"))
+    # the scatter back into the list: rows of boxes that own them
+    m, ncls = int(crop.offsets[-1]), 3
+    rng = np.random.default_rng(5)
+    scores = rng.standard_normal((m, ncls)).astype(np.float32)
+    pred, ana = rng.integers(0, 200, m).astype(np.uint8), rng.integers(0, 3, m).astype(np.uint8)
+    first = np.zeros(m, np.uint8)                            # every list row written at most once: its first owner only
+    seen = set()
+    for k in np.flatnonzero(owned):
+        if int(src[k]) not in seen:
+            seen.add(int(src[k]))
+            first[k] = 1
+    out = {"scores": _Guarded(M * ncls * 4, GUARD, 0xFF), "pred": _Guarded(M, GUARD, 0xFF), "ana": _Guarded(M, GUARD, 0xFF)}
+    keep = [_dev(a) for a in (src.astype(np.int32), first, scores, pred, ana)]
+    P = lambda t: ctypes.c_void_p(t.ptr if isinstance(t, _Guarded) else t.data_ptr())
+    torch.cuda.synchronize()
+    _lib.check(lib.ursn_scores_scatter(P(keep[0]), P(keep[1]), m, ncls, P(keep[2]), P(keep[3]), P(keep[4]), P(out["scores"]),
+                                       P(out["pred"]), P(out["ana"]), M, None))
+    torch.cuda.synchronize()
+    ref = {"scores": np.full((M, ncls), 0xFFFFFFFF, np.uint32), "pred": np.full(M, 0xFF, np.uint8), "ana": np.full(M, 0xFF, np.uint8)}
+    tiling.stitch_numpy(ref, src, first, scores=scores.view(np.uint32), pred=pred, ana=ana)
+    assert len(seen) > 50
+    for n, g in out.items():
+        assert g.guards_intact() == (True, True), n
+        assert np.array_equal(g.view.cpu().numpy().view(ref[n].dtype).reshape(ref[n].shape), ref[n]), n
 
 
 # ---- net level ----------------------------------------------------------------------------------------------------------------------
